@@ -6,12 +6,21 @@ at N=8. Rank 0 holds the batch inputs and the proofs: it scatters packed inputs 
 gathers the proof bytes back over RCCL (torch.distributed "nccl" backend), the only exchange
 step of the path; each rank proves its shard with libxfgstark.so (weak scaling).
 
-Prints ONE JSON line (rank 0) with `roofline` (trace-LDE kernel pair, HIP-event timed on the
-prover's stream), `whole_proof` (SURVEY 8(d)'s per-proof algorithmic bytes x proofs/s against the
-HBM peak), `verified` (every proof of the last timed step, gathered on rank 0, accepted by the GPU
-batch verifier against its statement -- the run fails otherwise), `verify` (batch-verify
-throughput, GPU vs host threads) and `cpu_baseline` (the oracle C restatement on the host cores:
-1 thread in the reference-faithful per-row Keccak mode, and all cores with OpenMP).
+A plain run sets up, warms up, times the steps and prints ONE JSON line (rank 0): the headline
+figure (`value`, `ms_per_step`), the run's `config`, and what the timed steps themselves recorded
+(`exchange`, `host_load`). `--dump-outputs DIR` also writes the last timed step's proofs as .npy
+files (dump_outputs), so that two builds can be compared output for output: the inputs depend on the
+arguments alone.
+
+`--full` adds every side measurement and check to the line, each a run of its own after the timed
+steps (the trace-LDE HIP events are the one exception: they are recorded inside the timed steps,
+and only then): `roofline` (trace-LDE kernel pair, HIP-event timed on the prover's stream),
+`whole_proof` (SURVEY 8(d)'s per-proof algorithmic bytes x proofs/s against the HBM peak),
+`verified` (every proof of the last timed step, gathered on rank 0, accepted by the GPU batch
+verifier against its statement -- the run fails otherwise), `verify` (batch-verify throughput, GPU
+vs host threads), `single_proof` (configs[1]), `config5` (configs[4]) and `cpu_baseline` (the oracle
+C restatement on the host cores: 1 thread in the reference-faithful per-row Keccak mode, and all
+cores with OpenMP).
 """
 import argparse
 import json
@@ -681,6 +690,31 @@ def verify_rate(prover, proofs, inputs, threads=16, reps=3):
             "host_proofs_per_s": round(len(items) / best["host"], 1), "host_threads": threads}
 
 
+DUMP_ROW_BYTES = 48 << 20  # --dump-outputs: float32 bytes of proof rows written (the files stay under 64 MB)
+
+
+def dump_outputs(path, proofs):
+    """--dump-outputs: the proofs of the last timed step as the caller of the timed path holds them on
+    rank 0 (all ranks' shards in rank order), as three .npy files under `path`:
+    proofs.npy float32 [k, longest]: one proof per row, one byte per element (0..255), zero-padded;
+    proof_lengths.npy float64 [k]: the rows' proof lengths in bytes;
+    proof_index.npy float64 [k]: each row's position in the step.
+    Every proof when the rows fit DUMP_ROW_BYTES, else a fixed (seeded) sample of them, in step order."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    width = max(len(p) for p in proofs)
+    k = max(1, min(len(proofs), DUMP_ROW_BYTES // (4 * width)))
+    idx = np.arange(len(proofs))
+    if k < len(proofs):
+        idx = np.sort(np.random.default_rng(0).choice(len(proofs), k, replace=False))
+    rows = np.zeros((k, width), dtype=np.float32)
+    for r, i in enumerate(idx):
+        rows[r, :len(proofs[i])] = np.frombuffer(proofs[i], dtype=np.uint8)
+    np.save(os.path.join(path, "proofs.npy"), rows)
+    np.save(os.path.join(path, "proof_lengths.npy"), np.array([len(proofs[i]) for i in idx], dtype=np.float64))
+    np.save(os.path.join(path, "proof_index.npy"), idx.astype(np.float64))
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -845,21 +879,81 @@ def check_world(gpus, env):
     return world
 
 
+def side_measurements(args, prover, gpu, world, last, inputs, proofs_per_s, pipe):
+    """--full, rank 0, after the timed steps: the fields of the line that take runs of their own.
+    `last` / `inputs`: the proofs of the last timed step and their inputs; `pipe`: lde_probe's
+    (ms, launch sets, polynomials) of the timed steps"""
+    n, per = 1 << args.log_n, args.per_gpu
+    # one synchronous batch call (no pipelining), for reference
+    t = time.perf_counter()
+    prover.prove_batch(inputs[:per], trace_length=n)
+    sync_call_ms = (time.perf_counter() - t) * 1e3
+
+    # BASELINE configs[1]: ONE proof of this shape through xfg_prove_burn_mint, synchronous (the
+    # reference's prove_burn_mint, src/burn_mint_prover.rs:62-129): best of 10 after a warm call
+    single = single_proof(prover, n)
+
+    # ---- roofline: trace LDE kernel pair, algorithmic bytes 8*w*(n+N) per proof, timed over a window
+    # of >= 150 ms of back-to-back launch sets: the chip's clock settles only after ~30 ms of load
+    # (DESIGN.md section 7, profiles/r04/lde_ramp.txt), so a short window mostly measures the transient
+    lde_ms = prover.bench_lde(per, n, BLOWUP, LDE_ITERS)
+    lde_bytes = 8 * WIDTH * (n + n * BLOWUP) * per
+    achieved = lde_bytes / (lde_ms * 1e-3) / 1e9
+    pmc, traffic_src = pmc_record(per, n, BLOWUP)
+    traffic = pmc["traffic_bytes"] if pmc else None
+    prover.set_timing(True)
+    prover.prove_batch([synthetic.burn_inputs(i) for i in range(per)], trace_length=n)
+    prover_stage = {k: round(v, 3) for k, v in prover.stage_times().items()}
+    prover.set_timing(False)
+    vrate = verify_rate(prover, last[:per], inputs[:per])
+    c5 = None if args.no_config5 else config5(prover, gpu)
+    out = {
+        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                     "frac": round(achieved / PEAK_HBM_GBS, 4), "traffic": traffic,
+                     "traffic_source": traffic_src,
+                     # the kernel is VALU-issue-bound (DESIGN.md section 4): the same launch set
+                     # against the VALU ceiling, instruction counts from the same PMC record
+                     "valu": valu_roofline(pmc, lde_ms, WIDTH * per * n * BLOWUP),
+                     "kernel": "trace LDE (ntt_pass_a_cos2 + ntt_pass_b_tq<8,8,4,split>), 7 columns x "
+                               f"{per} proofs, {lde_ms:.3f} ms/launch-set, {lde_bytes} algorithmic B",
+                     "window": f"{LDE_ITERS} back-to-back launch sets after one warm launch, HIP events",
+                     # the same launch sets inside the timed pipelined steps (per XFG_UNIT-proof unit,
+                     # sharing the GPU with the other lanes' kernels)
+                     "in_pipeline": in_pipeline(*pipe, n)},
+        "whole_proof": whole_proof_line(proofs_per_s, n, world),
+        "verify": vrate,
+        "stage_ms_one_batch": prover_stage,
+        "sync_prove_batch_ms": round(sync_call_ms, 3),
+        "single_proof": single,
+    }
+    if c5:
+        out["config5"] = c5
+    if world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1,
                     help="GPUs = ranks; N > 1 without a launcher starts torch.distributed.run itself")
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=100, help="timed steps")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--per-gpu", type=int, default=64)
     ap.add_argument("--log-n", type=int, default=LOG_N)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every side measurement and check (the proofs of the "
+                         "last step verified, roofline, single proof, batch verify, configs[4], CPU baseline)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the last timed step's proofs to DIR as .npy files (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-config5", action="store_true", help="skip the configs[4] side measurement")
+    ap.add_argument("--no-config5", action="store_true",
+                    help="with --full: skip the configs[4] side measurement")
     ap.add_argument("--depth", type=int, default=6, help="batches in flight (pipelined submission)")
     ap.add_argument("--dist", action="store_true",
                     help="run the scatter / gather collectives even at world size 1 (exercises the RCCL "
-                         "path on a one-GPU box; launch with torch.distributed.run); rank 0 then also "
+                         "path on a one-GPU box; launch with torch.distributed.run); with --full rank 0 also "
                          "checks the gathered proofs byte for byte against a direct prove_batch")
     ap.add_argument("--dump-proofs", default=None,
                     help="rank 0 writes the last step's gathered proofs here (u32 LE length + bytes each)")
@@ -868,6 +962,8 @@ def main():
                          "records per step over RCCL (its own, then copies), as rank 0 does at N = this "
                          "(rehearses the N = 8 exchange load on one GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
     world = check_world(args.gpus, os.environ)
@@ -940,7 +1036,8 @@ def main():
         pipelined_steps(submit_fn, collect_fn, batches[:args.warmup], args.depth, ex,
                         packed[:args.warmup] if packed else None)
     barrier()
-    prover.lde_probe(True)  # HIP events around every trace-LDE launch set inside the timed steps
+    if args.full:
+        prover.lde_probe(True)  # HIP events around every trace-LDE launch set inside the timed steps
     ru0 = resource.getrusage(resource.RUSAGE_SELF)
     t0 = time.perf_counter()
     out = pipelined_steps(submit_fn, collect_fn, batches[args.warmup:], args.depth, ex,
@@ -964,19 +1061,24 @@ def main():
     if dist is not None:
         dist.all_reduce(el_t, op=dist.ReduceOp.MAX)
     el = float(el_t.item())
-    pipe_ms, pipe_sets, pipe_polys = prover.lde_probe(False)
-    verified = None
-    if rank == 0:
+    pipe = prover.lde_probe(False) if args.full else None
+    verified, last = None, None
+    if rank == 0 and (args.full or args.dump_proofs or args.dump_outputs):
         last = [bytes(x) for x in out]
         if ex is not None and ex.rows != world:  # emulated ranks: the stand-in peer rows
-            peer = last[per:2 * per]
-            assert len(last) == ex.rows * per and all(last[q * per:(q + 1) * per] == peer for q in range(1, ex.rows))
+            if args.full:
+                peer = last[per:2 * per]
+                assert len(last) == ex.rows * per and all(last[q * per:(q + 1) * per] == peer
+                                                          for q in range(1, ex.rows))
             last = last[:per]
         assert len(last) == per * world
         if args.dump_proofs:
             with open(args.dump_proofs, "wb") as f:
                 for p in last:
                     f.write(len(p).to_bytes(4, "little") + p)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last)
+    if rank == 0 and args.full:
         # every proof of the last timed step (all ranks' shards, gathered in rank order) against the
         # statement of the input it was scattered for: a sharding or ordering bug fails the run
         verified = verify_proofs(prover, last, batches[-1])
@@ -988,35 +1090,11 @@ def main():
 
     if ex is not None:
         ex.close()
-    if rank != 0:  # the side measurements below are rank 0's
+    if rank != 0:  # the line, and with --full the side measurements below, are rank 0's
         prover.close()
         dist.barrier()
         dist.destroy_process_group()
         return
-
-    # one synchronous batch call (no pipelining), for reference
-    t = time.perf_counter()
-    prover.prove_batch(batches[-1][:per], trace_length=n)
-    sync_call_ms = (time.perf_counter() - t) * 1e3
-
-    # BASELINE configs[1]: ONE proof of this shape through xfg_prove_burn_mint, synchronous (the
-    # reference's prove_burn_mint, src/burn_mint_prover.rs:62-129): best of 10 after a warm call
-    single = single_proof(prover, n)
-
-    # ---- roofline: trace LDE kernel pair, algorithmic bytes 8*w*(n+N) per proof, timed over a window
-    # of >= 150 ms of back-to-back launch sets: the chip's clock settles only after ~30 ms of load
-    # (profiles/r04/lde_ramp.txt), so a short window mostly measures the transient
-    lde_ms = prover.bench_lde(per, n, BLOWUP, LDE_ITERS)
-    lde_bytes = 8 * WIDTH * (n + n * BLOWUP) * per
-    achieved = lde_bytes / (lde_ms * 1e-3) / 1e9
-    pmc, traffic_src = pmc_record(per, n, BLOWUP)
-    traffic = pmc["traffic_bytes"] if pmc else None
-    prover.set_timing(True)
-    prover.prove_batch([synthetic.burn_inputs(i) for i in range(per)], trace_length=n)
-    prover_stage = {k: round(v, 3) for k, v in prover.stage_times().items()}
-    prover.set_timing(False)
-    vrate = verify_rate(prover, last[:per], batches[-1][:per])
-    c5 = None if args.no_config5 else config5(prover, gpu)
 
     total = per * world * args.steps
     line = {
@@ -1055,29 +1133,10 @@ def main():
         # every rank's host CPU over the timed window (getrusage, all threads): whether the host was
         # the limit of a rank (cpu_util near its `cpus`)
         "host_load": ranks,
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                     "frac": round(achieved / PEAK_HBM_GBS, 4), "traffic": traffic,
-                     "traffic_source": traffic_src,
-                     # the kernel is VALU-issue-bound: the same launch set
-                     # against the VALU ceiling, instruction counts from the same PMC record
-                     "valu": valu_roofline(pmc, lde_ms, WIDTH * per * n * BLOWUP),
-                     "kernel": "trace LDE (ntt_pass_a_cos2 + ntt_pass_b_tq<8,8,4,split>), 7 columns x "
-                               f"{per} proofs, {lde_ms:.3f} ms/launch-set, {lde_bytes} algorithmic B",
-                     "window": f"{LDE_ITERS} back-to-back launch sets after one warm launch, HIP events",
-                     # the same launch sets inside the timed pipelined steps (per XFG_UNIT-proof unit,
-                     # sharing the GPU with the other lanes' kernels)
-                     "in_pipeline": in_pipeline(pipe_ms, pipe_sets, pipe_polys, n)},
-        "whole_proof": whole_proof_line(total / el, n, world),
-        "verified": verified,
-        "verify": vrate,
-        "stage_ms_one_batch": prover_stage,
-        "sync_prove_batch_ms": round(sync_call_ms, 3),
-        "single_proof": single,
     }
-    if c5:
-        line["config5"] = c5
-    if world == 1 and not args.no_cpu_baseline:
-        line["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
+    if args.full:
+        line.update(side_measurements(args, prover, gpu, world, last, batches[-1], total / el, pipe))
+        line["verified"] = verified
     print(json.dumps(line), flush=True)
     prover.close()
     if dist is not None:

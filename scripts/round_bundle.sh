@@ -14,5 +14,6 @@ timeout -k 10 120 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun
 python3 scripts/single_proof.py --summary gpurun_out/single > gpurun_out/single_summary.txt
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.txt 2>&1 || { tail -5 gpurun_out/smoke.txt; exit 1; }
 cat gpurun_out/smoke.txt
-timeout -k 10 600 python3 bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err || { tail -5 gpurun_out/bench_default.err; exit 1; }
-python3 -c "import json; d=json.loads(open('gpurun_out/bench_default.json').read().strip().splitlines()[-1]); print(d['value'], d['roofline']['frac'], d['whole_proof']['frac'], (d.get('config5') or {}).get('proofs_per_s'), d['single_proof']['ms'])"
+B=$(dirname "$(ls -d */round | head -1)")/bench_default  # the bundle directory: where scripts/profile_round.sh put round/
+timeout -k 10 600 python3 bench.py --full > $B.json 2> $B.err || { tail -5 $B.err; exit 1; }
+python3 -c "import json, sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(d['value'], d['roofline']['frac'], d['whole_proof']['frac'], (d.get('config5') or {}).get('proofs_per_s'), d['single_proof']['ms'])" $B.json

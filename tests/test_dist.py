@@ -250,7 +250,7 @@ def test_bench_two_ranks_real_prover(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"),
            "--gpus", str(world), "--steps", str(steps), "--warmup", str(warmup), "--per-gpu", str(per),
-           "--log-n", "10", "--depth", "2", "--no-cpu-baseline", "--no-config5", "--dist",
+           "--log-n", "10", "--depth", "2", "--full", "--no-cpu-baseline", "--no-config5", "--dist",
            "--dump-proofs", str(dump)]
     env = dict(os.environ, XFG_DIST_BACKEND="gloo")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=root, env=env)
@@ -317,7 +317,7 @@ def test_bench_rccl_collectives_one_rank():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"),
            "--gpus", "1", "--steps", "2", "--warmup", "1", "--per-gpu", "8", "--depth", "2",
-           "--no-cpu-baseline", "--no-config5", "--dist"]
+           "--full", "--no-cpu-baseline", "--no-config5", "--dist"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=110, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -347,7 +347,7 @@ def test_config3_eight_ranks_real_prover(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"),
            "--gpus", str(world), "--steps", str(steps), "--warmup", str(warmup), "--per-gpu", str(per),
-           "--log-n", "16", "--depth", "2", "--no-cpu-baseline", "--no-config5", "--dist",
+           "--log-n", "16", "--depth", "2", "--full", "--no-cpu-baseline", "--no-config5", "--dist",
            "--dump-proofs", str(dump)]
     # 3 lanes per rank: 8 contexts share the card's memory and hardware queues
     env = dict(os.environ, XFG_DIST_BACKEND="gloo", XFG_LANES="3", OMP_NUM_THREADS="2")
@@ -525,7 +525,7 @@ def test_bench_gpus_two_without_launcher():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--per-gpu", "8", "--log-n", "10",
-           "--steps", "2", "--warmup", "1", "--depth", "2", "--no-cpu-baseline", "--no-config5"]
+           "--steps", "2", "--warmup", "1", "--depth", "2", "--full", "--no-cpu-baseline", "--no-config5"]
     env = dict(os.environ, XFG_DIST_BACKEND="gloo")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
@@ -553,7 +553,7 @@ def test_bench_emulated_eight_rank_gather():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"),
            "--gpus", "1", "--steps", "3", "--warmup", "1", "--per-gpu", "8", "--depth", "2", "--log-n", "10",
-           "--no-cpu-baseline", "--no-config5", "--dist", "--emulate-ranks", "8"]
+           "--full", "--no-cpu-baseline", "--no-config5", "--dist", "--emulate-ranks", "8"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=110, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -577,3 +577,68 @@ def test_bench_roofline_records():
     assert w and w["ceiling_T_lane_instr_s"] > 36 and 0 < w["frac"] < 1 and w["source"].endswith("valu_per_proof.json")
     assert bench.whole_proof_valu(14000.0, 1 << 20, 1) is None  # the ledger is for configs[2] only
     assert bench.whole_proof_valu(28000.0, 1 << 16, 2)["ceiling_T_lane_instr_s"] == 2 * w["ceiling_T_lane_instr_s"]
+
+
+def test_dump_outputs_files(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 rows of proof bytes, their lengths and step positions; the
+    proofs read back byte for byte; over the size budget, a fixed sample in step order"""
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+
+    def read(d):
+        rows, lens, idx = (np.load(os.path.join(d, f + ".npy")) for f in ("proofs", "proof_lengths", "proof_index"))
+        assert rows.dtype == np.float32 and lens.dtype == np.float64 and idx.dtype == np.float64
+        return [bytes(r[:int(ln)].astype(np.uint8)) for r, ln in zip(rows, lens)], [int(i) for i in idx], rows
+
+    proofs = [bytes([200 + i]) * (5 + i) + b"\0" for i in range(6)]
+    bench.dump_outputs(str(tmp_path / "a"), proofs)
+    got, idx, rows = read(tmp_path / "a")
+    assert got == proofs and idx == list(range(6)) and rows.shape == (6, 11)
+    monkeypatch.setattr(bench, "DUMP_ROW_BYTES", 3 * 4 * 11)  # room for three rows
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), proofs)
+    got, idx, rows = read(tmp_path / "b")
+    assert rows.shape == (3, 11) and idx == sorted(set(idx)) and got == [proofs[i] for i in idx]
+    assert read(tmp_path / "c")[1] == idx
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """a plain bench.py run (no --full): the line holds the headline figure of exactly --steps timed
+    steps and none of the side measurements, and --dump-outputs writes the last timed step's proofs --
+    here the first and the last of them must equal the oracle's bytes for that step's inputs"""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    import oracle_lib as O
+    import synthetic
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    per, steps, warmup, n = 8, 2, 1, 1024
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup",
+           str(warmup), "--per-gpu", str(per), "--log-n", "10", "--depth", "2", "--dump-outputs", str(tmp_path / "out")]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=110, cwd=root, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [x for x in r.stdout.strip().splitlines() if x.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == steps and line["warmup"] == warmup and line["ms_per_step"] > 0
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 - per) < 1e-6 * per
+    assert (line["unit"], line["higher_is_better"], line["dtype"]) == ("proofs/s", True, "u64")
+    for k in ("roofline", "whole_proof", "verified", "verify", "single_proof", "config5", "cpu_baseline"):
+        assert k not in line, k
+    rows = np.load(tmp_path / "out" / "proofs.npy")
+    lens = np.load(tmp_path / "out" / "proof_lengths.npy")
+    idx = np.load(tmp_path / "out" / "proof_index.npy")
+    assert rows.dtype == np.float32 and rows.shape[0] == per and list(idx) == list(range(per))
+    for i in (0, per - 1):
+        kw = synthetic.burn_inputs((warmup + steps - 1) * per + i)
+        st, air = O.air_from_inputs(kw["burn_amount"], kw["mint_amount"], kw["tx_prefix_hash"],
+                                    kw["recipient_address"], kw["secret"])
+        st2, want = O.prove(air, n, O.options())
+        assert st == 0 and st2 == 0
+        assert bytes(rows[i, :int(lens[i])].astype(np.uint8)) == want, i
