@@ -98,7 +98,8 @@ size_t xfg_proof_size_bound(uint64_t trace_length, const xfg_options* opts);
 /* prove_burn_mint; trace_length 0 -> 64 (the reference's fixed TraceInfo::new(7, 64)) */
 int xfg_prove_burn_mint(xfg_ctx* ctx, const xfg_burn_inputs* in, uint64_t trace_length, const xfg_options* opts,
                         uint8_t* out, size_t* out_len);
-/* prove over a caller-supplied execution trace, column-major [width][n], width must be 7 */
+/* prove over a caller-supplied execution trace, column-major [width][n], width must be 7; trace cells
+ * and AIR constants must be canonical field elements (< p), else XFG_INVALID_ARGUMENT */
 int xfg_prove_trace(xfg_ctx* ctx, const uint64_t* trace, uint32_t width, uint64_t n, const xfg_air_consts* air,
                     const xfg_options* opts, uint8_t* out, size_t* out_len);
 /* batch of independent proofs on this context's device; statuses[i] per proof, returns XFG_OK if
@@ -187,7 +188,11 @@ int xfg_debug_interpolate(xfg_ctx* ctx, const uint64_t* evals, uint32_t npoly, u
  * 2 sub, 3 canonical(a), 4 a * 2^(b mod 96), 5 a + (b mod 2^32) * (2^32 - 1), 6 a - b with one
  * borrow fold (the weak subtraction of the NTT butterflies), 7 a + b with one carry fold (the weak
  * addition of the NTT butterflies, b < p), 8 a * b through the interleaved pair multiply (gl_mul2:
- * both a * b and b * a computed, all ones returned if they differ) */
+ * both a * b and b * a computed, all ones returned if they differ).
+ * Ops 9..12 read consecutive elements as pairs, x = (a[2i], a[2i+1]), y = (b[2i], b[2i+1]), and write
+ * out[2i], out[2i+1] (count must be even): 9 one gl_mul2 on the unrelated products a[2i] * b[2i] and
+ * a[2i+1] * b[2i+1] (any u64 operands), and on canonical operands 10 e2_mul(x, y) in the quadratic
+ * extension, 11 e2_mulb(x, b[2i]), 12 e2_inv(x) ((0, 0) for x = (0, 0)) */
 int xfg_debug_field(xfg_ctx* ctx, uint32_t op, uint64_t count, const uint64_t* a, const uint64_t* b, uint64_t* out);
 /* OOD evaluation + DEEP quotient kernels of the prover on `count` instances: coef [count][7][n],
  * hcoef [count][n] (trace / composition coefficients), zpts [count][2] = (z, z g), coeffs
@@ -195,6 +200,21 @@ int xfg_debug_field(xfg_ctx* ctx, uint32_t op, uint64_t count, const uint64_t* a
  * T_c(zg) interleaved, H(z)), deep_out [count][n] (DEEP composition coefficients) */
 int xfg_debug_ood_deep(xfg_ctx* ctx, uint32_t count, uint64_t n, const uint64_t* coef, const uint64_t* hcoef,
                        const uint64_t* zpts, const uint64_t* coeffs, uint64_t* ood_out, uint64_t* deep_out);
+/* constraint evaluation kernel of the prover on `count` instances, through the calls prove_lane
+ * makes (column interpolation, trace LDE at `blowup`, the host-built divisor table, the kernel):
+ * trace [count][7][n] canonical, airs [count], coeffs [count][15][ext] = 7 transition, 7 step-0
+ * boundary and the final-step boundary coefficient, E elements (ext 1 or 2 coordinates each);
+ * ce [count][ext][2n] coordinate planes in natural CE-domain order (index i <-> x = 7 w_2n^i) */
+int xfg_debug_constraint_eval(xfg_ctx* ctx, uint32_t count, uint64_t n, uint32_t blowup, uint32_t ext,
+                              const uint64_t* trace, const xfg_air_consts* airs, const uint64_t* coeffs,
+                              uint64_t* ce);
+/* FRI fold kernel (folding factor 8, domain offset 7) on `count` layers of D = 2^(logn + logbeta)
+ * E values: vals [count][ext][D] coordinate planes, natural order, or coset-major (natural index K
+ * stored at (K mod beta) n + K / beta, the layout of the first layer) when coset_major != 0;
+ * alpha [count][ext] (the entry forms alpha * 7^-1 on the host); out [count][ext][D / 8].
+ * All inputs canonical; D >= 16 */
+int xfg_debug_fri_fold(xfg_ctx* ctx, uint32_t count, uint32_t ext, uint32_t logn, uint32_t logbeta, int coset_major,
+                       const uint64_t* vals, const uint64_t* alpha, uint64_t* out);
 /* device Fiat-Shamir draws (DefaultRandomCoin<Blake3_256>::draw::<E>) from the coin (seed as 8 LE
  * u32 words, counter): k <= 64 draws of E (ext 1 or 2) by one wave -- the prover's coefficient and
  * DEEP draws -- and one at a time -- its FRI alpha draws. Besides the >= p rule, a candidate whose

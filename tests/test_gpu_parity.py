@@ -116,10 +116,57 @@ def _field_inputs(canonical, seed):
     return a, b
 
 
-@pytest.mark.parametrize("op", ["mul", "add", "sub", "canon", "pow2", "fold", "sub_weak", "add_w", "mul2"])
+def _pair_inputs(canonical, seed):
+    """operands of the paired ops as interleaved arrays: the first words (a[2i], b[2i]) run through
+    the edge list crossed with itself, the second words (a[2i+1], b[2i+1]) through an independently
+    shuffled copy of the same cross, so the two halves of a pair are unrelated; plus 20000 random
+    pairs, and the pairs with zero words ((0, 0), (x, 0), (0, x))"""
+    rng = random.Random(seed)
+    vals = [v for v in _EDGE if not canonical or v < P_GL]
+    top = P_GL if canonical else 1 << 64
+    first = [(x, y) for x in vals for y in vals]
+    second = list(first)
+    rng.shuffle(second)
+    quads = [(x0, x1, y0, y1) for (x0, y0), (x1, y1) in zip(first, second)]
+    quads += [(0, 0, 0, 0), (0, 0, 5, 7), (5, 0, 3, 0), (0, 5, 0, 3), (P_GL - 1, 0, 0, P_GL - 1), (0, 1, 0, 1)]
+    quads += [tuple(rng.randrange(top) for _ in range(4)) for _ in range(20000)]
+    a = [w for q in quads for w in q[:2]]
+    b = [w for q in quads for w in q[2:]]
+    return quads, a, b
+
+
+def _check_pair_op(prover, op):
+    import plain_ref as R
+    quads, a, b = _pair_inputs(op != "mul2_pair", sum(op.encode()))
+    got = prover.debug_field(op, np.array(a, dtype=np.uint64), np.array(b, dtype=np.uint64)).tolist()
+    assert len(got) == 2 * len(quads)
+    for k, (x0, x1, y0, y1) in enumerate(quads):
+        r = (got[2 * k], got[2 * k + 1])
+        if op == "mul2_pair":  # two unrelated products through one gl_mul2, any u64 operands
+            want = (x0 * y0 % P_GL, x1 * y1 % P_GL)
+        elif op == "e2_mul":
+            want = R.e_mul((x0, x1), (y0, y1))
+        elif op == "e2_mulb":
+            want = (x0 * y0 % P_GL, x1 * y0 % P_GL)
+        else:  # e2_inv: x * out = 1 by the schoolbook product; 0 -> 0
+            assert r[0] < P_GL and r[1] < P_GL, (op, x0, x1, r)
+            want = (0, 0) if (x0, x1) == (0, 0) else (1, 0)
+            assert R.e_mul((x0, x1), r) == want, (op, x0, x1, r)
+            if (x0, x1) == (0, 0):
+                assert r == (0, 0)
+            continue
+        assert r == want, (op, (x0, x1), (y0, y1), r, want)
+
+
+@pytest.mark.parametrize("op", ["mul", "add", "sub", "canon", "pow2", "fold", "sub_weak", "add_w", "mul2", "mul2_pair",
+                                "e2_mul", "e2_mulb", "e2_inv"])
 def test_field_primitives_match_bigint(prover, op):
     """the gfx950 inline-asm Goldilocks primitives (gl.hpp) against Python integers, edge values
-    (0, 2^32 - 1, p - 1, p, 2^64 - 1, ...) crossed with each other plus random operands"""
+    (0, 2^32 - 1, p - 1, p, 2^64 - 1, ...) crossed with each other plus random operands; the paired
+    ops (mul2_pair: one gl_mul2 on two unrelated products; e2_mul / e2_mulb / e2_inv of the quadratic
+    extension, built on it) against the schoolbook product of plain_ref, both output words"""
+    if op in ("mul2_pair", "e2_mul", "e2_mulb", "e2_inv"):
+        return _check_pair_op(prover, op)
     canonical_in = op in ("add", "sub")
     a, b = _field_inputs(canonical_in, sum(op.encode()))
     if op == "pow2":
@@ -283,6 +330,11 @@ def test_submitted_batches_in_flight_match_oracle(prover):
     pend = [prover.submit_batch(kws, trace_length=n) for n, kws in plan]
     with pytest.raises(xfgstark.XfgStarkError):  # lane 0 belongs to the workers meanwhile
         prover.debug_lde(np.zeros((1, 8), dtype=np.uint64), 8, 2)
+    with pytest.raises(xfgstark.XfgStarkError, match="batches pending"):
+        prover.debug_constraint_eval(np.zeros((1, 7, 8), dtype=np.uint64), [([0] * 12, 0, 0)],
+                                     np.zeros((1, 15, 1), dtype=np.uint64), 2)
+    with pytest.raises(xfgstark.XfgStarkError, match="batches pending"):
+        prover.debug_fri_fold(np.zeros((1, 1, 16), dtype=np.uint64), np.zeros((1, 1), dtype=np.uint64), 4, 0, False)
     for (n, kws), pb in reversed(list(zip(plan, pend))):
         res = pb.result()
         assert len(res) == len(kws)
@@ -371,6 +423,238 @@ def test_invalid_trace_same_outcome_as_oracle(prover):
     else:
         with pytest.raises(xfgstark.XfgStarkError):
             prover.prove_trace(trace, list(air.pub), air.nullifier, air.commitment)
+
+
+_KINDS = ["random", "edge", "wide_consts"]
+
+
+def _air_of(air):
+    """O.Air filled field by field from (pub[12], nullifier, commitment)"""
+    oa = O.Air()
+    for i in range(12):
+        oa.pub[i] = air[0][i]
+    oa.secret = 0
+    oa.nullifier = air[1]
+    oa.commitment = air[2]
+    return oa
+
+
+def _arbitrary_case(ext, n, blowup, kind):
+    """seeded arbitrary trace (plain_ref.make_trace) with its statement and the oracle's options"""
+    import plain_ref as R
+    tr, air = R.make_trace(kind, n, 7000 + 100 * ext + 3 * n + blowup + _KINDS.index(kind))
+    flat = (O.C.c_uint64 * (7 * n))(*[v for col in tr for v in col])
+    return tr, air, _air_of(air), flat, O.options(blowup=blowup, field_extension=ext)
+
+
+@pytest.mark.parametrize("kind", _KINDS)
+@pytest.mark.parametrize("n,blowup", [(8, 8), (64, 2), (256, 8), (1024, 16)])
+@pytest.mark.parametrize("ext", [1, 2])
+def test_prove_arbitrary_trace_bytes_match_oracle(prover, ext, n, blowup, kind):
+    """proofs of FALSE statements: traces that are no burn traces (uniformly random cells; edge
+    values with d and d - 1 at 0, 1, p - 1; 64-bit AIR constants up to p - 1 with single constraints
+    vanishing), so every transition expression, boundary numerator and composition coefficient
+    contributes to the bytes -- on a valid trace six columns are constants and most of them are
+    identically zero. The GPU proof equals the oracle's byte for byte, and the oracle verifier, the
+    host verifier and the GPU batch verifier all reject it"""
+    import xfgstark
+    tr, air, oa, flat, opts = _arbitrary_case(ext, n, blowup, kind)
+    st, want = O.prove(oa, n, opts, trace=flat)
+    assert st == 0
+    o = xfgstark.ProofOptions.reference()
+    o.blowup_factor, o.field_extension = blowup, ext
+    prover._options = o
+    got = prover.prove_trace(np.array(tr, dtype=np.uint64), air[0], air[1], air[2]).to_bytes()
+    assert got == want
+    assert O.verify(oa, got, opts) != 0
+    v = xfgstark.XfgBurnMintVerifier(proof_options=o)
+    assert v.batch_verify([(got, air)]) == [False]
+    assert v.batch_verify([(got, air)], gpu=prover) == [False]
+
+
+def _ce_coeffs(style, ext, rng):
+    """15 composition coefficients (E tuples): random, edge-valued, or -- with an extension -- with one
+    coordinate zero, alternating"""
+    import plain_ref as R
+    out = []
+    for k in range(15):
+        if style == "random":
+            c = (rng.randrange(P), rng.randrange(P))
+        elif style == "edge":
+            c = (rng.choice(EDGE), rng.choice(EDGE))
+        else:  # zero coordinates (and a zero coefficient)
+            c = [(rng.randrange(P), 0), (0, rng.randrange(P)), (0, 0), (R.P - 1, 0), (0, 1)][(k + rng.randrange(5)) % 5]
+        out.append(c if ext == 2 else (c[0], 0))
+    return out
+
+
+def _run_constraint_eval(prover, traces, airs, coeffs, blowup, ext):
+    """-> per instance, the kernel's 2n E tuples"""
+    co = np.array([[list(c[:ext]) for c in cs] for cs in coeffs], dtype=np.uint64)
+    ce = prover.debug_constraint_eval(np.array(traces, dtype=np.uint64), airs, co, blowup)
+    assert ce.shape == (len(traces), ext, 2 * len(traces[0][0]))
+    return [[(int(ce[b, 0, i]), int(ce[b, 1, i]) if ext == 2 else 0) for i in range(ce.shape[2])]
+            for b in range(len(traces))]
+
+
+@pytest.mark.parametrize("n,blowup,count", [(8, 2, 1), (8, 16, 2), (128, 8, 1), (256, 4, 2), (512, 2, 3)])
+@pytest.mark.parametrize("ext", [1, 2])
+def test_constraint_eval_kernel_matches_reference(prover, ext, n, blowup, count):
+    """constraint_eval_kernel behind the prover's own interpolation, LDE and batch-inverted divisor
+    table, against plain_ref.constraint_evals at every point of the CE domain. Shapes: a block smaller
+    than a wavefront with beta / 2 = 1 (8, 2); nce = 256, exactly one block (128); one block per
+    parity (256); four blocks and three instances (512: the blockIdx.y strides of air, coeffs, lde,
+    ce). Three calls per shape rotate the trace kinds over the instances with random, edge-valued and
+    zero-coordinate coefficients"""
+    import plain_ref as R
+    rng = random.Random(n * 64 + blowup * 4 + ext)
+    for call, style in enumerate(["random", "edge", "zeros"]):
+        made = [R.make_trace(_KINDS[(call + b) % 3], n, rng.randrange(1 << 30)) for b in range(count)]
+        traces, airs = [m[0] for m in made], [m[1] for m in made]
+        coeffs = [_ce_coeffs(style, ext, rng) for _ in range(count)]
+        got = _run_constraint_eval(prover, traces, airs, coeffs, blowup, ext)
+        for b in range(count):
+            want = R.constraint_evals(traces[b], airs[b], coeffs[b])
+            bad = [i for i in range(2 * n) if got[b][i] != want[i]]
+            assert not bad, (style, b, bad[:8], [(got[b][i], want[i]) for i in bad[:2]])
+
+
+@pytest.mark.parametrize("ext", [1, 2])
+def test_constraint_eval_unit_coefficients_name_the_index(prover, ext):
+    """one coefficient at a time set to 1 (and to phi with an extension), the others 0, at n = 8: a
+    swapped or misread coefficient slot shows up under its own index"""
+    import plain_ref as R
+    n, blowup = 8, 4
+    tr, _ = R.make_trace("random", n, 41)
+    air = R.WIDE_AIR
+    units = [(k, u) for u in ([(1, 0), (0, 1)] if ext == 2 else [(1, 0)]) for k in range(15)]
+    coeffs = [[u if j == k else (0, 0) for j in range(15)] for k, u in units]
+    got = _run_constraint_eval(prover, [tr] * len(units), [air] * len(units), coeffs, blowup, ext)
+    wrong = [(k, u) for b, (k, u) in enumerate(units) if got[b] != R.constraint_evals(tr, air, coeffs[b])]
+    assert not wrong, f"coefficient slots (index, unit) evaluated wrongly: {wrong}"
+    zero = R.constraint_evals(tr, air, [(0, 0)] * 15)
+    assert all(got[b] != zero for b in range(len(units)))  # every slot contributes on this trace
+
+
+def _fold_set(name, D, ext, rng):
+    """D E-values in natural order for one fold instance"""
+    R8 = D // 8
+    hi = (1 << 64) - (1 << 32)
+
+    def plane(flip):
+        if name == "random":
+            return [rng.randrange(P) for _ in range(D)]
+        if name == "all_pm1":
+            return [P - 1] * D
+        if name == "one_per_row":  # row i holds indices i + k D/8
+            v = [0] * D
+            for i in range(R8):
+                v[i + rng.randrange(8) * R8] = rng.choice([1, P - 1, hi, rng.randrange(1, P)])
+            return v
+        if name == "alternating":  # alternates inside a row (k) and from row to row
+            return [P - 1 if (K + K // R8 + flip) % 2 == 0 else hi for K in range(D)]
+        return [rng.choice(EDGE) for _ in range(D)]
+    planes = [plane(0), plane(1) if ext == 2 else [0] * D]
+    return list(zip(*planes))
+
+
+def _run_fold(prover, sets, alphas, logn, logbeta, coset_major, ext):
+    import plain_ref as R
+    n, beta = 1 << logn, 1 << logbeta
+    stored = [R.to_coset_major(s, n, beta) if coset_major else s for s in sets]
+    vals = np.array([[[v[c] for v in s] for c in range(ext)] for s in stored], dtype=np.uint64)
+    al = np.array([list(a[:ext]) for a in alphas], dtype=np.uint64)
+    out = prover.debug_fri_fold(vals, al, logn, logbeta, coset_major)
+    assert out.shape == (len(sets), ext, (n * beta) // 8)
+    return out
+
+
+@pytest.mark.parametrize("logn,logbeta,coset_major", [(4, 0, False), (6, 0, False), (5, 1, True), (11, 0, False),
+                                                      (9, 3, True), (8, 4, True)])
+@pytest.mark.parametrize("ext", [1, 2])
+def test_fri_fold_kernel_matches_reference(prover, ext, logn, logbeta, coset_major):
+    """fri_fold_kernel (size-8 inverse DFT, canonicalisation, Horner in E, the 2^-3 scaling) against
+    the Lagrange interpolation of plain_ref.fold_row, every row. Shapes: D = 16 (a 2-thread block),
+    64 natural and coset-major, 2048 (256 rows: one full block), 4096 coset-major at beta 8 and 16
+    (two blocks). Inputs: random, all p - 1, one non-zero value per row, alternating p - 1 /
+    2^64 - 2^32, picks from EDGE; each with every alpha: random, 1, p - 1 and with an extension
+    (a, 0), (0, b), (p - 1, p - 1); two instances per launch"""
+    import plain_ref as R
+    D = 1 << (logn + logbeta)
+    rng = random.Random(D * 8 + logbeta * 2 + ext)
+    if ext == 2:
+        alphas = [(rng.randrange(P), rng.randrange(P)), (1, 0), (P - 1, 0), (rng.randrange(P), 0),
+                  (0, rng.randrange(1, P)), (P - 1, P - 1)]
+    else:
+        alphas = [(rng.randrange(P), 0), (1, 0), (P - 1, 0), (rng.choice(EDGE[4:]), 0)]
+    for name in ["random", "all_pm1", "one_per_row", "alternating", "edge"]:
+        for k in range(0, len(alphas), 2):
+            sets = [_fold_set(name, D, ext, rng) for _ in range(2)]
+            out = _run_fold(prover, sets, alphas[k:k + 2], logn, logbeta, coset_major, ext)
+            for b in range(2):
+                want = R.fold_layer(sets[b], D, alphas[k + b])
+                got = [(int(out[b, 0, i]), int(out[b, 1, i]) if ext == 2 else 0) for i in range(D // 8)]
+                bad = [i for i in range(D // 8) if got[i] != want[i]]
+                assert not bad, (name, alphas[k + b], bad[:8], [(got[i], want[i]) for i in bad[:2]])
+
+
+def test_fri_fold_kernel_first_layer_of_config2_sampled(prover):
+    """D = 2^19 coset-major at beta 8 (the first FRI layer of the n = 2^16 benchmark shape), no
+    extension: the kernel runs in full; the first and last row of each of its 256 blocks and 2048
+    seeded random rows are compared (a full Python reference at this size would take minutes)"""
+    import plain_ref as R
+    logn, logbeta = 16, 3
+    D, rows = 1 << 19, 1 << 16
+    rs = np.random.default_rng(19)
+    nat = rs.integers(0, P, size=D, dtype=np.uint64)
+    edge_at = rs.integers(0, D, size=D // 8)
+    nat[edge_at] = rs.choice(np.array(EDGE, dtype=np.uint64), size=D // 8)
+    K = np.arange(D)
+    stored = np.zeros(D, dtype=np.uint64)
+    stored[(K % 8) * (1 << logn) + K // 8] = nat  # natural index K at (K mod beta) n + K // beta
+    alpha = (random.Random(19).randrange(P), 0)
+    out = prover.debug_fri_fold(stored.reshape(1, 1, D), np.array([[alpha[0]]], dtype=np.uint64), logn, logbeta, True)
+    pick = sorted({b * 256 + e for b in range(rows // 256) for e in (0, 255)}
+                  | set(random.Random(20).sample(range(rows), 2048)))
+    bad = []
+    for i in pick:
+        want = R.fold_row([(int(nat[i + k * rows]), 0) for k in range(8)], i, D, alpha)
+        if (int(out[0, 0, i]), 0) != want:
+            bad.append(i)
+    assert not bad, bad[:16]
+
+
+def test_noncanonical_air_constants_and_debug_inputs_are_rejected(prover):
+    """xfg_prove_trace and the kernel-level hooks refuse values >= p with XFG_INVALID_ARGUMENT and a
+    message (the constraint kernel's subtractions are exact for canonical operands only); p - 1 is
+    accepted (wide_consts above)"""
+    import plain_ref as R
+    import xfgstark
+    with_blowup(prover, 8)
+    n = 8
+    tr, air = R.make_trace("random", n, 77)
+    trace = np.array(tr, dtype=np.uint64)
+    for bad in [([P if i == 5 else v for i, v in enumerate(air[0])], air[1], air[2]),
+                (air[0], P, air[2]), (air[0], air[1], (1 << 64) - 1)]:
+        with pytest.raises(xfgstark.XfgStarkError, match="AIR constant is not a canonical") as e:
+            prover.prove_trace(trace, bad[0], bad[1], bad[2])
+        assert e.value.status == 9
+        with pytest.raises(xfgstark.XfgStarkError, match="AIR constant is not a canonical") as e:
+            prover.debug_constraint_eval(trace[None], [bad], np.ones((1, 15, 1), dtype=np.uint64), 2)
+        assert e.value.status == 9
+    co = np.ones((1, 15, 2), dtype=np.uint64)
+    co[0, 14, 1] = P
+    with pytest.raises(xfgstark.XfgStarkError, match="not a canonical") as e:
+        prover.debug_constraint_eval(trace[None], [air], co, 2)
+    assert e.value.status == 9
+    vals, al = np.ones((1, 1, 16), dtype=np.uint64), np.ones((1, 1), dtype=np.uint64)
+    for v, a in [(np.where(np.arange(16) == 9, np.uint64(P), vals), al), (vals, al * np.uint64(P))]:
+        with pytest.raises(xfgstark.XfgStarkError, match="not a canonical") as e:
+            prover.debug_fri_fold(v, a, 4, 0, False)
+        assert e.value.status == 9
+    # the accepted neighbours: the same calls with canonical values run
+    assert prover.debug_fri_fold(vals, al, 4, 0, False).shape == (1, 1, 2)
+    assert prover.debug_constraint_eval(trace[None], [air], np.ones((1, 15, 2), dtype=np.uint64), 2).shape == (1, 2, 16)
 
 
 @pytest.mark.parametrize("logn,blowup", [(17, 8), (18, 8), (20, 16)])

@@ -1212,7 +1212,33 @@ __global__ void field_op_kernel(int op, const u64* a, const u64* b, u64* out, u6
     }
     out[i] = r;
 }
+// ops 9..12: one thread per pair x = (a[2i], a[2i+1]), y = (b[2i], b[2i+1]) -> out[2i], out[2i+1]
+__global__ void field_pair_op_kernel(int op, const u64* a, const u64* b, u64* out, u64 pairs) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= pairs) return;
+    const E2 x{a[2 * i], a[2 * i + 1]}, y{b[2 * i], b[2 * i + 1]};
+    E2 r{0, 0};
+    switch (op) {
+        case 9: {  // one gl_mul2 on two unrelated products
+            r = x;
+            gl_mul2(r.a, y.a, r.b, y.b);
+            break;
+        }
+        case 10: r = e2_mul(x, y); break;
+        case 11: r = e2_mulb(x, y.a); break;
+        case 12: r = e2_inv(x); break;
+        default: break;
+    }
+    out[2 * i] = r.a;
+    out[2 * i + 1] = r.b;
+}
 void launch_field_op(int op, const u64* a, const u64* b, u64* out, u64 count, hipStream_t s) {
+    if (op >= 9) {  // count is even (checked by the caller)
+        const u64 pairs = count / 2;
+        hipLaunchKernelGGL(field_pair_op_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, s, op, a, b, out,
+                           pairs);
+        return;
+    }
     hipLaunchKernelGGL(field_op_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, op, a, b, out, count);
 }
 

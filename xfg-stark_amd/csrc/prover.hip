@@ -1329,6 +1329,16 @@ static bool busy(xfg_ctx* c) {
     return !c->pending.empty();
 }
 
+// the kernels' subtractions (gl_sub) are exact for canonical operands only: host inputs are checked
+static bool all_canonical(const uint64_t* v, size_t k) {
+    for (size_t i = 0; i < k; i++)
+        if (v[i] >= P) return false;
+    return true;
+}
+static bool air_canonical(const xfg_air_consts* a) {
+    return all_canonical(a->pub_inputs, 12) && a->nullifier < P && a->commitment < P;
+}
+
 static int copy_out(xfg_ctx* c, const std::vector<uint8_t>& bytes, uint8_t* out, size_t* out_len) {
     if (!out_len) {
         c->err = "out_len is NULL";
@@ -1485,11 +1495,14 @@ int xfg_prove_trace(xfg_ctx* c, const uint64_t* trace, uint32_t width, uint64_t 
         c->err = std::string("Prover error: ") + m;
         return XFG_PROVER_ERROR;
     }
-    for (u64 i = 0; i < 7 * n; i++)
-        if (trace[i] >= P) {
-            c->err = "trace element is not a canonical field element";
-            return XFG_INVALID_ARGUMENT;
-        }
+    if (!all_canonical(trace, 7 * n)) {
+        c->err = "trace element is not a canonical field element";
+        return XFG_INVALID_ARGUMENT;
+    }
+    if (!air_canonical(air)) {  // the constraint kernel subtracts them from trace values
+        c->err = "AIR constant is not a canonical field element";
+        return XFG_INVALID_ARGUMENT;
+    }
     return guarded(c, [&]() -> int {
         HIPCHK(hipSetDevice(c->device));
         std::unique_ptr<Batch> bp(new Batch());
@@ -1793,7 +1806,7 @@ int xfg_debug_interpolate(xfg_ctx* c, const uint64_t* evals, uint32_t npoly, uin
 }
 
 int xfg_debug_field(xfg_ctx* c, uint32_t op, uint64_t count, const uint64_t* a, const uint64_t* b, uint64_t* out) {
-    if (!c || !a || !b || !out || op > 8 || count == 0) return XFG_INVALID_ARGUMENT;
+    if (!c || !a || !b || !out || op > 12 || count == 0 || (op >= 9 && count % 2)) return XFG_INVALID_ARGUMENT;
     if (busy(c)) {
         c->err = "batches pending: call xfg_batch_wait first";
         return XFG_INVALID_ARGUMENT;
@@ -1899,6 +1912,110 @@ int xfg_debug_ood_deep(xfg_ctx* c, uint32_t count, uint64_t n, const uint64_t* c
         HIPCHK(hipMemcpyAsync(L->dp.p, dps.data(), B * sizeof(DeepParams), hipMemcpyHostToDevice, s));
         launch_deep(L->coef.p, L->hcoef.p, L->dp.p, L->partial.p, L->carry.p, L->deep.p, logn, (int)B, 1, s);
         HIPCHK(hipMemcpyAsync(deep_out, L->deep.p, B * n * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return XFG_OK;
+    });
+}
+
+int xfg_debug_constraint_eval(xfg_ctx* c, uint32_t count, uint64_t n, uint32_t blowup, uint32_t ext,
+                              const uint64_t* trace, const xfg_air_consts* airs, const uint64_t* coeffs,
+                              uint64_t* ce) {
+    if (!c) return XFG_INVALID_ARGUMENT;
+    c->err.clear();
+    if (!trace || !airs || !coeffs || !ce || count == 0 || !is_pow2(n) || n < 8 || !is_pow2(blowup) || blowup < 2 ||
+        blowup > 16 || (ext != 1 && ext != 2)) {
+        c->err = "xfg_debug_constraint_eval: null or unsupported argument";
+        return XFG_INVALID_ARGUMENT;
+    }
+    if (busy(c)) {  // lane 0's stream and buffers belong to the workers while batches are pending
+        c->err = "batches pending: call xfg_batch_wait first";
+        return XFG_INVALID_ARGUMENT;
+    }
+    const size_t B = count;
+    if (!all_canonical(trace, B * 7 * n) || !all_canonical(coeffs, B * 15 * ext)) {
+        c->err = "trace element or coefficient is not a canonical field element";
+        return XFG_INVALID_ARGUMENT;
+    }
+    for (size_t b = 0; b < B; b++)
+        if (!air_canonical(&airs[b])) {
+            c->err = "AIR constant is not a canonical field element";
+            return XFG_INVALID_ARGUMENT;
+        }
+    return guarded(c, [&]() -> int {
+        Lane* L = lane0(c);
+        HIPCHK(hipSetDevice(c->device));
+        const int logn = (int)ilog2(n), logbeta = (int)ilog2(blowup);
+        const u64 N = n * blowup, nce = 2 * n;
+        ensure_tables(c, std::max(logn + logbeta, logn + 1));
+        ensure_fourstep(c, logn, logbeta);
+        const Tables T = tables_of(c);
+        const u64* ce_div = ensure_ce_table(c, logn);
+        L->trace.ensure(B * 7 * n);
+        L->coef.ensure(B * 7 * n);
+        L->scratch.ensure(B * 7 * N);
+        L->lde.ensure(B * 7 * N);
+        L->air.ensure(B);
+        L->coeffs.ensure(B * 15 * ext);
+        L->ce.ensure(B * ext * nce);
+        std::vector<AirConst> ha(B);
+        for (size_t b = 0; b < B; b++) {
+            memset(&ha[b], 0, sizeof(AirConst));
+            memcpy(ha[b].pub, airs[b].pub_inputs, sizeof airs[b].pub_inputs);
+            ha[b].nullifier = airs[b].nullifier;
+            ha[b].commitment = airs[b].commitment;
+        }
+        hipStream_t s = L->stream;
+        HIPCHK(hipMemcpy(L->trace.p, trace, B * 7 * n * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(L->air.p, ha.data(), B * sizeof(AirConst), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(L->coeffs.p, coeffs, B * 15 * ext * 8, hipMemcpyHostToDevice));
+        // as prove_lane, steps 1 and 3
+        launch_interpolate(L->trace.p, n, L->coef.p, n, L->scratch.p, (int)B * 7, logn, false, n, T, s);
+        launch_lde(L->coef.p, n, L->lde.p, L->scratch.p, (int)B * 7, logn, logbeta, T, s);
+        launch_constraint_eval(L->lde.p, L->air.p, L->coeffs.p, ce_div, L->ce.p, logn, logbeta, (int)B, (int)ext, s);
+        HIPCHK(hipMemcpyAsync(ce, L->ce.p, B * ext * nce * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return XFG_OK;
+    });
+}
+
+int xfg_debug_fri_fold(xfg_ctx* c, uint32_t count, uint32_t ext, uint32_t logn, uint32_t logbeta, int coset_major,
+                       const uint64_t* vals, const uint64_t* alpha, uint64_t* out) {
+    if (!c) return XFG_INVALID_ARGUMENT;
+    c->err.clear();
+    if (!vals || !alpha || !out || count == 0 || (ext != 1 && ext != 2) || logn > 28 || logbeta > 28 ||
+        logn + logbeta < 4 || logn + logbeta > 28) {
+        c->err = "xfg_debug_fri_fold: null or unsupported argument";
+        return XFG_INVALID_ARGUMENT;
+    }
+    if (busy(c)) {  // lane 0's stream and buffers belong to the workers while batches are pending
+        c->err = "batches pending: call xfg_batch_wait first";
+        return XFG_INVALID_ARGUMENT;
+    }
+    const size_t B = count;
+    const int logD = (int)(logn + logbeta);
+    const u64 D = 1ULL << logD, rows = D / 8;
+    if (!all_canonical(vals, B * ext * D) || !all_canonical(alpha, B * ext)) {
+        c->err = "layer value or alpha is not a canonical field element";
+        return XFG_INVALID_ARGUMENT;
+    }
+    return guarded(c, [&]() -> int {
+        Lane* L = lane0(c);
+        HIPCHK(hipSetDevice(c->device));
+        ensure_tables(c, logD);
+        const Tables T = tables_of(c);
+        L->f0.ensure(B * ext * D);
+        L->alpha7.ensure(B * ext);
+        L->deep.ensure(B * ext * rows);
+        // alpha * 7^-1 per coordinate (7^-1 is a base-field element), as the device transcript step stores it
+        const u64 i7 = gl_inv(GEN);
+        std::vector<u64> a7(B * ext);
+        for (size_t k = 0; k < a7.size(); k++) a7[k] = gl_mul(alpha[k], i7);
+        hipStream_t s = L->stream;
+        HIPCHK(hipMemcpy(L->f0.p, vals, B * ext * D * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(L->alpha7.p, a7.data(), a7.size() * 8, hipMemcpyHostToDevice));
+        launch_fri_fold(L->f0.p, ext * D, D, coset_major != 0, (int)logn, (int)logbeta, rows, logD, L->alpha7.p,
+                        L->deep.p, rows, T, (int)B, (int)ext, s);
+        HIPCHK(hipMemcpyAsync(out, L->deep.p, B * ext * rows * 8, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return XFG_OK;
     });

@@ -88,6 +88,11 @@ _lib.xfg_lde_probe.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POI
 _lib.xfg_debug_lde.argtypes = [C.c_void_p, _u64p, C.c_uint32, C.c_uint64, C.c_uint32, _u64p]
 _lib.xfg_debug_ood_deep.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p]
 _lib.xfg_debug_interpolate.argtypes = [C.c_void_p, _u64p, C.c_uint32, C.c_uint64, C.c_int, _u64p]
+if hasattr(_lib, "xfg_debug_constraint_eval"):  # absent from builds older than the kernel-level parity hooks
+    _lib.xfg_debug_constraint_eval.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _u64p,
+                                               C.POINTER(_AirConsts), _u64p, _u64p]
+    _lib.xfg_debug_fri_fold.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _u64p,
+                                        _u64p, _u64p]
 if hasattr(_lib, "xfg_debug_field"):  # absent from builds older than the primitive self test (XFG_LIB A/B)
     _lib.xfg_debug_field.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, _u64p, _u64p, _u64p]
 if hasattr(_lib, "xfg_debug_coin_draws"):  # absent from builds older than the device transcript
@@ -694,7 +699,44 @@ class XfgBurnMintProver:
             raise self._err(st)
         return ood, deep
 
-    FIELD_OPS = {"mul": 0, "add": 1, "sub": 2, "canon": 3, "pow2": 4, "fold": 5, "sub_weak": 6, "add_w": 7, "mul2": 8}
+    def debug_constraint_eval(self, trace, airs, coeffs, blowup):
+        """constraint evaluation kernel behind interpolation + LDE + the divisor table, as the prover
+        runs them: trace [B,7,n], airs = B x (pub[12], nullifier, commitment), coeffs [B,15,ext]
+        -> ce [B,ext,2n] in natural CE-domain order"""
+        import numpy as np
+        tr = np.ascontiguousarray(trace, dtype=np.uint64)
+        co = np.ascontiguousarray(coeffs, dtype=np.uint64)
+        B, width, n = tr.shape
+        if width != 7 or co.ndim != 3 or co.shape[:2] != (B, 15) or len(airs) != B:
+            raise XfgStarkError(9, "debug_constraint_eval: trace [B,7,n], airs [B], coeffs [B,15,ext]")
+        ext = co.shape[2]
+        arr = (_AirConsts * B)(*[_air_struct(a) for a in airs])
+        ce = np.zeros((B, ext, 2 * n), dtype=np.uint64)
+        st = _lib.xfg_debug_constraint_eval(self._ctx, B, n, blowup, ext, tr.ctypes.data_as(_u64p), arr,
+                                            co.ctypes.data_as(_u64p), ce.ctypes.data_as(_u64p))
+        if st:
+            raise self._err(st)
+        return ce
+
+    def debug_fri_fold(self, vals, alpha, logn, logbeta, coset_major):
+        """FRI fold kernel (factor 8): vals [B,ext,D] with D = 2^(logn + logbeta), natural order or
+        coset-major (natural index K at (K mod beta) n + K // beta), alpha [B,ext] -> [B,ext,D/8]"""
+        import numpy as np
+        v = np.ascontiguousarray(vals, dtype=np.uint64)
+        al = np.ascontiguousarray(alpha, dtype=np.uint64)
+        B, ext, D = v.shape
+        if D != 1 << (logn + logbeta) or al.shape != (B, ext):
+            raise XfgStarkError(9, "debug_fri_fold: vals [B,ext,2^(logn+logbeta)], alpha [B,ext]")
+        out = np.zeros((B, ext, D // 8), dtype=np.uint64)
+        st = _lib.xfg_debug_fri_fold(self._ctx, B, ext, logn, logbeta, 1 if coset_major else 0,
+                                     v.ctypes.data_as(_u64p), al.ctypes.data_as(_u64p), out.ctypes.data_as(_u64p))
+        if st:
+            raise self._err(st)
+        return out
+
+    # ops from mul2_pair on read a, b as pairs (a[2i], a[2i+1]) and write both words of the result
+    FIELD_OPS = {"mul": 0, "add": 1, "sub": 2, "canon": 3, "pow2": 4, "fold": 5, "sub_weak": 6, "add_w": 7, "mul2": 8,
+                 "mul2_pair": 9, "e2_mul": 10, "e2_mulb": 11, "e2_inv": 12}
 
     def debug_field(self, op, a, b):
         """device Goldilocks primitive `op` (FIELD_OPS) applied elementwise to u64 arrays a, b"""
