@@ -1,0 +1,280 @@
+// The debug and bench entry points of the C ABI (include/xfg_stark.h): single kernels and launch
+// sets of the prover run on lane 0, for the kernel-level parity tests and the micro-benchmarks.
+// Each goes through on_lane0 (prover_internal.hpp): refused while batches are pending.
+#include <cstring>
+#include <vector>
+
+#include "prover_internal.hpp"
+
+using namespace xfg;
+
+extern "C" {
+
+int xfg_bench_lde(xfg_ctx* c, uint32_t count, uint64_t n, uint32_t blowup, uint32_t iters, double* avg_ms) {
+    if (!c || !avg_ms || !is_pow2(n) || !is_pow2(blowup) || n < 8 || blowup < 2 || blowup > 16 || iters == 0)
+        return XFG_INVALID_ARGUMENT;
+    return on_lane0(c, [&](Lane* L) -> int {
+        const int logn = (int)ilog2(n), logbeta = (int)ilog2(blowup);
+        const u64 N = n * blowup;
+        ensure_tables(c, logn + logbeta);
+        ensure_fourstep(c, logn, logbeta);
+        Tables T = tables_of(c);
+        L->coef.ensure((size_t)count * 7 * n);
+        L->scratch.ensure((size_t)count * 7 * N);
+        L->lde.ensure((size_t)count * 7 * N);
+        // deterministic canonical coefficients
+        std::vector<u64> h((size_t)count * 7 * n);
+        u64 x = 0x46472d535441524bULL;  // "FG-STARK"
+        for (auto& v : h) {
+            x += 0x9E3779B97F4A7C15ULL;
+            u64 z = x;
+            z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+            z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+            v = (z ^ (z >> 31)) % P;
+        }
+        HIPCHK(hipMemcpy(L->coef.p, h.data(), h.size() * 8, hipMemcpyHostToDevice));
+        launch_lde(L->coef.p, n, L->lde.p, L->scratch.p, count * 7, logn, logbeta, T, L->stream);  // warm
+        HIPCHK(hipEventRecord(L->ev[0], L->stream));
+        for (uint32_t i = 0; i < iters; i++)
+            launch_lde(L->coef.p, n, L->lde.p, L->scratch.p, count * 7, logn, logbeta, T, L->stream);
+        HIPCHK(hipEventRecord(L->ev[1], L->stream));
+        HIPCHK(hipEventSynchronize(L->ev[1]));
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, L->ev[0], L->ev[1]));
+        *avg_ms = ms / iters;
+        return XFG_OK;
+    });
+}
+
+int xfg_lde_probe(xfg_ctx* c, int enabled, double* total_ms, uint64_t* launch_sets, uint64_t* polys) {
+    if (!c) return XFG_INVALID_ARGUMENT;
+    return on_lane0(c, [&](Lane*) -> int {
+        double ms = 0;
+        u64 sets = 0, np = 0;
+        for (auto& L : c->lanes) {
+            ms += L->lde_ms;
+            sets += L->lde_sets;
+            np += L->lde_polys;
+            if (enabled) L->lde_ms = 0, L->lde_sets = 0, L->lde_polys = 0;
+            L->lde_probe = enabled != 0;
+        }
+        if (total_ms) *total_ms = ms;
+        c->lde_probe = enabled != 0;
+        if (launch_sets) *launch_sets = sets;
+        if (polys) *polys = np;
+        return XFG_OK;
+    });
+}
+
+int xfg_debug_lde(xfg_ctx* c, const uint64_t* coef, uint32_t npoly, uint64_t n, uint32_t blowup, uint64_t* out) {
+    if (!c || !coef || !out || !is_pow2(n) || !is_pow2(blowup) || n < 8 || blowup < 2 || blowup > 16)
+        return XFG_INVALID_ARGUMENT;
+    return on_lane0(c, [&](Lane* L) -> int {
+        const int logn = (int)ilog2(n), logbeta = (int)ilog2(blowup);
+        const u64 N = n * blowup;
+        ensure_tables(c, logn + logbeta);
+        ensure_fourstep(c, logn, logbeta);
+        Tables T = tables_of(c);
+        L->coef.ensure((size_t)npoly * n);
+        L->scratch.ensure((size_t)npoly * N);
+        L->lde.ensure((size_t)npoly * N);
+        HIPCHK(hipMemcpy(L->coef.p, coef, (size_t)npoly * n * 8, hipMemcpyHostToDevice));
+        launch_lde(L->coef.p, n, L->lde.p, L->scratch.p, npoly, logn, logbeta, T, L->stream);
+        std::vector<u64> cm((size_t)npoly * N);
+        HIPCHK(hipMemcpyAsync(cm.data(), L->lde.p, cm.size() * 8, hipMemcpyDeviceToHost, L->stream));
+        HIPCHK(hipStreamSynchronize(L->stream));
+        for (u64 p = 0; p < npoly; p++)  // coset-major -> natural order
+            for (u64 t = 0; t < blowup; t++)
+                for (u64 m = 0; m < n; m++) out[p * N + t + blowup * m] = cm[(p * blowup + t) * n + m];
+        return XFG_OK;
+    });
+}
+
+int xfg_debug_interpolate(xfg_ctx* c, const uint64_t* evals, uint32_t npoly, uint64_t n, int offset7, uint64_t* out) {
+    if (!c || !evals || !out || !is_pow2(n) || n < 8) return XFG_INVALID_ARGUMENT;
+    return on_lane0(c, [&](Lane* L) -> int {
+        const int logn = (int)ilog2(n);
+        ensure_tables(c, std::max(logn, c->tables.LM));
+        if (logn >= 4) ensure_fourstep(c, logn - 1, 1);  // inverse tables up to size n
+        Tables T = tables_of(c);
+        L->trace.ensure((size_t)npoly * n);
+        L->coef.ensure((size_t)npoly * n);
+        L->scratch.ensure((size_t)npoly * n);
+        HIPCHK(hipMemcpy(L->trace.p, evals, (size_t)npoly * n * 8, hipMemcpyHostToDevice));
+        launch_interpolate(L->trace.p, n, L->coef.p, n, L->scratch.p, npoly, logn, offset7 != 0, n, T, L->stream);
+        HIPCHK(hipMemcpyAsync(out, L->coef.p, (size_t)npoly * n * 8, hipMemcpyDeviceToHost, L->stream));
+        HIPCHK(hipStreamSynchronize(L->stream));
+        return XFG_OK;
+    });
+}
+
+int xfg_debug_field(xfg_ctx* c, uint32_t op, uint64_t count, const uint64_t* a, const uint64_t* b, uint64_t* out) {
+    if (!c || !a || !b || !out || op > 12 || count == 0 || (op >= 9 && count % 2)) return XFG_INVALID_ARGUMENT;
+    return on_lane0(c, [&](Lane* L) -> int {
+        L->trace.ensure((size_t)count * 3);
+        u64* da = L->trace.p;
+        u64* db = da + count;
+        u64* dout = db + count;
+        HIPCHK(hipMemcpy(da, a, count * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(db, b, count * 8, hipMemcpyHostToDevice));
+        launch_field_op((int)op, da, db, dout, count, L->stream);
+        HIPCHK(hipMemcpyAsync(out, dout, count * 8, hipMemcpyDeviceToHost, L->stream));
+        HIPCHK(hipStreamSynchronize(L->stream));
+        return XFG_OK;
+    });
+}
+
+int xfg_debug_coin_draws(xfg_ctx* c, const uint32_t seed[8], uint64_t counter, uint32_t k, uint32_t ext,
+                         const uint64_t reject[4], uint64_t* out_wave, uint64_t* out_seq, uint64_t counters[2],
+                         int ok[2]) {
+    if (!c || !seed || !reject || !out_wave || !out_seq || !counters || !ok || k == 0 || k > 64 ||
+        (ext != 1 && ext != 2))
+        return XFG_INVALID_ARGUMENT;
+    return on_lane0(c, [&](Lane* L) -> int {
+        L->trace.ensure(4 + 4 * (size_t)k + 2 + 1);
+        u64* drej = L->trace.p;
+        u64* dw = drej + 4;
+        u64* ds = dw + 2 * k;
+        u64* dctr = ds + 2 * k;
+        int* dok = (int*)(dctr + 2);
+        HIPCHK(hipMemcpy(drej, reject, 32, hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(dw, 0, 16 * (size_t)k));
+        DevCoin c0;
+        memcpy(c0.seed.w, seed, 32);
+        c0.counter = counter;
+        c0.pad = 0;
+        launch_coin_draw_test(c0, (int)k, (int)ext, drej, dw, ds, dctr, dok, L->stream);
+        HIPCHK(hipMemcpyAsync(out_wave, dw, 16 * (size_t)k, hipMemcpyDeviceToHost, L->stream));
+        HIPCHK(hipMemcpyAsync(out_seq, ds, 16 * (size_t)k, hipMemcpyDeviceToHost, L->stream));
+        HIPCHK(hipMemcpyAsync(counters, dctr, 16, hipMemcpyDeviceToHost, L->stream));
+        HIPCHK(hipMemcpyAsync(ok, dok, 8, hipMemcpyDeviceToHost, L->stream));
+        HIPCHK(hipStreamSynchronize(L->stream));
+        return XFG_OK;
+    });
+}
+
+int xfg_debug_ood_deep(xfg_ctx* c, uint32_t count, uint64_t n, const uint64_t* coef, const uint64_t* hcoef,
+                       const uint64_t* zpts, const uint64_t* coeffs, uint64_t* ood_out, uint64_t* deep_out) {
+    if (!c || !coef || !hcoef || !zpts || !coeffs || !ood_out || !deep_out || !is_pow2(n) || n < 8 || count == 0)
+        return XFG_INVALID_ARGUMENT;
+    return on_lane0(c, [&](Lane* L) -> int {
+        const ProofShape sh(n, Opts{0, 2, 0, 1, 8, 31});  // base field; the blowup plays no part
+        const int logn = sh.logn;
+        const size_t B = count;
+        L->coef.ensure(B * 7 * n);
+        size_ood_deep(L, B, sh);
+        hipStream_t s = L->stream;
+        HIPCHK(hipMemcpyAsync(L->coef.p, coef, B * 7 * n * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(L->hcoef.p, hcoef, B * n * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(L->zpts.p, zpts, B * 2 * 8, hipMemcpyHostToDevice, s));
+        launch_ood(L->coef.p, L->hcoef.p, L->zpts.p, L->partial.p, L->ood.p, logn, (int)B, 1, s);
+        HIPCHK(hipMemcpyAsync(ood_out, L->ood.p, B * 15 * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        std::vector<DeepParams> dps(B);
+        for (size_t b = 0; b < B; b++) {  // what the device transcript step derives: c1, c2 from the OOD values
+            DeepParams& dp = dps[b];
+            memset(&dp, 0, sizeof dp);
+            for (int k = 0; k < 7; k++) dp.a[k][0] = coeffs[b * 8 + k];
+            dp.gamma[0] = coeffs[b * 8 + 7];
+            dp.z[0] = zpts[2 * b];
+            dp.zg[0] = zpts[2 * b + 1];
+            dp.zinv[0] = gl_inv(dp.z[0]);
+            dp.zginv[0] = gl_inv(dp.zg[0]);
+            const u64* o = ood_out + b * 15;
+            u64 c1 = gl_mul(dp.gamma[0], o[14]), c2 = 0;
+            for (int k = 0; k < 7; k++) {
+                c1 = gl_add(c1, gl_mul(dp.a[k][0], o[2 * k]));
+                c2 = gl_add(c2, gl_mul(dp.a[k][0], o[2 * k + 1]));
+            }
+            dp.c1[0] = c1;
+            dp.c2[0] = c2;
+        }
+        HIPCHK(hipMemcpyAsync(L->dp.p, dps.data(), B * sizeof(DeepParams), hipMemcpyHostToDevice, s));
+        launch_deep(L->coef.p, L->hcoef.p, L->dp.p, L->partial.p, L->carry.p, L->deep.p, logn, (int)B, 1, s);
+        HIPCHK(hipMemcpyAsync(deep_out, L->deep.p, B * n * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return XFG_OK;
+    });
+}
+
+int xfg_debug_constraint_eval(xfg_ctx* c, uint32_t count, uint64_t n, uint32_t blowup, uint32_t ext,
+                              const uint64_t* trace, const xfg_air_consts* airs, const uint64_t* coeffs,
+                              uint64_t* ce) {
+    if (!c) return XFG_INVALID_ARGUMENT;
+    c->err.clear();
+    if (!trace || !airs || !coeffs || !ce || count == 0 || !is_pow2(n) || n < 8 || !is_pow2(blowup) || blowup < 2 ||
+        blowup > 16 || (ext != 1 && ext != 2)) {
+        c->err = "xfg_debug_constraint_eval: null or unsupported argument";
+        return XFG_INVALID_ARGUMENT;
+    }
+    return on_lane0(c, [&](Lane* L) -> int {
+        const size_t B = count;
+        if (!all_canonical(trace, B * 7 * n) || !all_canonical(coeffs, B * 15 * ext)) {
+            c->err = "trace element or coefficient is not a canonical field element";
+            return XFG_INVALID_ARGUMENT;
+        }
+        std::vector<AirConst> ha(B);
+        for (size_t b = 0; b < B; b++) {
+            if (!air_canonical(&airs[b])) {
+                c->err = "AIR constant is not a canonical field element";
+                return XFG_INVALID_ARGUMENT;
+            }
+            ha[b] = air_of(&airs[b]);
+        }
+        const ProofShape sh(n, Opts{0, blowup, 0, ext, 8, 31});
+        ensure_tables(c, std::max(sh.logn + sh.logbeta, sh.logn + 1));
+        ensure_fourstep(c, sh.logn, sh.logbeta);
+        const Tables T = tables_of(c);
+        const u64* ce_div = ensure_ce_table(c, sh.logn);
+        size_trace_lde(L, B, sh);
+        size_constraint_eval(L, B, sh);
+        hipStream_t s = L->stream;
+        HIPCHK(hipMemcpy(L->trace.p, trace, B * 7 * n * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(L->air.p, ha.data(), B * sizeof(AirConst), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(L->coeffs.p, coeffs, B * 15 * ext * 8, hipMemcpyHostToDevice));
+        launch_trace_lde(L, T, (int)B, sh, false);
+        launch_constraint_eval(L->lde.p, L->air.p, L->coeffs.p, ce_div, L->ce.p, sh.logn, sh.logbeta, (int)B, sh.DE, s);
+        HIPCHK(hipMemcpyAsync(ce, L->ce.p, B * ext * 2 * n * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return XFG_OK;
+    });
+}
+
+int xfg_debug_fri_fold(xfg_ctx* c, uint32_t count, uint32_t ext, uint32_t logn, uint32_t logbeta, int coset_major,
+                       const uint64_t* vals, const uint64_t* alpha, uint64_t* out) {
+    if (!c) return XFG_INVALID_ARGUMENT;
+    c->err.clear();
+    if (!vals || !alpha || !out || count == 0 || (ext != 1 && ext != 2) || logn > 28 || logbeta > 28 ||
+        logn + logbeta < 4 || logn + logbeta > 28) {
+        c->err = "xfg_debug_fri_fold: null or unsupported argument";
+        return XFG_INVALID_ARGUMENT;
+    }
+    return on_lane0(c, [&](Lane* L) -> int {
+        const size_t B = count;
+        const int logD = (int)(logn + logbeta);
+        const u64 D = 1ULL << logD, rows = D / 8;
+        if (!all_canonical(vals, B * ext * D) || !all_canonical(alpha, B * ext)) {
+            c->err = "layer value or alpha is not a canonical field element";
+            return XFG_INVALID_ARGUMENT;
+        }
+        ensure_tables(c, logD);
+        const Tables T = tables_of(c);
+        L->f0.ensure(B * ext * D);
+        L->alpha7.ensure(B * ext);
+        L->deep.ensure(B * ext * rows);
+        // alpha * 7^-1 per coordinate (7^-1 is a base-field element), as the device transcript step stores it
+        const u64 i7 = gl_inv(GEN);
+        std::vector<u64> a7(B * ext);
+        for (size_t k = 0; k < a7.size(); k++) a7[k] = gl_mul(alpha[k], i7);
+        hipStream_t s = L->stream;
+        HIPCHK(hipMemcpy(L->f0.p, vals, B * ext * D * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(L->alpha7.p, a7.data(), a7.size() * 8, hipMemcpyHostToDevice));
+        launch_fri_fold(L->f0.p, ext * D, D, coset_major != 0, (int)logn, (int)logbeta, rows, logD, L->alpha7.p,
+                        L->deep.p, rows, T, (int)B, (int)ext, s);
+        HIPCHK(hipMemcpyAsync(out, L->deep.p, B * ext * rows * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return XFG_OK;
+    });
+}
+
+}  // extern "C"

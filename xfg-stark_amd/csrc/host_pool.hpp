@@ -1,5 +1,5 @@
 // Process-wide pool of host threads for the per-proof host work of a proof unit (transcript replay,
-// grinding and opening plans, serialisation, copy-out). The lane workers (prover.hip) run up to
+// grinding and opening plans, serialisation: proof_assembly.hpp; copy-out). The lane workers (prover.hip) run up to
 // XFG_LANES units' host tails at once, each a loop over 8-64 independent proofs that used to run on
 // the lane's own thread while its stream waited; parallel_for spreads such a loop over the pool.
 #pragma once

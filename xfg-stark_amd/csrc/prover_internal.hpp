@@ -1,0 +1,218 @@
+// The prover context as its translation units share it: table registry, lanes, the batch queue
+// (prover.hip), the debug / bench entry points (debug_abi.hip) and the GPU batch verifier's host
+// side (verify_batch_gpu.hip).
+#pragma once
+#include <chrono>
+#include <condition_variable>
+#include <deque>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/xfg_stark.h"
+#include "hip_util.hpp"
+#include "host_common.hpp"
+#include "kernels.hpp"
+#include "proof_assembly.hpp"
+#include "verifier.hpp"
+
+namespace xfg {
+
+struct TablesHost {
+    int LM = -1;
+    DBuf<u64> tw, pow7, ipow7;
+    std::map<int, DBuf<u64>> ce_div;  // constraint divisor tables per log2(trace length)
+    FourStep fs;                      // four-step twiddle tables (pointers into four_buf)
+    std::map<int, DBuf<u64>> four_buf;
+    std::map<int, DBuf<u64>> pass_buf;  // standalone forward pass tables (fs.pass_fwd)
+};
+
+enum {
+    ST_LDE, ST_TCOMMIT, ST_CE, ST_COMP, ST_CCOMMIT, ST_OOD, ST_DEEP, ST_FRI, ST_GATHER, ST_HOST, ST_HQUERY, ST_HSER,
+    ST_COUNT
+};
+
+// one lane = one HIP stream + its pooled device buffers + one host thread; a batch is split
+// across lanes so one lane's host-side Fiat-Shamir / serialisation overlaps another's kernels.
+// Destroyed with no work in flight: the destructor synchronises both streams, then the buffers go.
+struct Lane {
+    hipStream_t stream = nullptr;
+    hipStream_t gstream = nullptr;  // the openings' gathers (gather_stream)
+    bool timing = false;
+    double stage_ms[ST_COUNT] = {0};
+    hipEvent_t ev[ST_COUNT + 1] = {};
+    // xfg_lde_probe: events around the trace LDE launch set, totals of the units so far
+    bool lde_probe = false;
+    hipEvent_t lde_ev[2] = {};
+    double lde_ms = 0;
+    u64 lde_sets = 0, lde_polys = 0;
+    DBuf<AirConst> air;
+    DBuf<u64> coeffs, trace, coef, scratch, lde, ce, hcoef, hlde, zpts, partial, ood, carry, deep, f0, alpha7,
+        rem, dn2, falpha;
+    DBuf<Digest> tnodes, hnodes, droots;
+    DBuf<DeepParams> dp;
+    DBuf<DevCoin> dcoin;  // device-side transcript
+    DBuf<int> dfail;
+    std::vector<DBuf<u64>> flayer;
+    std::vector<DBuf<Digest>> fnodes;
+    // pinned host staging
+    MappedHBuf<Digest> h_gd;
+    MappedHBuf<u64> h_idx, h_gv;
+    MappedHBuf<unsigned char> h_xfer;  // the replay's inputs, written by launch_pack
+    MappedHBuf<AirConst> h_air;
+    MappedHBuf<DevCoin> h_coin;
+    // host scratch of the opening plans and the serialiser, kept across units so steady-state
+    // units neither allocate nor page-fault (their cost grew with the shared hosts' load)
+    struct {
+        OpeningIndex ix;
+        std::vector<LaneLayout> lay;
+    } hs;
+    Lane() = default;
+    Lane(const Lane&) = delete;
+    Lane& operator=(const Lane&) = delete;
+    ~Lane() {
+        if (stream) (void)hipStreamSynchronize(stream);
+        if (gstream) (void)hipStreamSynchronize(gstream);
+        for (auto& e : ev)
+            if (e) (void)hipEventDestroy(e);
+        for (auto& e : lde_ev)
+            if (e) (void)hipEventDestroy(e);
+        if (stream) (void)hipStreamDestroy(stream);
+        if (gstream) (void)hipStreamDestroy(gstream);
+    }
+};
+
+struct Batch;
+struct Unit {
+    Batch* b;
+    int b0, b1;
+    int lane;  // -1: any worker
+};
+
+struct HostTrace {
+    std::vector<std::pair<const char*, std::chrono::steady_clock::time_point>> m;
+    std::map<std::string, double> acc;  // accumulated sub-phase ms
+    using clk = std::chrono::steady_clock;
+    clk::time_point t_ = {};
+    void tic() {
+        if (trace_on()) t_ = clk::now();
+    }
+    void toc(const char* what) {
+        if (!trace_on()) return;
+        auto t = clk::now();
+        acc[what] += std::chrono::duration<double, std::milli>(t - t_).count();
+        t_ = t;
+    }
+    void mark(const char* what) {
+        if (trace_on()) m.push_back({what, std::chrono::steady_clock::now()});
+    }
+    void dump(int B) {
+        if (!trace_on() || m.size() < 2) return;
+        std::string line = "[xfg] B=" + std::to_string(B);
+        for (size_t i = 1; i < m.size(); i++) {
+            char buf[96];
+            snprintf(buf, sizeof buf, " %s=%.2f", m[i].first,
+                     std::chrono::duration<double, std::milli>(m[i].second - m[i - 1].second).count());
+            line += buf;
+        }
+        for (auto& kv : acc) {
+            char buf[96];
+            snprintf(buf, sizeof buf, " [%s=%.3f]", kv.first.c_str(), kv.second);
+            line += buf;
+        }
+        fprintf(stderr, "%s\n", line.c_str());
+    }
+};
+
+}  // namespace xfg
+
+struct xfg_ctx {
+    int device = 0;
+    std::string err;
+    bool timing = false;
+    bool lde_probe = false;  // xfg_lde_probe state, inherited by lanes created later
+    xfg::TablesHost tables;
+    std::vector<std::unique_ptr<xfg::Lane>> lanes;
+    // persistent lane workers: one host thread per lane pulls proof units from a FIFO shared by
+    // every submitted batch, so the host tail of one batch overlaps the kernels of the next
+    std::mutex qm;
+    std::condition_variable qcv, dcv;
+    std::deque<xfg::Unit> q;
+    std::vector<std::thread> workers;
+    bool stop = false;
+    uint64_t next_ticket = 1;
+    std::map<uint64_t, std::unique_ptr<xfg::Batch>> pending;
+    int last_lane = 0;
+    int idle = 0;  // lane workers waiting for a unit
+    // batched GPU verification workspace (xfg_verify_batch_gpu)
+    struct {
+        xfg::HBuf<uint8_t> stage;  // pinned: proof blob + task lists, one DMA
+        xfg::DBuf<uint8_t> dstage;
+        xfg::DBuf<uint32_t> flags;
+        std::vector<xfg::VState> st;        // per-proof transcript states, reused between calls
+        std::vector<xfg::VerifyPlan> frag;  // per-proof plan fragments, reused between calls
+    } vb;
+    ~xfg_ctx();  // prover.hip (Batch is complete there)
+};
+
+namespace xfg {
+
+// ---- defined in prover.hip
+void ensure_tables(xfg_ctx* c, int LM);
+const u64* ensure_ce_table(xfg_ctx* c, int logn);
+// caller guarantees no kernel in flight reads the registry (fresh context or drained)
+void ensure_fourstep(xfg_ctx* c, int logn, int logbeta);
+Tables tables_of(xfg_ctx* c);
+Lane* lane0(xfg_ctx* c);
+// true while a submitted batch has not been waited for
+bool busy(xfg_ctx* c);
+// buffer sizing and launch sets of the proving chain that the debug entry points run too; of the
+// shape they read n, beta and DE only
+void size_trace_lde(Lane* c, size_t B, const ProofShape& sh);        // trace, coef, scratch, lde
+void size_constraint_eval(Lane* c, size_t B, const ProofShape& sh);  // air, coeffs, ce
+void size_ood_deep(Lane* c, size_t B, const ProofShape& sh);  // hcoef, zpts, partial, ood, dp, carry, deep
+// trace -> coefficients -> LDE (DefaultTraceLde::new); probe: the xfg_lde_probe events around the LDE
+void launch_trace_lde(Lane* c, const Tables& T, int B, const ProofShape& sh, bool probe);
+
+// the kernels' subtractions (gl_sub) are exact for canonical operands only: host inputs are checked
+static inline bool all_canonical(const uint64_t* v, size_t k) {
+    for (size_t i = 0; i < k; i++)
+        if (v[i] >= P) return false;
+    return true;
+}
+static inline bool air_canonical(const xfg_air_consts* a) {
+    return all_canonical(a->pub_inputs, 12) && a->nullifier < P && a->commitment < P;
+}
+
+template <class F>
+static int guarded(xfg_ctx* c, F f) {
+    try {
+        return f();
+    } catch (const HipError& e) {
+        c->err = e.what();
+        return XFG_DEVICE_ERROR;
+    } catch (const std::exception& e) {
+        c->err = std::string("Prover error: ") + e.what();
+        return XFG_PROVER_ERROR;
+    }
+}
+
+// an entry point that uses lane 0 directly: refused while batches are pending (lane 0's stream,
+// buffers and counters belong to the workers then), else f(lane 0) with the context's device current
+template <class F>
+static int on_lane0(xfg_ctx* c, F f) {
+    if (busy(c)) {
+        c->err = "batches pending: call xfg_batch_wait first";
+        return XFG_INVALID_ARGUMENT;
+    }
+    return guarded(c, [&]() -> int {
+        Lane* L = lane0(c);
+        HIPCHK(hipSetDevice(c->device));
+        return f(L);
+    });
+}
+
+}  // namespace xfg

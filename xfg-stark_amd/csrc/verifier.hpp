@@ -1,5 +1,5 @@
 // Proof parsing and verification state shared by the host verifier (verifier.cpp) and the batched
-// GPU verifier (verify_kernels.hip + xfg_verify_batch_gpu in prover.hip).
+// GPU verifier (verify_kernels.hip + xfg_verify_batch_gpu in verify_batch_gpu.hip).
 #pragma once
 #include <string>
 #include <vector>

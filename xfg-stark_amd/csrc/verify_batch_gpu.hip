@@ -1,0 +1,133 @@
+// Host side of the batched GPU verifier (xfg_verify_batch_gpu): transcripts and plans per proof on
+// the host pool (verifier.cpp), one staging upload, the two kernels of verify_kernels.hip on lane
+// 0's stream, verdicts in the host verifier's check order.
+#include <cstring>
+#include <functional>
+#include <string>
+#include <vector>
+
+#include "host_pool.hpp"
+#include "prover_internal.hpp"
+
+using namespace xfg;
+
+extern "C" int xfg_verify_batch_gpu(xfg_ctx* c, uint32_t count, const uint8_t* const* proofs, const size_t* lens,
+                                    const xfg_air_consts* airs, const xfg_options* acceptable, int* results) {
+    if (!c || !proofs || !lens || !airs || !acceptable || !results) return XFG_INVALID_ARGUMENT;
+    c->err.clear();
+    return on_lane0(c, [&](Lane* L0) -> int {
+        const Opts acc = to_opts(acceptable);
+        HostTrace ht;
+        ht.mark("start");
+        // per-proof transcript states and plan fragments are kept in the context between calls
+        // (reset in place: a large batch would otherwise allocate and free ~10^5 small blocks)
+        auto& V = c->vb;
+        if (V.st.size() < count) V.st.resize(count);
+        if (V.frag.size() < count) V.frag.resize(count);
+        std::vector<VState>& st = V.st;
+        std::vector<std::string> err(count);
+        // per-proof host phases on the host pool (spawning 16 threads per phase cost more than the
+        // phases' own work at 64 proofs); a proof per task
+        auto parallel = [&](const std::function<void(uint32_t)>& f) {
+            host_pool().parallel_for((int)count, [&](int i) { f((uint32_t)i); });
+        };
+        // 1. transcripts (host threads)
+        parallel([&](uint32_t i) {
+            if (!proofs[i]) {
+                err[i] = "null proof";
+                return;
+            }
+            try {
+                err[i] = verify_transcript(proofs[i], lens[i], air_of(&airs[i]), acc, st[i]);
+            } catch (const std::exception& e) {
+                err[i] = std::string("ProofDeserializationError(\"") + e.what() + "\")";
+            }
+        });
+        ht.mark("transcripts");
+        // 2. plan: per-proof fragments (openings, queries) built in parallel; blob offsets by prefix
+        //    sum of the accepted proofs' lengths
+        std::vector<size_t> boff(count + 1, 0);
+        for (uint32_t i = 0; i < count; i++) boff[i + 1] = boff[i] + (err[i].empty() ? lens[i] : 0);
+        std::vector<VerifyPlan>& frag = V.frag;
+        parallel([&](uint32_t i) {
+            if (!err[i].empty()) return;
+            std::string e;
+            if (!plan_proof(st[i], boff[i], frag[i], e)) err[i] = e;
+        });
+        ht.mark("plan_fragments");
+        // 3. concatenate into one pinned staging region (parallel fill) and one DMA
+        struct Off {
+            size_t t = 0, lf = 0, v = 0, q = 0, fp = 0;
+        };
+        std::vector<Off> fo(count + 1);
+        std::vector<int> planned(count, -1);
+        for (uint32_t i = 0; i < count; i++) {
+            const bool ok = err[i].empty();
+            const VerifyPlan& f = frag[i];
+            Off& a = fo[i];
+            Off& b = fo[i + 1];
+            b.t = a.t + (ok ? f.trees.size() : 0);
+            b.lf = a.lf + (ok ? f.tleaves.size() : 0);
+            b.v = a.v + (ok ? f.vecs.size() : 0);
+            b.q = a.q + (ok ? f.fqueries.size() : 0);
+            b.fp = a.fp + (ok ? 1 : 0);
+            if (ok) planned[i] = (int)a.fp;
+        }
+        const Off& E = fo[count];
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        const size_t o_blob = 0, o_t = al(boff[count]), o_lf = al(o_t + E.t * sizeof(VTree)),
+                     o_v = al(o_lf + E.lf * sizeof(VTreeLeaf)), o_fp = al(o_v + E.v * sizeof(VVec)),
+                     o_fq = al(o_fp + E.fp * sizeof(VFieldProof)), total_b = al(o_fq + E.q * sizeof(VFieldQuery));
+        uint8_t* H = V.stage.ensure(total_b);
+        VTree* ht_ = (VTree*)(H + o_t);
+        VTreeLeaf* hlf = (VTreeLeaf*)(H + o_lf);
+        VVec* hv = (VVec*)(H + o_v);
+        VFieldProof* hfp = (VFieldProof*)(H + o_fp);
+        VFieldQuery* hfq = (VFieldQuery*)(H + o_fq);
+        parallel([&](uint32_t i) {
+            if (planned[i] < 0) return;
+            memcpy(H + o_blob + boff[i], proofs[i], lens[i]);
+            const VerifyPlan& f = frag[i];
+            const Off& a = fo[i];
+            for (size_t k = 0; k < f.trees.size(); k++) {
+                VTree t = f.trees[k];
+                t.leaf0 += (uint32_t)a.lf;
+                t.vec0 += (uint32_t)a.v;
+                t.proof = (uint32_t)a.fp;
+                ht_[a.t + k] = t;
+            }
+            memcpy(hlf + a.lf, f.tleaves.data(), f.tleaves.size() * sizeof(VTreeLeaf));
+            memcpy(hv + a.v, f.vecs.data(), f.vecs.size() * sizeof(VVec));
+            hfp[a.fp] = f.fproof;
+            for (size_t k = 0; k < f.fqueries.size(); k++) {
+                hfq[a.q + k] = f.fqueries[k];
+                hfq[a.q + k].proof = (uint32_t)a.fp;
+            }
+        });
+        ht.mark("plan_merge");
+        std::vector<uint32_t> flags(E.fp, 0);
+        if (E.fp > 0) {
+            hipStream_t s = L0->stream;
+            V.dstage.ensure(total_b);
+            V.flags.ensure(E.fp);
+            HIPCHK(hipMemcpyAsync(V.dstage.p, H, total_b, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemsetAsync(V.flags.p, 0, E.fp * 4, s));
+            ht.mark("upload_enqueue");
+            uint8_t* D = V.dstage.p;
+            launch_verify(D + o_blob, (const VTree*)(D + o_t), E.t, (const VTreeLeaf*)(D + o_lf), (const VVec*)(D + o_v),
+                          (const VFieldProof*)(D + o_fp), (const VFieldQuery*)(D + o_fq), E.q, V.flags.p, s);
+            HIPCHK(hipMemcpyAsync(flags.data(), V.flags.p, flags.size() * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            ht.mark("device");
+        }
+        // 4. verdicts in the host verifier's check order
+        parallel([&](uint32_t i) {
+            if (planned[i] >= 0) err[i] = finish_proof(st[i], flags[planned[i]]);
+            results[i] = proofs[i] ? (err[i].empty() ? XFG_OK : XFG_VERIFY_FAILED) : XFG_INVALID_ARGUMENT;
+        });
+        ht.mark("finish");
+        ht.dump((int)count);
+        return XFG_OK;
+    });
+}
+

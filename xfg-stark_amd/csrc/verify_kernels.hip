@@ -1,6 +1,6 @@
 // Batched verification on the GPU (gfx950): the Merkle openings and the per-query DEEP / FRI /
 // remainder checks of many burn proofs at once. The host replays each transcript and lays the work
-// out as flat task lists (verifier.cpp plan_proof); see xfg_verify_batch_gpu in prover.hip.
+// out as flat task lists (verifier.cpp plan_proof); see xfg_verify_batch_gpu in verify_batch_gpu.hip.
 // Replaces the serial BatchBurnMintVerifier loops of the reference (src/burn_mint_verifier.rs:
 // 326-338, 386-408), each of which runs winterfell::verify on the CPU.
 #include "verifier.hpp"
