@@ -14,6 +14,7 @@ import random
 import numpy as np
 import pytest
 
+import ntt_shapes
 import oracle_lib as O
 import synthetic
 
@@ -45,8 +46,7 @@ def with_blowup(prover, b):
     return o
 
 
-@pytest.mark.parametrize("n,blowup", [(8, 2), (64, 8), (256, 16), (1024, 4), (4096, 8), (1 << 15, 8), (1 << 16, 2),
-                                      (1 << 17, 2), (1 << 19, 2), (1 << 20, 2), (1 << 21, 2)])
+@pytest.mark.parametrize("n,blowup", ntt_shapes.LDE_3POLY)
 def test_lde_kernel_matches_oracle(prover, n, blowup):
     rng = np.random.default_rng(n + blowup)
     coef = rng.integers(0, P, size=(3, n), dtype=np.uint64)
@@ -56,8 +56,7 @@ def test_lde_kernel_matches_oracle(prover, n, blowup):
         assert [int(v) for v in got[p]] == want
 
 
-@pytest.mark.parametrize("n,blowup", [(1 << 18, 2), (1 << 22, 2), (1 << 20, 16), (1 << 22, 4), (1 << 16, 4),
-                                      (1 << 16, 16), (1 << 17, 8), (1 << 17, 16)])
+@pytest.mark.parametrize("n,blowup", ntt_shapes.LDE_1POLY)
 def test_lde_kernel_tile_paths_match_oracle(prover, n, blowup):
     """the remaining four-step shapes: 2^18 (R = 256 narrow tiles, C = 1024 with 512-thread pass B
     tiles) and 2^22 (R = 1024 wide 1024-thread pass A, C = 4096 narrow pass B), one polynomial,
@@ -69,7 +68,7 @@ def test_lde_kernel_tile_paths_match_oracle(prover, n, blowup):
     assert np.array_equal(got, O.evaluate_lde_np(coef[0], blowup, 7))
 
 
-@pytest.mark.parametrize("npoly,blowup", [(32, 8), (32, 2), (32, 4), (33, 16), (28, 8)])
+@pytest.mark.parametrize("npoly,blowup", ntt_shapes.LDE_2P16_SETS)
 def test_lde_launch_set_routes_match_oracle(prover, npoly, blowup):
     """the two routes of the tabled 2^16 forward LDE: launch sets of >= 512 all-coset blocks (16 per
     polynomial: 32 or 33 polynomials) take ntt_pass_a_cos2 (beta >= 4) / ntt_pass_a_cos (beta = 2) +
@@ -83,7 +82,7 @@ def test_lde_launch_set_routes_match_oracle(prover, npoly, blowup):
         assert np.array_equal(got[k], O.evaluate_lde_np(coef[k], blowup, 7)), k
 
 
-@pytest.mark.parametrize("blowup", [8, 16])
+@pytest.mark.parametrize("blowup", ntt_shapes.LDE_R1024_BLOWUPS)
 def test_lde_r1024_kernels_two_polys_match_oracle(prover, blowup):
     """ntt_pass_a_r1024 / ntt_pass_b_r1024 (n = 2^20 past the four-step tables): two polynomials, so
     the (poly, coset) block numbering of the coset-consecutive order is exercised across polys"""
@@ -95,7 +94,44 @@ def test_lde_r1024_kernels_two_polys_match_oracle(prover, blowup):
         assert np.array_equal(got[k], O.evaluate_lde_np(coef[k], blowup, 7)), k
 
 
-@pytest.mark.parametrize("n,off7", [(1 << 18, True), (1 << 22, False)])
+@pytest.mark.parametrize("n,npoly,blowup", ntt_shapes.LDE_ALL_COSET_GENERIC_B)
+def test_lde_all_coset_generic_pass_b_matches_oracle(prover, n, npoly, blowup):
+    """launch sets of >= 512 all-coset blocks at 2^17 and 2^18 (production batch shapes): ntt_pass_a_cos /
+    ntt_pass_a_cos2 leave the four-step twiddles to the generic ntt_pass_b<9 | 10, false, 8, 5> (tq_b);
+    bit-exact against the oracle on every polynomial"""
+    rng = np.random.default_rng(n + npoly * 100 + blowup)
+    coef = rng.integers(0, P, size=(npoly, n), dtype=np.uint64)
+    got = np.asarray(prover.debug_lde(coef, n, blowup))
+    for k in range(npoly):
+        assert np.array_equal(got[k], O.evaluate_lde_np(coef[k], blowup, 7)), k
+
+
+def test_ntt_sizes_without_a_kernel_are_refused(prover):
+    """n = 16, blowup 2, remainder degree 7 folds 32 points once: the FRI remainder would be interpolated at
+    size 4, which has no kernel (nor have sizes from 2^23): the prover says so instead of emitting a proof
+    with an unwritten remainder, and the debug entries refuse such sizes as invalid arguments"""
+    import xfgstark
+    o = xfgstark.ProofOptions.reference()
+    o.blowup_factor, o.fri_remainder_max_degree, o.num_queries = 2, 7, 8
+    prover._options = o
+    try:
+        with pytest.raises(xfgstark.XfgStarkError) as e:
+            prover.prove_burn_mint(**synthetic.burn_inputs(916), trace_length=16)
+        assert e.value.status == 6 and "NTT of size 4" in str(e.value)
+        o.fri_remainder_max_degree = 1  # n = 32: 64 -> 8 -> 1, a remainder of size 1
+        with pytest.raises(xfgstark.XfgStarkError) as e:
+            prover.prove_burn_mint(**synthetic.burn_inputs(916), trace_length=32)
+        assert e.value.status == 6 and "NTT of size 1 " in str(e.value)
+    finally:
+        prover._options = xfgstark.ProofOptions.reference()
+    big = np.zeros((1, 1 << 23), dtype=np.uint64)
+    for call in (lambda: prover.debug_lde(big, 1 << 23, 2), lambda: prover.debug_interpolate(big, 1 << 23, False)):
+        with pytest.raises(xfgstark.XfgStarkError) as e:
+            call()
+        assert e.value.status == 9
+
+
+@pytest.mark.parametrize("n,off7", ntt_shapes.INTERPOLATE_1POLY)
 def test_interpolate_kernel_tile_paths_match_oracle(prover, n, off7):
     rng = np.random.default_rng(n + 11)
     ev = rng.integers(0, P, size=(1, n), dtype=np.uint64)
@@ -204,8 +240,7 @@ def test_field_primitives_match_bigint(prover, op):
         assert r == want, (op, x, y, r, want)
 
 
-@pytest.mark.parametrize("n,off7", [(8, False), (64, True), (2048, False), (2048, True), (1 << 14, True),
-                                    (1 << 17, True), (1 << 19, True), (1 << 20, False), (1 << 21, True)])
+@pytest.mark.parametrize("n,off7", ntt_shapes.INTERPOLATE_2POLY)
 def test_interpolate_kernel_matches_oracle(prover, n, off7):
     rng = np.random.default_rng(n)
     ev = rng.integers(0, P, size=(2, n), dtype=np.uint64)

@@ -4,15 +4,79 @@
 #include <cstring>
 #include <vector>
 
+#include "field_dft.hpp"
 #include "prover_internal.hpp"
 
 using namespace xfg;
+
+// field-primitive self test (xfg_debug_field): op 0 mul, 1 add, 2 sub, 3 canon(a), 4 a * 2^b,
+// 5 fold(a, (u32)b), 6 sub_weak(a, b), 7 add_w(a, b) (the NTT butterfly add, b < p)
+__global__ void field_op_kernel(int op, const u64* a, const u64* b, u64* out, u64 count) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const u64 x = a[i], y = b[i];
+    u64 r = 0;
+    switch (op) {
+        case 0: r = gl_mul(x, y); break;
+        case 1: r = gl_add(x, y); break;
+        case 2: r = gl_sub(x, y); break;
+        case 3: r = gl_canon(x); break;
+        case 4: {
+            const int sh = (int)(y % 96);
+            static_for<96>([&](auto sc) {
+                if (sh == decltype(sc)::value) r = mul_pow2<decltype(sc)::value>(x);
+            });
+            break;
+        }
+        case 5: r = gl_fold(x, (u32)y); break;
+        case 6: r = gl_sub_weak(x, y); break;
+        case 7: r = add_w(x, y); break;
+        case 8: {  // gl_mul2: both products (x y and y x) must equal; the first is returned
+            u64 p = x, q = y;
+            gl_mul2(p, y, q, x);
+            r = p == q ? p : ~0ULL;
+            break;
+        }
+        default: break;
+    }
+    out[i] = r;
+}
+// ops 9..12: one thread per pair x = (a[2i], a[2i+1]), y = (b[2i], b[2i+1]) -> out[2i], out[2i+1]
+__global__ void field_pair_op_kernel(int op, const u64* a, const u64* b, u64* out, u64 pairs) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= pairs) return;
+    const E2 x{a[2 * i], a[2 * i + 1]}, y{b[2 * i], b[2 * i + 1]};
+    E2 r{0, 0};
+    switch (op) {
+        case 9: {  // one gl_mul2 on two unrelated products
+            r = x;
+            gl_mul2(r.a, y.a, r.b, y.b);
+            break;
+        }
+        case 10: r = e2_mul(x, y); break;
+        case 11: r = e2_mulb(x, y.a); break;
+        case 12: r = e2_inv(x); break;
+        default: break;
+    }
+    out[2 * i] = r.a;
+    out[2 * i + 1] = r.b;
+}
+static void launch_field_op(int op, const u64* a, const u64* b, u64* out, u64 count, hipStream_t s) {
+    if (op >= 9) {  // count is even (checked by the caller)
+        const u64 pairs = count / 2;
+        hipLaunchKernelGGL(field_pair_op_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, s, op, a, b, out,
+                           pairs);
+        return;
+    }
+    hipLaunchKernelGGL(field_op_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, op, a, b, out, count);
+}
 
 extern "C" {
 
 int xfg_bench_lde(xfg_ctx* c, uint32_t count, uint64_t n, uint32_t blowup, uint32_t iters, double* avg_ms) {
     if (!c || !avg_ms || !is_pow2(n) || !is_pow2(blowup) || n < 8 || blowup < 2 || blowup > 16 || iters == 0)
         return XFG_INVALID_ARGUMENT;
+    if (!ntt_supported((int)ilog2(n), (int)ilog2(blowup), false)) return XFG_INVALID_ARGUMENT;
     return on_lane0(c, [&](Lane* L) -> int {
         const int logn = (int)ilog2(n), logbeta = (int)ilog2(blowup);
         const u64 N = n * blowup;
@@ -69,6 +133,7 @@ int xfg_lde_probe(xfg_ctx* c, int enabled, double* total_ms, uint64_t* launch_se
 int xfg_debug_lde(xfg_ctx* c, const uint64_t* coef, uint32_t npoly, uint64_t n, uint32_t blowup, uint64_t* out) {
     if (!c || !coef || !out || !is_pow2(n) || !is_pow2(blowup) || n < 8 || blowup < 2 || blowup > 16)
         return XFG_INVALID_ARGUMENT;
+    if (!ntt_supported((int)ilog2(n), (int)ilog2(blowup), false)) return XFG_INVALID_ARGUMENT;
     return on_lane0(c, [&](Lane* L) -> int {
         const int logn = (int)ilog2(n), logbeta = (int)ilog2(blowup);
         const u64 N = n * blowup;
@@ -91,7 +156,7 @@ int xfg_debug_lde(xfg_ctx* c, const uint64_t* coef, uint32_t npoly, uint64_t n, 
 }
 
 int xfg_debug_interpolate(xfg_ctx* c, const uint64_t* evals, uint32_t npoly, uint64_t n, int offset7, uint64_t* out) {
-    if (!c || !evals || !out || !is_pow2(n) || n < 8) return XFG_INVALID_ARGUMENT;
+    if (!c || !evals || !out || !is_pow2(n) || n < 8 || !ntt_supported((int)ilog2(n), 0, true)) return XFG_INVALID_ARGUMENT;
     return on_lane0(c, [&](Lane* L) -> int {
         const int logn = (int)ilog2(n);
         ensure_tables(c, std::max(logn, c->tables.LM));

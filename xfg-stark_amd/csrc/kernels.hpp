@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include "gl.hpp"
 #include "blake3.hpp"
+#include "ntt_plan.hpp"
 
 namespace xfg {
 
@@ -28,14 +29,13 @@ struct DeepParams {
 
 // precomputed four-step twiddles (ntt.hip build_fourstep): fwd[logn][logbeta] holds
 // 7^j2 w_N^(j2 (t + beta k1)) at [t][k1][j2], inv[logn] holds w_n^-(j2 k1) / n at [k1][j2];
-// nullptr -> the kernels form them as running products
-constexpr int FOURSTEP_MAX_LOG = 22;
+// nullptr -> the kernels form them as running products. Which of the two a forward size gets:
+// table_kind (ntt_plan.hpp).
 // forward sizes past FOURSTEP_MAX_LOG (configs[4]: 2^20 x 16 = 2^24 points, where a full table would
 // be 128 MB) get no beta n table, only the per-size pass tables as one contiguous block,
 // pass_fwd[logn][logbeta]: w_R^i, w_C^i and the coset pre-factors (R + C + beta R entries); at
 // R = C = 1024 also the per-coset [r][k] and [t][j2] factors and the coset-independent [k1][j2]
 // four-step table (8 MiB, ntt_pass_a_r1024); other sizes keep running-product four-step twiddles
-constexpr int PASS_MAX_LOG = 24;
 struct FourStep {
     const u64* fwd[FOURSTEP_MAX_LOG + 1][5] = {};
     const u64* inv[FOURSTEP_MAX_LOG + 1] = {};
@@ -53,15 +53,10 @@ struct Tables {
 // forward LDE: coef[poly][n] -> out[poly][beta][n] (coset-major: out[p][t][m] = P(7 w_N^(t + beta m)))
 void launch_lde(const u64* coef, u64 coef_stride, u64* out, u64* scratch, int npoly, int logn, int logbeta,
                 const Tables& T, hipStream_t s);
-// entries of the four-step table for (logn, logbeta) (inverse: logbeta = -1), and its generator
-u64 fourstep_size(int logn, int logbeta);
+// generator of the four-step table for (logn, logbeta) (inverse: logbeta = -1; fourstep_size entries)
 void build_fourstep(u64* out, int logn, int logbeta, const Tables& T, hipStream_t s);
-// the pass tables alone (forward, for sizes without a four-step table): entries and generator
-u64 pass_tables_size(int logn, int logbeta);
+// the pass tables alone (forward, for sizes without a four-step table; pass_tables_size entries)
 void build_pass_tables(u64* out, int logn, int logbeta, const Tables& T, hipStream_t s);
-// field-primitive self test (xfg_debug_field): op 0 mul, 1 add, 2 sub, 3 canon(a), 4 a * 2^b,
-// 5 fold(a, (u32)b), 6 sub_weak(a, b), 7 add_w(a, b) (the NTT butterfly add, b < p)
-void launch_field_op(int op, const u64* a, const u64* b, u64* out, u64 count, hipStream_t s);
 // inverse: evals[poly][n] at 7^off7 * w_n^i -> coefficients (first `keep` written, stride out_stride)
 void launch_interpolate(const u64* evals, u64 in_stride, u64* out, u64 out_stride, u64* scratch, int npoly, int logn,
                         bool off7, u64 keep, const Tables& T, hipStream_t s);

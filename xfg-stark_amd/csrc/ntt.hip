@@ -18,11 +18,15 @@
 // The coset shift (7 w_N^t)^j, j = C j1 + j2, is split into a pre-factor 7^(C j1) w_(beta R)^(t j1)
 // (LDS table per coset) and a post-factor 7^j2 w_N^(j2 t) folded into the four-step twiddle.
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
+#include <string>
 #include <type_traits>
 #include <utility>
+#include "hip_util.hpp"
 #include "kernels.hpp"
 #include "field_dft.hpp"
+#include "ntt_plan.hpp"
 
 namespace xfg {
 
@@ -91,29 +95,10 @@ __device__ __forceinline__ void store_pairs(const u64* v, AT at) {
     }
 }
 
-// LDS tile: row `seq` of length S at seq * PITCH; element i at i + (i >> P), one pad word per 2^P
-// elements, P = log2 elements per thread (4 or 5). The pad word makes the stride-2^P stores of a
-// full-radix first step (lanes along a row, 2^P contiguous outputs each) conflict-free: 16 lanes
-// land on 16 different 8-byte bank pairs. The pitch does the same for lanes walking across rows:
-// a 16-lane group spans 2^L rows and 16 / 2^L consecutive elements, so the pitch must be an odd
-// multiple of 16 / 2^L mod 16 (radix 16: odd; radix 32 with 8-row tiles, pass B at n = 2^20: 2 mod
-// 4 -- the odd pitch there cost 2-way conflicts on every last-step read, and the pad per 16 on
-// every first-step write, 14.8 M conflict cycles per configs[4] trace LDE).
-// L = log2 of the tile's row count (the kernel's maximum; a smaller tile only uses fewer rows).
-__host__ __device__ constexpr int row_pitch(int S, int P = 4, int L = 4) {
-    return P == 4 ? S + S / 16 + 1 : S + (S >> P) + ((L >= 4 || L <= 0) ? 1 : (16 >> L));
-}
-// Pitch of a 32-bit exchange tile (pass_dft_split). Its writes and ds_read_b32 / ds_read2_b32 reads
-// bank on (a / 4) mod 32 per 32-lane half, where a row-fast half-wave spans 2^L rows of the tile and
-// 32 / 2^L consecutive groups, so a row pitch of 32 / 2^L (mod 32) spreads the rows over distinct bank
-// groups. Radix 32 (P = 5): S + S / 32 + 32 / 2^L (the 64-bit pitch, 2 mod 32 at 8 rows, was 2-way
-// conflicted on pass A's first-step writes and both passes' second-step reads: 22 M conflict cycles
-// per configs[4] trace LDE). Radix 16 keeps row_pitch.
-__host__ __device__ constexpr int split_pitch(int S, int P, int L) {
-    return P == 5 ? S + (S >> 5) + ((32 >> L) & 31) : row_pitch(S, P, L);
-}
+// element i of an LDS tile row sits at i + (i >> P): one pad word per 2^P elements (row_pitch, ntt_plan.hpp)
 template <int P>
 __device__ __forceinline__ int phys(int i) { return i + (i >> P); }
+
 // phys(j + o) for an offset o that is a compile-time constant after unrolling: a multiple of 2^P
 // splits off as a constant (the LDS instruction's immediate offset), so the per-lane index
 // phys(j) is computed once per group instead of once per element
@@ -291,7 +276,6 @@ __device__ __forceinline__ void pass_dft_split(u32* tile, int lognseq, const u64
     __syncthreads();
 }
 
-__host__ __device__ u64 fourstep_main(int logn, int logbeta);
 struct NttArgs {
     const u64* in;
     u64* y;
@@ -303,12 +287,13 @@ struct NttArgs {
     u64 scale;    // inverse: n^-1
     u64 keep;     // inverse: coefficients written
     const u64* t4;  // four-step twiddle table (FourStep) or nullptr
-    const u64* pt;  // pass tables: w_R^(+-i) [R], w_C^(+-i) [C], forward coset pre-factors [beta][R]; or nullptr
+    const u64* pt;  // pass tables (PassTableLayout), or nullptr
     int xcd;        // 1 / 2: XCD-contiguous block order of pass A / B (xcd_block); 4: pass A cosets
                     // of a tile consecutive (xcd_block_coset)
     int tq_b;       // forward: pass B applies the four-step twiddles as it loads (ntt_pass_a_cos)
     int preg;       // forward pass A: coset pre-factors read from the pass tables in L2, not LDS
     Tables T;
+    __device__ PassTableLayout tab() const { return {logR, logC, logbeta}; }
 };
 
 // Workgroups are dealt round-robin over the 8 XCDs, each with its own L2. When a pass writes less
@@ -351,14 +336,14 @@ __device__ __forceinline__ void xcd_block_coset(int logbeta, int& bx, int& by) {
 // LDS, one block per CU: 16 columns per tile even at R = 1024)
 template <int LOGR, bool INV, int LOGT, int LOGE>
 __global__ __launch_bounds__(1 << LOGT, (1 << (10 - LOGT)) >> (LOGE - 4)) void ntt_pass_a(NttArgs a) {
-    constexpr int R = 1 << LOGR, PITCH = row_pitch(R, LOGE, LOGT + LOGE - LOGR), RR = Plan<LOGR, LOGE>::LAST_R,
-                  NT = 1 << LOGT;
+    constexpr int R = 1 << LOGR, RR = Plan<LOGR, LOGE>::LAST_R, NT = 1 << LOGT;
     extern __shared__ u64 lds[];
     const int logTC = (a.logC < LOGT + LOGE - LOGR) ? a.logC : LOGT + LOGE - LOGR;
     const int TC = 1 << logTC;
+    const LdsLayout L = lds_pass_a(LOGR, LOGT, LOGE, a.logC, false);
     u64* tile = lds;
-    u64* ltw = lds + TC * PITCH;
-    u64* pre = ltw + R;  // forward: 7^(C j1) w_(beta R)^(t j1) for this block's coset
+    u64* ltw = lds + L.tw;
+    u64* pre = lds + L.pre;  // forward: 7^(C j1) w_(beta R)^(t j1) for this block's coset
     // one block per (column tile, poly, coset); y is [poly][coset][R][C]
     int bx, by;
     if (!INV && (a.xcd & 4)) xcd_block_coset(a.logbeta, bx, by);
@@ -368,11 +353,12 @@ __global__ __launch_bounds__(1 << LOGT, (1 << (10 - LOGT)) >> (LOGE - 4)) void n
     const u64 n = 1ULL << a.logn;
     const int logN = a.logn + a.logbeta;
     const u64 maskN = (1ULL << logN) - 1;
+    const PassTableLayout TL{LOGR, a.logC, a.logbeta};
     if (a.pt) {
         // contiguous per-size tables (behind the four-step table, or standalone): coalesced loads
         for (int i = threadIdx.x; i < R; i += NT) {
             ltw[i] = a.pt[i];
-            if (!INV && !a.preg) pre[i] = a.pt[R + (1 << a.logC) + t * R + i];
+            if (!INV && !a.preg) pre[i] = a.pt[TL.pre(t) + i];
         }
     } else {
         for (int i = threadIdx.x; i < R; i += NT) {
@@ -386,7 +372,7 @@ __global__ __launch_bounds__(1 << LOGT, (1 << (10 - LOGT)) >> (LOGE - 4)) void n
     const u64* in = a.in + (u64)poly * a.in_stride;
     u64* y = a.y + (u64)pt * n;
     const auto rin = buf_rsrc(in + col0), ry = buf_rsrc(y + col0);
-    const u64* preg = (!INV && a.preg) ? a.pt + R + (1 << a.logC) + (u64)t * R : nullptr;
+    const u64* preg = (!INV && a.preg) ? a.pt + TL.pre(0) + (u64)t * R : nullptr;  // row t of the [beta][R] table
     auto ldg = [&](int seq, int j, int o) -> u64 {
         const u64 v = buf_ld(rin, (((u32)j << a.logC) + seq) * 8, ((u32)o << a.logC) * 8);
         if (INV) return v;
@@ -456,21 +442,22 @@ __global__ __launch_bounds__(1 << LOGT, (1 << (10 - LOGT)) >> (LOGE - 4)) void n
 // one first-step group per thread (256 x 16 tiles of R = 256: 16 columns).
 template <int LOGR>
 __global__ __launch_bounds__(256, 3) void ntt_pass_a_cos(NttArgs a) {
-    constexpr int LOGT = 8, LOGE = 4, NT = 1 << LOGT, R = 1 << LOGR, PITCH = row_pitch(R);
+    constexpr int LOGT = 8, LOGE = 4, NT = 1 << LOGT, R = 1 << LOGR;
     using PL = Plan<LOGR, LOGE>;
     constexpr int R1 = 1 << PL::FIRST_LOGR, G1 = R / R1, RR = PL::LAST_R;
     static_assert((1 << LOGE) / R1 == 1, "one first-step group per thread");
     extern __shared__ u64 lds[];
     const int logTC = (a.logC < LOGT + LOGE - LOGR) ? a.logC : LOGT + LOGE - LOGR;
     const int TC = 1 << logTC;
+    const LdsLayout L = lds_pass_a(LOGR, LOGT, LOGE, a.logC, false);
     u64* tile = lds;
-    u64* ltw = lds + TC * PITCH;
-    u64* pre = ltw + R;
+    u64* ltw = lds + L.tw;
+    u64* pre = lds + L.pre;
     const int poly = blockIdx.y, col0 = blockIdx.x * TC;
     const u64 n = 1ULL << a.logn;
     const int beta = 1 << a.logbeta;
     const u64* pt4 = a.pt;
-    const u64* pre_all = pt4 + R + (1 << a.logC);  // [t][R]
+    const u64* pre_all = pt4 + PassTableLayout{LOGR, a.logC, a.logbeta}.pre(0);  // [t][R]
     for (int i = threadIdx.x; i < R; i += NT) {
         ltw[i] = pt4[i];
         pre[i] = pre_all[i];
@@ -526,7 +513,7 @@ __device__ __forceinline__ u64 mul_w64pow(u64 x) {  // x * w_64^R_ = x * 2^(39 R
     else return mul_pow2<e - 96>(P - x);  // 2^96 = -1; P - x is -x for any canonical x
 }
 __global__ __launch_bounds__(256, 4) void ntt_pass_a_cos2(NttArgs a) {
-    constexpr int LOGR = 8, LOGT = 8, LOGE = 4, NT = 1 << LOGT, R = 1 << LOGR, PITCH = row_pitch(R);
+    constexpr int LOGR = 8, LOGT = 8, LOGE = 4, NT = 1 << LOGT, R = 1 << LOGR;
     using PL = Plan<LOGR, LOGE>;
     constexpr int R1 = 1 << PL::FIRST_LOGR, G1 = R / R1, RR = PL::LAST_R;
     static_assert(R1 == 16 && G1 == 16 && RR == 16 && PL::NSTEP == 2, "16 x 16 column DFTs");
@@ -534,12 +521,13 @@ __global__ __launch_bounds__(256, 4) void ntt_pass_a_cos2(NttArgs a) {
     const int logTC = (a.logC < LOGT + LOGE - LOGR) ? a.logC : LOGT + LOGE - LOGR;
     const int TC = 1 << logTC;
     u64* tile = lds;
-    u64* comb = lds + TC * PITCH;  // [r][k] second-step twiddles of the current coset
+    u64* comb = lds + lds_pass_a(LOGR, LOGT, LOGE, a.logC, false).tw;  // [r][k] second-step twiddles of the current coset
     const int poly = blockIdx.y, col0 = blockIdx.x * TC;
     const u64 n = 1ULL << a.logn;
     const int beta = 1 << a.logbeta, M = beta >> 2, KP = beta / M;
-    const u64* comb_all = a.pt + R + (1 << a.logC) + ((u64)R << a.logbeta);  // [t][16][16]
-    const u64* scal = comb_all + ((u64)R << a.logbeta);                        // [c][16]
+    const PassTableLayout TL{LOGR, a.logC, a.logbeta};
+    const u64* comb_all = a.pt + TL.comb((u64)0);  // [t][16][16]
+    const u64* scal = a.pt + TL.cos2_scal();  // [c][16]
     const int g = threadIdx.x, seq0 = g & (TC - 1), j0 = g >> logTC;
     const auto rin = buf_rsrc(a.in + (u64)poly * a.in_stride + col0);
     u64 cnext = comb_all[threadIdx.x];  // coset 0's table (class 0, k = 0)
@@ -595,20 +583,20 @@ __global__ __launch_bounds__(256, 4) void ntt_pass_a_cos2(NttArgs a) {
 //    requests).
 __global__ __launch_bounds__(256, 3) void ntt_pass_a_r1024(NttArgs a) {
     constexpr int LOGR = 10, LOGE = 5, NT = 256, R = 1 << LOGR, RR = 32, logTC = 3, TC = 1 << logTC;
-    constexpr int PITCH = split_pitch(R, LOGE, NT_LOG2(NT) + LOGE - LOGR);
     extern __shared__ u64 lds[];
+    constexpr LdsLayout L = lds_r1024(false);
     u32* tile = reinterpret_cast<u32*>(lds);
-    u64* comb = lds + (TC * PITCH + 1) / 2;
-    u64* pre2 = comb + R;  // [r][seq]: first-step factors of this tile's 8 columns
+    u64* comb = lds + L.tw;
+    u64* pre2 = lds + L.pre;  // [r][seq]: first-step factors of this tile's 8 columns
     int bx, by;
     xcd_block_coset(a.logbeta, bx, by);
     const int pt = by, col0 = bx * TC, poly = pt >> a.logbeta, t = pt & ((1 << a.logbeta) - 1);
     const u64 n = 1ULL << a.logn;
-    const u64* pre = a.pt + R + (1 << a.logC) + (u64)t * R;                                     // g_t^j1
-    const u64* comb_t = a.pt + R + (1 << a.logC) + ((u64)R << a.logbeta) + ((u64)t << LOGR);  // [r][k]
-    const u64* xt = a.pt + R + (1 << a.logC) + ((u64)(2 * R) << a.logbeta);
-    const u64* seed_t = xt + ((u64)t << 10);                   // [t][j2] s_t(j2)
-    const u64* t4 = xt + ((u64)1 << (10 + a.logbeta));          // [k1][j2] w_n^(j2 k1)
+    const PassTableLayout TL{LOGR, a.logC, a.logbeta};
+    const u64* pre = a.pt + TL.pre((u64)t);            // g_t^j1
+    const u64* comb_t = a.pt + TL.comb((u64)t);        // [r][k]
+    const u64* seed_t = a.pt + TL.r1024_seed((u64)t);  // [t][j2] s_t(j2)
+    const u64* t4 = a.pt + TL.r1024_t4();         // [k1][j2] w_n^(j2 k1)
     for (int i = threadIdx.x; i < R; i += NT) comb[i] = comb_t[i];
     // (comb is read only by the second step, behind pass_dft_split's first barrier; the first step's
     // element r of group j is row j + 32 r)
@@ -634,7 +622,6 @@ __global__ __launch_bounds__(256, 3) void ntt_pass_a_r1024(NttArgs a) {
     pass_dft_split<LOGR, LOGE, false, true, NT, decltype(ldg), decltype(stg), NoPf, true>(tile, logTC, comb, ldg, stg,
                                                                                        NoPf{});
 }
-size_t pass_a_r1024_lds() { return (size_t)((8 * split_pitch(1024, 5, 3) + 1) / 2 + 1024 + 256) * sizeof(u64); }
 
 // Forward pass B of the same LDEs: row DFTs of C = 1024 (radix 32 x 32), one 8-row tile per 256-thread
 // block with the exchange in 32-bit halves (three blocks per CU). The first step walks the tile-major
@@ -642,15 +629,15 @@ size_t pass_a_r1024_lds() { return (size_t)((8 * split_pitch(1024, 5, 3) + 1) / 
 // instruction); canonical outputs are stored as row pairs (store_pairs) into the coset-major LDE.
 __global__ __launch_bounds__(256, 3) void ntt_pass_b_r1024(NttArgs a) {
     constexpr int LOGC = 10, LOGE = 5, NT = 256, C = 1 << LOGC, R1 = 32, G1 = C / R1, RR = 32, logTR = 3;
-    constexpr int TR = 1 << logTR, PITCH = split_pitch(C, LOGE, logTR);
+    constexpr int TR = 1 << logTR;
     extern __shared__ u64 lds[];
     u32* tile = reinterpret_cast<u32*>(lds);
-    u64* ltw = lds + (TR * PITCH + 1) / 2;
+    u64* ltw = lds + lds_r1024(true).tw;
     int bx, by;
     xcd_block(true, bx, by);
     const int pt = by, k10 = bx * TR;
     const u64 n = 1ULL << a.logn;
-    for (int i = threadIdx.x; i < C; i += NT) ltw[i] = a.pt[(1 << a.logR) + i];
+    for (int i = threadIdx.x; i < C; i += NT) ltw[i] = a.pt[a.tab().wC() + i];
     // this thread's first-step group (stockham, SEQ_FAST): row seq0 of the tile, columns j0 + 32 r
     const int seq0 = threadIdx.x & (TR - 1), j0 = threadIdx.x >> logTR;
     const auto ry = buf_rsrc(a.y + (u64)pt * n);
@@ -667,7 +654,6 @@ __global__ __launch_bounds__(256, 3) void ntt_pass_b_r1024(NttArgs a) {
     pass_dft_split<LOGC, LOGE, false, true, NT, decltype(ldg), decltype(stg), NoPf, false, true>(tile, logTR, ltw, ldg, stg,
                                                                                               NoPf{});
 }
-size_t pass_b_r1024_lds() { return (size_t)((8 * split_pitch(1024, 5, 3) + 1) / 2 + 1024) * sizeof(u64); }
 
 // ---------------------------------------------------------------- pass B: row DFTs (size C)
 template <int LOGC, bool INV, int LOGT, int LOGE>
@@ -677,13 +663,13 @@ __global__ __launch_bounds__(1 << LOGT) void ntt_pass_b(NttArgs a) {
     const int logTR = (a.logR < LOGT + LOGE - LOGC) ? a.logR : LOGT + LOGE - LOGC;
     const int TR = 1 << logTR;
     u64* tile = lds;
-    u64* ltw = lds + TR * row_pitch(C, LOGE, LOGT + LOGE - LOGC);
+    u64* ltw = lds + lds_pass_b(LOGC, LOGT, LOGE, a.logR).tw;
     int bx, by;
     xcd_block(a.xcd & 2, bx, by);
     const int pt = by, k10 = bx * TR;
     const u64 n = 1ULL << a.logn;
     if (a.pt) {
-        const u64* pt4 = a.pt + (1 << a.logR);
+        const u64* pt4 = a.pt + a.tab().wC();
         for (int i = threadIdx.x; i < C; i += NT) ltw[i] = pt4[i];
     } else {
         for (int i = threadIdx.x; i < C; i += NT) ltw[i] = tw_get(a.T, LOGC, i, INV);
@@ -757,8 +743,7 @@ __global__ __launch_bounds__(1 << LOGT) void ntt_pass_b_tq(NttArgs a) {
     const int logTR = (a.logR < LOGT + LOGE - LOGC) ? a.logR : LOGT + LOGE - LOGC;
     const int TR = 1 << logTR;
     u64* tile = lds;
-    const int tw = TR * row_pitch(C, LOGE, LOGT + LOGE - LOGC);
-    u64* ltw = reinterpret_cast<u64*>(reinterpret_cast<u32*>(lds) + tw);
+    u64* ltw = reinterpret_cast<u64*>(reinterpret_cast<u32*>(lds) + lds_pass_b_tq(LOGC, LOGT, LOGE, a.logR).tw);
     int bx, by;
     xcd_block(a.xcd & 2, bx, by);
     const int pt = by, k10 = bx * TR;
@@ -768,7 +753,7 @@ __global__ __launch_bounds__(1 << LOGT) void ntt_pass_b_tq(NttArgs a) {
         // LDS offset r * 128 from the lane's k * 8, so no per-element address arithmetic (w_C[r k]
         // needs a multiply and an add per element)
         static_assert(LOGC == 2 * LOGE, "two full-radix steps");
-        const u64* pt4 = a.pt + (1 << a.logR);
+        const u64* pt4 = a.pt + a.tab().wC();
         for (int i = threadIdx.x; i < C; i += NT) ltw[i] = pt4[(i >> LOGE) * (i & ((1 << LOGE) - 1))];
     }
     const int seq0 = threadIdx.x / G1, j0 = threadIdx.x % G1;
@@ -812,9 +797,9 @@ __global__ __launch_bounds__(1 << LOGT, MINW) void ntt_pass_b_pers(NttArgs a, in
     constexpr int logTR = LOGT + LOGE - LOGC, TR = 1 << logTR;
     extern __shared__ u64 lds[];
     u64* tile = lds;
-    u64* ltw = lds + TR * row_pitch(C, LOGE, logTR);
+    u64* ltw = lds + lds_pass_b(LOGC, LOGT, LOGE, LOGT + LOGE - LOGC).tw;
     {
-        const u64* pt4 = a.pt + (1 << a.logR);
+        const u64* pt4 = a.pt + a.tab().wC();
         for (int i = threadIdx.x; i < C; i += NT) ltw[i] = pt4[i];
     }
     __syncthreads();
@@ -849,127 +834,7 @@ __global__ __launch_bounds__(1 << LOGT, MINW) void ntt_pass_b_pers(NttArgs a, in
     }
 }
 
-// ---------------------------------------------------------------- dispatch
-// tiles above 64 KiB of LDS need the per-kernel opt-in (a workgroup may use 160 KiB on gfx950)
-#define XFG_NTT_LAUNCH(KERNEL, NT)                                                                          \
-    do {                                                                                                    \
-        if (lds > 65536) {                                                                                  \
-            static const bool ok_ = hipFuncSetAttribute((const void*)KERNEL,                                \
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize,         \
-                                                        160 * 1024) == hipSuccess;                          \
-            (void)ok_;                                                                                      \
-        }                                                                                                   \
-        hipLaunchKernelGGL(KERNEL, g, dim3(NT), lds, s, a);                                                 \
-    } while (0)
-template <bool INV>
-static void run_pass_a(int logR, int logT, int logE, dim3 g, size_t lds, hipStream_t s, const NttArgs& a) {
-#define XFG_CASE_A(L) \
-    case L: XFG_NTT_LAUNCH((ntt_pass_a<L, INV, 8, 4>), 256); break;
-#define XFG_CASE_A10(L) \
-    case L: XFG_NTT_LAUNCH((ntt_pass_a<L, INV, 10, 4>), 1024); break;
-#define XFG_CASE_A9(L) \
-    case L: XFG_NTT_LAUNCH((ntt_pass_a<L, INV, 9, 4>), 512); break;
-#define XFG_CASE_A5(L, T) \
-    case L: XFG_NTT_LAUNCH((ntt_pass_a<L, INV, T, 5>), (1 << T)); break;
-    if (logE == 5) {
-        if (logT == 9) {
-            switch (logR) {
-                XFG_CASE_A5(9, 9) XFG_CASE_A5(10, 9)
-                default: break;
-            }
-        } else {
-            switch (logR) {
-                XFG_CASE_A5(9, 8) XFG_CASE_A5(10, 8)
-                default: break;
-            }
-        }
-        return;
-    }
-    if (logT == 10) {
-        switch (logR) {
-            XFG_CASE_A10(9) XFG_CASE_A10(10)
-            default: break;
-        }
-        return;
-    }
-    if (logT == 9) {
-        switch (logR) {
-            XFG_CASE_A9(9) XFG_CASE_A9(10)
-            default: break;
-        }
-        return;
-    }
-    switch (logR) {
-        XFG_CASE_A(1) XFG_CASE_A(2) XFG_CASE_A(3) XFG_CASE_A(4) XFG_CASE_A(5) XFG_CASE_A(6)
-        XFG_CASE_A(7) XFG_CASE_A(8) XFG_CASE_A(9) XFG_CASE_A(10)
-        default: break;
-    }
-#undef XFG_CASE_A
-#undef XFG_CASE_A10
-#undef XFG_CASE_A9
-#undef XFG_CASE_A5
-}
-template <bool INV>
-static void run_pass_b(int logC, int logT, int logE, dim3 g, size_t lds, hipStream_t s, const NttArgs& a) {
-#define XFG_CASE_B(L) \
-    case L: XFG_NTT_LAUNCH((ntt_pass_b<L, INV, 8, 4>), 256); break;
-#define XFG_CASE_B10(L) \
-    case L: XFG_NTT_LAUNCH((ntt_pass_b<L, INV, 10, 4>), 1024); break;
-#define XFG_CASE_B9(L) \
-    case L: XFG_NTT_LAUNCH((ntt_pass_b<L, INV, 9, 4>), 512); break;
-#define XFG_CASE_B5(L, T) \
-    case L: XFG_NTT_LAUNCH((ntt_pass_b<L, INV, T, 5>), (1 << T)); break;
-    if (logE == 5) {
-        if (logT == 9) {
-            switch (logC) {
-                XFG_CASE_B5(9, 9) XFG_CASE_B5(10, 9)
-                default: break;
-            }
-        } else {
-            switch (logC) {
-                XFG_CASE_B5(9, 8) XFG_CASE_B5(10, 8)
-                default: break;
-            }
-        }
-        return;
-    }
-    if (logT == 10) {
-        switch (logC) {
-            XFG_CASE_B10(9) XFG_CASE_B10(10) XFG_CASE_B10(11)
-            default: break;
-        }
-        return;
-    }
-    if (logT == 9) {
-        switch (logC) {
-            XFG_CASE_B9(9) XFG_CASE_B9(10) XFG_CASE_B9(11)
-            default: break;
-        }
-        return;
-    }
-    switch (logC) {
-        XFG_CASE_B(2) XFG_CASE_B(3) XFG_CASE_B(4) XFG_CASE_B(5) XFG_CASE_B(6) XFG_CASE_B(7)
-        XFG_CASE_B(8) XFG_CASE_B(9) XFG_CASE_B(10) XFG_CASE_B(11) XFG_CASE_B(12)
-        default: break;
-    }
-#undef XFG_CASE_B
-#undef XFG_CASE_B10
-#undef XFG_CASE_B9
-#undef XFG_CASE_B5
-}
-#undef XFG_NTT_LAUNCH
-
-// split n = R * C: evenly below 2^18, C = 2R from 2^18 on except 2^20 (faster at 2^18; see
-// scripts/ntt_split.py; at 2^24 the splits C = 512 / 2048 / 4096 measured slower than 1024)
-static void ntt_split(int logn, int& logR, int& logC) {
-    if (logn >= 18) {
-        logC = logn == 20 ? 10 : logn / 2 + 1;  // 2^20: R = C = 1024, both passes wide-tiled (3 % faster)
-    } else {
-        logC = logn - logn / 2;
-    }
-    logR = logn - logC;
-}
-
+// ---------------------------------------------------------------- tables
 __global__ void fourstep_kernel(u64* out, int logn, int logbeta, int logC, u64 scale, Tables T) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     const u64 n = 1ULL << logn;
@@ -984,195 +849,119 @@ __global__ void fourstep_kernel(u64* out, int logn, int logbeta, int logC, u64 s
         out[i] = gl_mul(T.pow7[j2], tw_get(T, logN, (j2 * (t + (k1 << logbeta))) & ((1ULL << logN) - 1), false));
     }
 }
-// pass tables appended to a four-step table: w_R^(+-i) (i < R), w_C^(+-i) (i < C), and for the
-// forward LDE the coset pre-factors 7^(C i) w_(beta R)^(t i) at [t][i] -- what every pass block
-// would otherwise gather from the master tables at its start
-__global__ void pass_tables_kernel(u64* out, int logn, int logbeta, int logR, int logC, Tables T) {
+// the pass tables (PassTableLayout, ntt_plan.hpp): what every pass block would otherwise gather from
+// the master tables at its start
+__global__ void pass_tables_kernel(u64* out, PassTableLayout L, Tables T) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    const u64 R = 1ULL << logR, C = 1ULL << logC;
-    const bool inv = logbeta < 0;
-    if (i < R) {
-        out[i] = tw_get(T, logR, i, inv);
-    } else if (i < R + C) {
-        out[i] = tw_get(T, logC, i - R, inv);
-    } else if (!inv && i < R + C + (R << logbeta)) {
-        const u64 t = (i - R - C) >> logR, j = (i - R - C) & (R - 1);
+    const int logR = L.logR, logC = L.logC, logbeta = L.logbeta;
+    const u64 R = L.R(), C = L.C(), Z = 0;
+    if (i >= L.total()) return;
+    if (i < L.wC()) {
+        out[i] = tw_get(T, logR, i, !L.fwd());
+    } else if (i < L.pre(Z)) {
+        out[i] = tw_get(T, logC, i - L.wC(), !L.fwd());
+    } else if (i < L.comb(Z)) {
+        const u64 t = (i - L.pre(Z)) >> logR, j = (i - L.pre(Z)) & (R - 1);
         out[i] = gl_mul(T.pow7[j << logC], tw_get(T, logR + logbeta, (t * j) & ((1ULL << (logR + logbeta)) - 1), false));
-    } else if (!inv && logR == 10 && i < R + C + 2 * (R << logbeta)) {
+    } else if (L.has_r1024() && i < L.r1024_seed(Z)) {
         // ntt_pass_a_r1024: [t][r][k] = w_1024^(r k) g_t^r, g_t^r = 7^(C r) w_(beta R)^(t r)  (r, k < 32)
-        const u64 q = i - R - C - (R << logbeta);
+        const u64 q = i - L.comb(Z);
         const u64 t = q >> 10, r = (q >> 5) & 31, k = q & 31;
         const u64 g = gl_mul(T.pow7[r << logC], tw_get(T, logR + logbeta, (t * r) & ((1ULL << (logR + logbeta)) - 1), false));
         out[i] = gl_mul(tw_get(T, logR, r * k, false), g);
-    } else if (!inv && logR == 10 && i < R + C + 2 * (R << logbeta) + (C << logbeta) + R * C) {
+    } else if (L.has_r1024()) {
         // ntt_pass_a_r1024's four-step factors: [t][j2] 7^j2 w_N^(j2 t) (t < beta, j2 < C) and the
         // t-independent four-step table [k1][j2] w_n^(j2 k1) (R x C)
-        const u64 q = i - R - C - 2 * (R << logbeta);
         const int logn = logR + logC, logN = logn + logbeta;
-        if (q < (C << logbeta)) {
-            const u64 t = q >> logC, j2 = q & (C - 1);
+        const u64 j2 = i & (C - 1);  // both regions start at multiples of C
+        if (i < L.r1024_t4()) {
+            const u64 t = (i - L.r1024_seed(Z)) >> logC;
             out[i] = gl_mul(T.pow7[j2], tw_get(T, logN, (j2 * t) & ((1ULL << logN) - 1), false));
         } else {
-            const u64 k1 = (q - (C << logbeta)) >> logC, j2 = q & (C - 1);
+            const u64 k1 = (i - L.r1024_t4()) >> logC;
             out[i] = tw_get(T, logn, (j2 * k1) & ((1ULL << logn) - 1), false);
         }
-    } else if (!inv && logR == 8 && logbeta >= 2) {
-        // ntt_pass_a_cos2: [t][r][k] = w_R^(r k) 7^(C r) w_(beta R)^(t r), then [c][r] = 7^(16 C r) w_(16 beta)^(c r)
-        const u64 q = i - R - C - (R << logbeta);
-        const u64 M = 1ULL << (logbeta - 2);
-        if (q < (R << logbeta)) {
-            const u64 t = q >> 8, r = (q >> 4) & 15, k = q & 15;
-            const u64 grp = gl_mul(T.pow7[r << logC], tw_get(T, logR + logbeta, (t * r) & ((1ULL << (logR + logbeta)) - 1), false));
-            out[i] = gl_mul(tw_get(T, logR, r * k, false), grp);
-        } else if (q < (R << logbeta) + 16 * M) {
-            const u64 c = (q - (R << logbeta)) >> 4, r = q & 15;
-            out[i] = gl_mul(T.pow7[(16 * r) << logC], tw_get(T, 4 + logbeta, (c * r) & ((1ULL << (4 + logbeta)) - 1), false));
-        }
+    } else if (i < L.cos2_scal()) {
+        // ntt_pass_a_cos2: [t][r][k] = w_R^(r k) 7^(C r) w_(beta R)^(t r)
+        const u64 q = i - L.comb(Z);
+        const u64 t = q >> 8, r = (q >> 4) & 15, k = q & 15;
+        const u64 grp = gl_mul(T.pow7[r << logC], tw_get(T, logR + logbeta, (t * r) & ((1ULL << (logR + logbeta)) - 1), false));
+        out[i] = gl_mul(tw_get(T, logR, r * k, false), grp);
+    } else {
+        // ntt_pass_a_cos2: [c][r] = 7^(16 C r) w_(16 beta)^(c r)
+        const u64 q = i - L.cos2_scal();
+        const u64 c = q >> 4, r = q & 15;
+        out[i] = gl_mul(T.pow7[(16 * r) << logC], tw_get(T, 4 + logbeta, (c * r) & ((1ULL << (4 + logbeta)) - 1), false));
     }
 }
-// entries of the ntt_pass_a_cos2 tables appended to the forward pass tables (R = 256, beta >= 4), or of
-// the ntt_pass_a_r1024 tables (R = 1024)
-static u64 cos2_extra(int logR, int logC, int logbeta) {
-    if (logbeta >= 0 && logR == 10 && logC == 10) return (1ULL << (logR + logbeta)) + (1ULL << (logC + logbeta)) + (1ULL << (logR + logC));
-    return (logbeta >= 0 && logR == 8 && logbeta >= 2) ? ((1ULL << (logR + logbeta)) + (16ULL << (logbeta - 2))) : 0;
-}
-u64 pass_tables_size(int logn, int logbeta) {
-    int logR, logC;
-    ntt_split(logn, logR, logC);
-    return (1ULL << logR) + (1ULL << logC) + (logbeta >= 0 ? (1ULL << (logR + logbeta)) : 0) + cos2_extra(logR, logC, logbeta);
-}
 void build_pass_tables(u64* out, int logn, int logbeta, const Tables& T, hipStream_t s) {
-    int logR, logC;
-    ntt_split(logn, logR, logC);
-    const u64 cnt = pass_tables_size(logn, logbeta);
-    hipLaunchKernelGGL(pass_tables_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, out, logn, logbeta,
-                       logR, logC, T);
-}
-__host__ __device__ u64 fourstep_main(int logn, int logbeta) { return 1ULL << (logn + (logbeta > 0 ? logbeta : 0)); }
-u64 fourstep_size(int logn, int logbeta) {
-    int logR, logC;
-    ntt_split(logn, logR, logC);
-    return fourstep_main(logn, logbeta) + (1ULL << logR) + (1ULL << logC) + (logbeta >= 0 ? (1ULL << (logR + logbeta)) : 0) +
-           cos2_extra(logR, logC, logbeta);
+    const PassTableLayout L = pass_table_layout(logn, logbeta);
+    hipLaunchKernelGGL(pass_tables_kernel, dim3((unsigned)((L.total() + 255) / 256)), dim3(256), 0, s, out, L, T);
 }
 void build_fourstep(u64* out, int logn, int logbeta, const Tables& T, hipStream_t s) {
-    int logR, logC;
-    ntt_split(logn, logR, logC);
-    const u64 cnt = fourstep_main(logn, logbeta), extra = fourstep_size(logn, logbeta) - cnt;
-    hipLaunchKernelGGL(fourstep_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, out, logn, logbeta, logC,
-                       gl_inv(1ULL << logn), T);
-    hipLaunchKernelGGL(pass_tables_kernel, dim3((unsigned)((extra + 255) / 256)), dim3(256), 0, s, out + cnt, logn,
-                       logbeta, logR, logC, T);
+    const u64 cnt = fourstep_main(logn, logbeta);
+    hipLaunchKernelGGL(fourstep_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, out, logn, logbeta,
+                       pass_table_layout(logn, logbeta).logC, gl_inv(1ULL << logn), T);
+    build_pass_tables(out + cnt, logn, logbeta, T, s);
+}
+
+// ---------------------------------------------------------------- dispatch
+// every kernel ntt_plan can name, with its key: XFG_NTT_KERNELS (ntt_plan.hpp) is the only list
+struct NttEntry {
+    NttKey key;
+    const void* fn;
+    std::atomic<bool> big_lds;  // the opt-in for more than 64 KiB of dynamic LDS has been made (and has returned)
+};
+#define XFG_NTT_ENTRY(K, SYM, S, INV, T, E) {{NttKernel::K, S, T, E, INV}, (const void*)SYM},
+static NttEntry ntt_entries[] = {XFG_NTT_KERNELS(XFG_NTT_ENTRY)};
+#undef XFG_NTT_ENTRY
+
+static void ntt_launch(const NttPass& p, void** args, hipStream_t s) {
+    for (NttEntry& e : ntt_entries) {
+        if (!(e.key == p.key)) continue;
+        // more than 64 KiB of LDS needs the per-kernel opt-in (a workgroup may use 160 KiB on gfx950)
+        // (lanes launch concurrently: the flag is set only once a call has returned; a second call is harmless)
+        if (p.lds > 65536 && !e.big_lds.load(std::memory_order_acquire)) {
+            HIPCHK(hipFuncSetAttribute(e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            e.big_lds.store(true, std::memory_order_release);
+        }
+        HIPCHK(hipLaunchKernel(e.fn, dim3(p.gx, p.gy), dim3(p.block), args, p.lds, s));
+        return;
+    }
+    throw std::runtime_error("NTT: planned kernel is not in the kernel list");
 }
 
 static void ntt_run(NttArgs& a, int npoly, bool inv, hipStream_t s) {
-    ntt_split(a.logn, a.logR, a.logC);
-    const int R = 1 << a.logR, C = 1 << a.logC;
-    // Pass shapes (the alternatives named there measured slower on the box):
-    // * radix-32 steps (32 elements per thread) for pass sizes 2^9 and 2^10: 16 x 32 and 32 x 32
-    //   instead of 2 x 16 x 16 and 4 x 16 x 16, one general-twiddle step fewer;
-    // * wide tiles (1024 threads, 16384 elements) where a 4096-element radix-16 tile would hold fewer
-    //   than 16 columns (pass A, R >= 512) or rows (pass B, C >= 512), so the scattered stores write
-    //   whole 128 B lines; pass B at C <= 1024 runs 512-thread blocks (8192 elements, <= 78 KiB, two
-    //   blocks per CU: one block's barriers and loads hide behind the other's butterflies);
-    // * radix-32 tiles: pass A 16 columns (512 threads at R = 1024, 256 at R = 512; the forward
-    //   R = 1024 pass past the four-step tables at other C, e.g. 2^21, 256 threads x 8 columns with the
-    //   coset pre-factors read from L2 -- 76 KiB of LDS, two blocks per CU), pass B 8192 elements (256
-    //   threads, two blocks per CU). configs[4]'s 2^20 takes the dedicated R = C = 1024 passes below.
-    const int eA = (a.logR >= 9 && a.logR <= 10 && a.logC >= 4) ? 5 : 4;
-    const int eB = (a.logC >= 9 && a.logC <= 10 && a.logR >= 3) ? 5 : 4;
-    const bool capA = a.logR >= 9 && a.logR <= 10 && a.logC >= 4, capB = a.logC >= 9 && a.logC <= 11 && a.logR >= 4;
-    int ltA = capA ? 10 : 8;
-    int ltB = capB ? (a.logC <= 10 ? 9 : 10) : 8;
-    if (eA == 5) ltA = (!inv && a.logR == 10 && a.pt) ? 8 : a.logR - 1;
-    if (eB == 5) ltB = 8;
-    const int logTC = a.logC < ltA + eA - a.logR ? a.logC : ltA + eA - a.logR;
-    const int logTR = a.logR < ltB + eB - a.logC ? a.logR : ltB + eB - a.logC;
-    const int ncos = inv ? 1 : (1 << a.logbeta);
-    a.preg = (!inv && a.pt && eA == 5 && ltA == 8 && a.logR == 10) ? 1 : 0;
-    size_t lds_a = ((size_t)(1 << logTC) * row_pitch(R, eA, ltA + eA - a.logR) + (a.preg ? 1 : 2) * R) * sizeof(u64);
-    size_t lds_b = ((size_t)(1 << logTR) * row_pitch(C, eB, ltB + eB - a.logC) + C) * sizeof(u64);
-    dim3 ga(C >> logTC, npoly * ncos), gb(R >> logTR, npoly * ncos);
-    // XCD-contiguous block order where a tile row of the scattered writes is narrower than a 128 B
-    // line: pass A stores TC consecutive words per row, pass B TR (xcd_block)
-    a.xcd = (logTC < 4 ? 1 : 0) | (logTR < 4 ? 2 : 0) | (a.preg ? 4 : 0);
-    if (inv) {
-        run_pass_a<true>(a.logR, ltA, eA, ga, lds_a, s, a);
-        run_pass_b<true>(a.logC, ltB, eB, gb, lds_b, s, a);
-        return;
-    }
-    if (!a.t4 && a.pt && a.logR == 10 && a.logC == 10 && eA == 5 && eB == 5) {
-        // past the four-step tables at n = 2^20 (configs[4])
-        const size_t la = pass_a_r1024_lds(), lb = pass_b_r1024_lds();
-        hipLaunchKernelGGL(ntt_pass_a_r1024, dim3(C >> 3, npoly << a.logbeta), dim3(256), la, s, a);
-        hipLaunchKernelGGL(ntt_pass_b_r1024, dim3(R >> 3, npoly << a.logbeta), dim3(256), lb, s, a);
-        return;
-    }
-    // pass A: all cosets of a column tile in one block where the four-step table exists (R = 256):
-    // shift-twisted cosets (ntt_pass_a_cos2) for beta >= 4, per-coset pre-factors (ntt_pass_a_cos) at
-    // beta = 2; the four-step twiddles are then applied by pass B as it loads (tq_b). Only for launch
-    // sets of >= 512 such blocks (two per CU): the all-coset grid is C / 16 blocks per polynomial, so
-    // a small set (one proof's trace: 7 polynomials, its composition or DEEP column: 1) leaves most CUs
-    // idle while each block walks its beta cosets, and one block per (tile, poly, coset) -- ntt_pass_a,
-    // beta times the grid -- finishes sooner: 2^16 x 8, 1 / 7 / 16 / 28 polynomials 52 / 67 / 77 / 110 us
-    // against 20 / 41 / 66 / 107 us; 32 / 64 / 224 polynomials 119 / 232 / 727 against 122 / 255 / 821
-    // (profiles/r06/lde_small.txt)
-    if (a.t4 && a.logR == 8 && ltA == 8 && eA == 4 && !(a.xcd & 1) && (u64)npoly * (C >> logTC) >= 512) {
-        a.tq_b = 1;
-        if (a.logbeta >= 2)
-            hipLaunchKernelGGL(ntt_pass_a_cos2, dim3(C >> logTC, npoly), dim3(256), lds_a, s, a);
-        else
-            hipLaunchKernelGGL(ntt_pass_a_cos<8>, dim3(C >> logTC, npoly), dim3(256), lds_a, s, a);
-    } else {
-        run_pass_a<false>(a.logR, ltA, eA, ga, lds_a, s, a);
-    }
-    if (eB == 5 && ltB == 8 && a.logC == 10 && a.logR >= 3 && !a.tq_b && a.pt) {
-        // past the four-step tables: persistent pass B (prefetches the next tile during this one)
-        static int cus = [] {
-            int dev = 0, n = 256;
-            if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-            return n;
-        }();
-        const int ntx = R >> logTR, ntiles = ntx * npoly * ncos;
-        const int nb = std::max(8, std::min(2 * cus, ntiles) & ~7);
-        hipLaunchKernelGGL((ntt_pass_b_pers<10, 8, 5, 2>), dim3(nb), dim3(256), lds_b, s, a, ntx, ntiles);
-    } else if (eB == 4 && ltB == 8 && a.logC == 8 && a.logR >= 4 && a.t4 && a.tq_b && a.pt) {
-        // the tabled LDE's pass B with the 32-bit split exchange (pass_dft_split): 19.5 instead of 37
-        // KiB of LDS per block, 6 instead of 4 waves per SIMD (pass B 919-942 vs 946-961 us per 64-proof
-        // launch set, same box)
-        const size_t l = ((size_t)(1 << logTR) * row_pitch(C, 4, 4) * 4 + C * 8);
-        hipLaunchKernelGGL((ntt_pass_b_tq<8, 8, 4>), gb, dim3(256), l, s, a);
-    } else {
-        run_pass_b<false>(a.logC, ltB, eB, gb, lds_b, s, a);
-    }
+    static const int cus = [] {
+        int dev = 0, n = 256;
+        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+        return n;
+    }();
+    NttPlan p = ntt_plan(a.logn, a.logbeta, inv, npoly, a.t4 != nullptr, a.pt != nullptr, cus);
+    if (!p.ok)
+        throw std::runtime_error((inv ? "inverse NTT of size 2^" : "forward NTT of size 2^") + std::to_string(a.logn) +
+                                 " has no kernel");
+    a.logR = p.logR, a.logC = p.logC;
+    a.xcd = p.xcd, a.tq_b = p.tq_b, a.preg = p.preg;
+    void* args[] = {&a, &p.ntx, &p.ntiles};  // the last two are ntt_pass_b_pers's alone
+    ntt_launch(p.a, args, s);
+    ntt_launch(p.b, args, s);
 }
 
 void launch_lde(const u64* coef, u64 coef_stride, u64* out, u64* scratch, int npoly, int logn, int logbeta,
                 const Tables& T, hipStream_t s) {
-    NttArgs a{};
-    a.in = coef;
-    a.in_stride = coef_stride;
-    a.y = scratch;
-    a.out = out;
-    a.logn = logn;
+    NttArgs a{coef, scratch, out, coef_stride, 0, logn};  // in, y, out, in_stride, out_stride, logn
     a.logbeta = logbeta;
     a.T = T;
-    a.t4 = (T.fs && logn <= FOURSTEP_MAX_LOG && logbeta <= 4) ? T.fs->fwd[logn][logbeta] : nullptr;
-    a.pt = a.t4 ? a.t4 + fourstep_main(logn, logbeta)
-                : ((T.fs && logn <= PASS_MAX_LOG && logbeta <= 4) ? T.fs->pass_fwd[logn][logbeta] : nullptr);
+    const TableKind k = T.fs ? table_kind(logn, logbeta) : TableKind::none;
+    a.t4 = k == TableKind::fourstep ? T.fs->fwd[logn][logbeta] : nullptr;
+    a.pt = a.t4 ? a.t4 + fourstep_main(logn, logbeta) : (k == TableKind::pass_only ? T.fs->pass_fwd[logn][logbeta] : nullptr);
     ntt_run(a, npoly, false, s);
 }
 
 void launch_interpolate(const u64* evals, u64 in_stride, u64* out, u64 out_stride, u64* scratch, int npoly, int logn,
                         bool off7, u64 keep, const Tables& T, hipStream_t s) {
-    NttArgs a{};
-    a.in = evals;
-    a.in_stride = in_stride;
-    a.y = scratch;
-    a.out = out;
-    a.out_stride = out_stride;
-    a.logn = logn;
-    a.logbeta = 0;
+    NttArgs a{evals, scratch, out, in_stride, out_stride, logn};  // in, y, out, in_stride, out_stride, logn
     a.off7 = off7 ? 1 : 0;
     a.keep = keep;
     a.T = T;
@@ -1180,66 +969,6 @@ void launch_interpolate(const u64* evals, u64 in_stride, u64* out, u64 out_strid
     a.t4 = (T.fs && logn <= FOURSTEP_MAX_LOG) ? T.fs->inv[logn] : nullptr;
     a.pt = a.t4 ? a.t4 + fourstep_main(logn, -1) : nullptr;
     ntt_run(a, npoly, true, s);
-}
-
-__global__ void field_op_kernel(int op, const u64* a, const u64* b, u64* out, u64 count) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    const u64 x = a[i], y = b[i];
-    u64 r = 0;
-    switch (op) {
-        case 0: r = gl_mul(x, y); break;
-        case 1: r = gl_add(x, y); break;
-        case 2: r = gl_sub(x, y); break;
-        case 3: r = gl_canon(x); break;
-        case 4: {
-            const int sh = (int)(y % 96);
-            static_for<96>([&](auto sc) {
-                if (sh == decltype(sc)::value) r = mul_pow2<decltype(sc)::value>(x);
-            });
-            break;
-        }
-        case 5: r = gl_fold(x, (u32)y); break;
-        case 6: r = gl_sub_weak(x, y); break;
-        case 7: r = add_w(x, y); break;
-        case 8: {  // gl_mul2: both products (x y and y x) must equal; the first is returned
-            u64 p = x, q = y;
-            gl_mul2(p, y, q, x);
-            r = p == q ? p : ~0ULL;
-            break;
-        }
-        default: break;
-    }
-    out[i] = r;
-}
-// ops 9..12: one thread per pair x = (a[2i], a[2i+1]), y = (b[2i], b[2i+1]) -> out[2i], out[2i+1]
-__global__ void field_pair_op_kernel(int op, const u64* a, const u64* b, u64* out, u64 pairs) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= pairs) return;
-    const E2 x{a[2 * i], a[2 * i + 1]}, y{b[2 * i], b[2 * i + 1]};
-    E2 r{0, 0};
-    switch (op) {
-        case 9: {  // one gl_mul2 on two unrelated products
-            r = x;
-            gl_mul2(r.a, y.a, r.b, y.b);
-            break;
-        }
-        case 10: r = e2_mul(x, y); break;
-        case 11: r = e2_mulb(x, y.a); break;
-        case 12: r = e2_inv(x); break;
-        default: break;
-    }
-    out[2 * i] = r.a;
-    out[2 * i + 1] = r.b;
-}
-void launch_field_op(int op, const u64* a, const u64* b, u64* out, u64 count, hipStream_t s) {
-    if (op >= 9) {  // count is even (checked by the caller)
-        const u64 pairs = count / 2;
-        hipLaunchKernelGGL(field_pair_op_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, s, op, a, b, out,
-                           pairs);
-        return;
-    }
-    hipLaunchKernelGGL(field_op_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, op, a, b, out, count);
 }
 
 }  // namespace xfg

@@ -99,12 +99,11 @@ Tables tables_of(xfg_ctx* c) {
 // 2^FOURSTEP_MAX_LOG entries get the per-size pass tables instead (at 2^20 with the n-entry [k1][j2]
 // table of ntt_pass_a_r1024: a full 2^24-entry table for configs[4] measured slower).
 // Returns false when one is missing.
-// largest log2(n beta) with a forward four-step table
-static int fwd_table_max_log() { return FOURSTEP_MAX_LOG; }
 static bool fourstep_ready(xfg_ctx* c, int logn, int logbeta) {
     const FourStep& f = c->tables.fs;
-    if (logn + logbeta <= fwd_table_max_log() && !f.fwd[logn][logbeta]) return false;
-    if (logn + logbeta > fwd_table_max_log() && logn <= PASS_MAX_LOG && !f.pass_fwd[logn][logbeta]) return false;
+    const TableKind k = table_kind(logn, logbeta);
+    if (k == TableKind::fourstep && !f.fwd[logn][logbeta]) return false;
+    if (k == TableKind::pass_only && !f.pass_fwd[logn][logbeta]) return false;
     for (int l = 3; l <= std::min(logn + 1, FOURSTEP_MAX_LOG); l++)
         if (!f.inv[l]) return false;
     return true;
@@ -121,8 +120,9 @@ void ensure_fourstep(xfg_ctx* c, int logn, int logbeta) {
         return (const u64*)b.p;
     };
     FourStep& f = c->tables.fs;
-    if (logn + logbeta <= fwd_table_max_log() && !f.fwd[logn][logbeta]) f.fwd[logn][logbeta] = build(logn, logbeta);
-    if (logn + logbeta > fwd_table_max_log() && logn <= PASS_MAX_LOG && !f.pass_fwd[logn][logbeta]) {
+    const TableKind k = table_kind(logn, logbeta);
+    if (k == TableKind::fourstep && !f.fwd[logn][logbeta]) f.fwd[logn][logbeta] = build(logn, logbeta);
+    if (k == TableKind::pass_only && !f.pass_fwd[logn][logbeta]) {
         DBuf<u64>& b = c->tables.pass_buf[logn * 8 + logbeta];
         b.ensure(pass_tables_size(logn, logbeta));
         build_pass_tables(b.p, logn, logbeta, T, 0);
@@ -838,6 +838,26 @@ int xfg_burn_air_consts(const xfg_burn_inputs* in, xfg_air_consts* out) {
     return XFG_OK;
 }
 
+// options the prover takes, and a kernel for every NTT the proof will run: the forward LDE of size n
+// and the inverse NTTs of the trace (n), the composition (2n) and the FRI remainder (D[nl])
+static int check_request(xfg_ctx* c, u64 n, const Opts& o) {
+    if (const char* m = check_options(n, o)) {
+        c->err = std::string("Prover error: ") + m;
+        return XFG_PROVER_ERROR;
+    }
+    const ProofShape sh(n, o);
+    const u64 rem = sh.nl > 0 ? sh.D[sh.nl] : 0;  // size the FRI remainder is interpolated at
+    const char* what = nullptr;
+    u64 size = 0;
+    if (!ntt_supported(sh.logn, sh.logbeta, false) || !ntt_supported(sh.logn, 0, true)) what = "", size = n;
+    else if (!ntt_supported(sh.logn + 1, 0, true)) what = "", size = 2 * n;
+    else if (sh.nl > 0 && !ntt_supported((int)ilog2(rem), 0, true)) what = " (the FRI remainder)", size = rem;
+    if (!what) return XFG_OK;
+    c->err = "Prover error: these options need an NTT of size " + std::to_string(size) + what +
+             ", which this prover has no kernel for";
+    return XFG_PROVER_ERROR;
+}
+
 int xfg_prove_trace(xfg_ctx* c, const uint64_t* trace, uint32_t width, uint64_t n, const xfg_air_consts* air,
                     const xfg_options* opts, uint8_t* out, size_t* out_len) {
     if (!c) return XFG_INVALID_ARGUMENT;
@@ -851,10 +871,7 @@ int xfg_prove_trace(xfg_ctx* c, const uint64_t* trace, uint32_t width, uint64_t 
         return XFG_INVALID_ARGUMENT;
     }
     Opts o = to_opts(opts);
-    if (const char* m = check_options(n, o)) {
-        c->err = std::string("Prover error: ") + m;
-        return XFG_PROVER_ERROR;
-    }
+    if (int st = check_request(c, n, o)) return st;
     if (!all_canonical(trace, 7 * n)) {
         c->err = "trace element is not a canonical field element";
         return XFG_INVALID_ARGUMENT;
@@ -898,10 +915,7 @@ int xfg_prove_batch_submit(xfg_ctx* c, uint32_t count, const xfg_burn_inputs* in
     *ticket = 0;
     u64 n = trace_length ? trace_length : 64;
     Opts o = to_opts(opts);
-    if (const char* m = check_options(n, o)) {
-        c->err = std::string("Prover error: ") + m;
-        return XFG_PROVER_ERROR;
-    }
+    if (int st = check_request(c, n, o)) return st;
     return guarded(c, [&]() -> int {
         HIPCHK(hipSetDevice(c->device));
         std::unique_ptr<Batch> bp(new Batch());
@@ -963,10 +977,7 @@ int xfg_prepare(xfg_ctx* c, uint32_t count, uint64_t trace_length, const xfg_opt
     c->err.clear();
     u64 n = trace_length ? trace_length : 64;
     Opts o = to_opts(opts);
-    if (const char* m = check_options(n, o)) {
-        c->err = std::string("Prover error: ") + m;
-        return XFG_PROVER_ERROR;
-    }
+    if (int st = check_request(c, n, o)) return st;
     return guarded(c, [&]() -> int {
         HIPCHK(hipSetDevice(c->device));
         // two throw-away proving passes over a fixed valid statement size every lane workspace
