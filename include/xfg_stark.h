@@ -178,12 +178,26 @@ int xfg_stage_times(const xfg_ctx* ctx, double* ms, const char** names, int max)
 int xfg_bench_lde(xfg_ctx* ctx, uint32_t count, uint64_t n, uint32_t blowup, uint32_t iters, double* avg_ms);
 /* in-pipeline trace-LDE timing: HIP events around the trace LDE launch set of every proof unit
  * (on the lane stream that launches it). enabled = 1 resets and starts; enabled = 0 stops. The
- * totals so far (sum of launch-set durations, launch sets, polynomials) are returned either way. */
+ * totals so far (sum of launch-set durations, launch sets, polynomials transformed: constant columns,
+ * which skip the transform, are not counted) are returned either way. */
 int xfg_lde_probe(xfg_ctx* ctx, int enabled, double* total_ms, uint64_t* launch_sets, uint64_t* polys);
 /* kernel-level parity hooks (host buffers in/out) */
 int xfg_debug_lde(xfg_ctx* ctx, const uint64_t* coef, uint32_t npoly, uint64_t n, uint32_t blowup, uint64_t* out);
 int xfg_debug_interpolate(xfg_ctx* ctx, const uint64_t* evals, uint32_t npoly, uint64_t n, int offset7,
                           uint64_t* out);
+/* the prover's constant-column detection alone: trace [count][width][n] -> flags_out [count][width],
+ * 1 where the column holds one value in every row, else 0 */
+int xfg_debug_const_columns(xfg_ctx* ctx, const uint64_t* trace, uint32_t count, uint32_t width, uint64_t n,
+                            uint8_t* flags_out);
+/* xfg_debug_lde / xfg_debug_interpolate with a caller-supplied flag vector skip [npoly]: polynomials
+ * with a non-zero flag take no transform and are filled in as constants (coefficient / evaluation 0 of
+ * the input is the value), as the prover does for the columns it detects. The caller vouches that a
+ * flagged polynomial is constant. Both set their device output and intermediate buffers to 0xFF bytes
+ * (no field element) before they launch, so nothing an earlier call left there can pass for output. */
+int xfg_debug_lde_skip(xfg_ctx* ctx, const uint64_t* coef, uint32_t npoly, uint64_t n, uint32_t blowup,
+                       const uint8_t* skip, uint64_t* out);
+int xfg_debug_interpolate_skip(xfg_ctx* ctx, const uint64_t* evals, uint32_t npoly, uint64_t n, int offset7,
+                               const uint8_t* skip, uint64_t* out);
 /* Goldilocks primitive self test on the device: out[i] = op(a[i], b[i]) with op 0 mul, 1 add,
  * 2 sub, 3 canonical(a), 4 a * 2^(b mod 96), 5 a + (b mod 2^32) * (2^32 - 1), 6 a - b with one
  * borrow fold (the weak subtraction of the NTT butterflies), 7 a + b with one carry fold (the weak

@@ -71,6 +71,71 @@ static void launch_field_op(int op, const u64* a, const u64* b, u64* out, u64 co
     hipLaunchKernelGGL(field_op_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, op, a, b, out, count);
 }
 
+// xfg_debug_lde / xfg_debug_lde_skip: skip (host, [npoly]) or nullptr
+static int debug_lde(xfg_ctx* c, const uint64_t* coef, uint32_t npoly, uint64_t n, uint32_t blowup, const uint8_t* skip,
+                     uint64_t* out) {
+    if (!c || !coef || !out || !is_pow2(n) || !is_pow2(blowup) || n < 8 || blowup < 2 || blowup > 16)
+        return XFG_INVALID_ARGUMENT;
+    if (!ntt_supported((int)ilog2(n), (int)ilog2(blowup), false)) return XFG_INVALID_ARGUMENT;
+    return on_lane0(c, [&](Lane* L) -> int {
+        const int logn = (int)ilog2(n), logbeta = (int)ilog2(blowup);
+        const u64 N = n * blowup;
+        ensure_tables(c, logn + logbeta);
+        ensure_fourstep(c, logn, logbeta);
+        Tables T = tables_of(c);
+        L->coef.ensure((size_t)npoly * n);
+        L->scratch.ensure((size_t)npoly * N);
+        L->lde.ensure((size_t)npoly * N);
+        HIPCHK(hipMemcpy(L->coef.p, coef, (size_t)npoly * n * 8, hipMemcpyHostToDevice));
+        if (skip) {
+            L->const_col.ensure(npoly);
+            HIPCHK(hipMemcpy(L->const_col.p, skip, npoly, hipMemcpyHostToDevice));
+            // the lane's buffers keep what an earlier call left, which may be this call's answer:
+            // whatever the flagged run fails to write must show (0xFF..FF is no field element)
+            HIPCHK(hipMemsetAsync(L->scratch.p, 0xFF, (size_t)npoly * N * 8, L->stream));
+            HIPCHK(hipMemsetAsync(L->lde.p, 0xFF, (size_t)npoly * N * 8, L->stream));
+        }
+        launch_lde(L->coef.p, n, L->lde.p, L->scratch.p, npoly, logn, logbeta, T, L->stream, skip ? L->const_col.p : nullptr);
+        if (skip) launch_const_fill(L->const_col.p, L->coef.p, n, nullptr, L->lde.p, npoly, logn, logbeta, L->stream);
+        std::vector<u64> cm((size_t)npoly * N);
+        HIPCHK(hipMemcpyAsync(cm.data(), L->lde.p, cm.size() * 8, hipMemcpyDeviceToHost, L->stream));
+        HIPCHK(hipStreamSynchronize(L->stream));
+        for (u64 p = 0; p < npoly; p++)  // coset-major -> natural order
+            for (u64 t = 0; t < blowup; t++)
+                for (u64 m = 0; m < n; m++) out[p * N + t + blowup * m] = cm[(p * blowup + t) * n + m];
+        return XFG_OK;
+    });
+}
+
+// xfg_debug_interpolate / xfg_debug_interpolate_skip
+static int debug_interpolate(xfg_ctx* c, const uint64_t* evals, uint32_t npoly, uint64_t n, int offset7,
+                             const uint8_t* skip, uint64_t* out) {
+    if (!c || !evals || !out || !is_pow2(n) || n < 8 || !ntt_supported((int)ilog2(n), 0, true)) return XFG_INVALID_ARGUMENT;
+    return on_lane0(c, [&](Lane* L) -> int {
+        const int logn = (int)ilog2(n);
+        ensure_tables(c, std::max(logn, c->tables.LM));
+        if (logn >= 4) ensure_fourstep(c, logn - 1, 1);  // inverse tables up to size n
+        Tables T = tables_of(c);
+        L->trace.ensure((size_t)npoly * n);
+        L->coef.ensure((size_t)npoly * n);
+        L->scratch.ensure((size_t)npoly * n);
+        HIPCHK(hipMemcpy(L->trace.p, evals, (size_t)npoly * n * 8, hipMemcpyHostToDevice));
+        if (skip) {
+            L->const_col.ensure(npoly);
+            HIPCHK(hipMemcpy(L->const_col.p, skip, npoly, hipMemcpyHostToDevice));
+            // as in debug_lde: nothing of an earlier call's answer stays in the buffers
+            HIPCHK(hipMemsetAsync(L->scratch.p, 0xFF, (size_t)npoly * n * 8, L->stream));
+            HIPCHK(hipMemsetAsync(L->coef.p, 0xFF, (size_t)npoly * n * 8, L->stream));
+        }
+        launch_interpolate(L->trace.p, n, L->coef.p, n, L->scratch.p, npoly, logn, offset7 != 0, n, T, L->stream,
+                           skip ? L->const_col.p : nullptr);
+        if (skip) launch_const_fill(L->const_col.p, L->trace.p, n, L->coef.p, nullptr, npoly, logn, 0, L->stream);
+        HIPCHK(hipMemcpyAsync(out, L->coef.p, (size_t)npoly * n * 8, hipMemcpyDeviceToHost, L->stream));
+        HIPCHK(hipStreamSynchronize(L->stream));
+        return XFG_OK;
+    });
+}
+
 extern "C" {
 
 int xfg_bench_lde(xfg_ctx* c, uint32_t count, uint64_t n, uint32_t blowup, uint32_t iters, double* avg_ms) {
@@ -131,43 +196,35 @@ int xfg_lde_probe(xfg_ctx* c, int enabled, double* total_ms, uint64_t* launch_se
 }
 
 int xfg_debug_lde(xfg_ctx* c, const uint64_t* coef, uint32_t npoly, uint64_t n, uint32_t blowup, uint64_t* out) {
-    if (!c || !coef || !out || !is_pow2(n) || !is_pow2(blowup) || n < 8 || blowup < 2 || blowup > 16)
-        return XFG_INVALID_ARGUMENT;
-    if (!ntt_supported((int)ilog2(n), (int)ilog2(blowup), false)) return XFG_INVALID_ARGUMENT;
-    return on_lane0(c, [&](Lane* L) -> int {
-        const int logn = (int)ilog2(n), logbeta = (int)ilog2(blowup);
-        const u64 N = n * blowup;
-        ensure_tables(c, logn + logbeta);
-        ensure_fourstep(c, logn, logbeta);
-        Tables T = tables_of(c);
-        L->coef.ensure((size_t)npoly * n);
-        L->scratch.ensure((size_t)npoly * N);
-        L->lde.ensure((size_t)npoly * N);
-        HIPCHK(hipMemcpy(L->coef.p, coef, (size_t)npoly * n * 8, hipMemcpyHostToDevice));
-        launch_lde(L->coef.p, n, L->lde.p, L->scratch.p, npoly, logn, logbeta, T, L->stream);
-        std::vector<u64> cm((size_t)npoly * N);
-        HIPCHK(hipMemcpyAsync(cm.data(), L->lde.p, cm.size() * 8, hipMemcpyDeviceToHost, L->stream));
-        HIPCHK(hipStreamSynchronize(L->stream));
-        for (u64 p = 0; p < npoly; p++)  // coset-major -> natural order
-            for (u64 t = 0; t < blowup; t++)
-                for (u64 m = 0; m < n; m++) out[p * N + t + blowup * m] = cm[(p * blowup + t) * n + m];
-        return XFG_OK;
-    });
+    return debug_lde(c, coef, npoly, n, blowup, nullptr, out);
+}
+int xfg_debug_lde_skip(xfg_ctx* c, const uint64_t* coef, uint32_t npoly, uint64_t n, uint32_t blowup,
+                       const uint8_t* skip, uint64_t* out) {
+    if (!skip) return XFG_INVALID_ARGUMENT;
+    return debug_lde(c, coef, npoly, n, blowup, skip, out);
 }
 
 int xfg_debug_interpolate(xfg_ctx* c, const uint64_t* evals, uint32_t npoly, uint64_t n, int offset7, uint64_t* out) {
-    if (!c || !evals || !out || !is_pow2(n) || n < 8 || !ntt_supported((int)ilog2(n), 0, true)) return XFG_INVALID_ARGUMENT;
+    return debug_interpolate(c, evals, npoly, n, offset7, nullptr, out);
+}
+int xfg_debug_interpolate_skip(xfg_ctx* c, const uint64_t* evals, uint32_t npoly, uint64_t n, int offset7,
+                               const uint8_t* skip, uint64_t* out) {
+    if (!skip) return XFG_INVALID_ARGUMENT;
+    return debug_interpolate(c, evals, npoly, n, offset7, skip, out);
+}
+
+int xfg_debug_const_columns(xfg_ctx* c, const uint64_t* trace, uint32_t count, uint32_t width, uint64_t n,
+                            uint8_t* flags_out) {
+    if (!c || !trace || !flags_out || count == 0 || width == 0 || !is_pow2(n) || n < 8 ||
+        (uint64_t)count * width > 0xFFFF)  // one grid row per column
+        return XFG_INVALID_ARGUMENT;
     return on_lane0(c, [&](Lane* L) -> int {
-        const int logn = (int)ilog2(n);
-        ensure_tables(c, std::max(logn, c->tables.LM));
-        if (logn >= 4) ensure_fourstep(c, logn - 1, 1);  // inverse tables up to size n
-        Tables T = tables_of(c);
-        L->trace.ensure((size_t)npoly * n);
-        L->coef.ensure((size_t)npoly * n);
-        L->scratch.ensure((size_t)npoly * n);
-        HIPCHK(hipMemcpy(L->trace.p, evals, (size_t)npoly * n * 8, hipMemcpyHostToDevice));
-        launch_interpolate(L->trace.p, n, L->coef.p, n, L->scratch.p, npoly, logn, offset7 != 0, n, T, L->stream);
-        HIPCHK(hipMemcpyAsync(out, L->coef.p, (size_t)npoly * n * 8, hipMemcpyDeviceToHost, L->stream));
+        const size_t cols = (size_t)count * width;
+        L->trace.ensure(cols * n);
+        L->const_col.ensure(cols);
+        HIPCHK(hipMemcpy(L->trace.p, trace, cols * n * 8, hipMemcpyHostToDevice));
+        launch_const_detect(L->trace.p, (int)cols, (int)ilog2(n), L->const_col.p, L->stream);
+        HIPCHK(hipMemcpyAsync(flags_out, L->const_col.p, cols, hipMemcpyDeviceToHost, L->stream));
         HIPCHK(hipStreamSynchronize(L->stream));
         return XFG_OK;
     });

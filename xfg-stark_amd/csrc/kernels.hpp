@@ -51,15 +51,25 @@ struct Tables {
 
 // ---- NTT (four-step, natural order in/out) ----
 // forward LDE: coef[poly][n] -> out[poly][beta][n] (coset-major: out[p][t][m] = P(7 w_N^(t + beta m)))
+// skip [npoly] (device, or nullptr): polynomials with a non-zero byte are not transformed and their
+// planes of out are left untouched (launch_const_fill writes them)
 void launch_lde(const u64* coef, u64 coef_stride, u64* out, u64* scratch, int npoly, int logn, int logbeta,
-                const Tables& T, hipStream_t s);
+                const Tables& T, hipStream_t s, const unsigned char* skip = nullptr);
 // generator of the four-step table for (logn, logbeta) (inverse: logbeta = -1; fourstep_size entries)
 void build_fourstep(u64* out, int logn, int logbeta, const Tables& T, hipStream_t s);
 // the pass tables alone (forward, for sizes without a four-step table; pass_tables_size entries)
 void build_pass_tables(u64* out, int logn, int logbeta, const Tables& T, hipStream_t s);
 // inverse: evals[poly][n] at 7^off7 * w_n^i -> coefficients (first `keep` written, stride out_stride)
 void launch_interpolate(const u64* evals, u64 in_stride, u64* out, u64 out_stride, u64* scratch, int npoly, int logn,
-                        bool off7, u64 keep, const Tables& T, hipStream_t s);
+                        bool off7, u64 keep, const Tables& T, hipStream_t s, const unsigned char* skip = nullptr);
+// constant columns: flags[col] = 1 where cols[col][0..n) holds one value in every row, else 0
+// (flags: ncols bytes; detection blocks cover CONST_DETECT_SPAN rows each)
+constexpr int CONST_DETECT_SPAN = 1024, CONST_FILL_SPAN = 4096;
+void launch_const_detect(const u64* cols, int ncols, int logn, unsigned char* flags, hipStream_t s);
+// what the NTTs would have produced for the flagged columns, v = src[col * src_stride]:
+// coef[col] = (v, 0, ..., 0) and lde[col][t][m] = v (coset-major planes); coef or lde may be nullptr
+void launch_const_fill(const unsigned char* flags, const u64* src, u64 src_stride, u64* coef, u64* lde, int ncols,
+                       int logn, int logbeta, hipStream_t s);
 
 // ---- device-side Fiat-Shamir (winter-crypto DefaultRandomCoin<Blake3_256>, as host_common.hpp Coin).
 // Each transcript step runs in the kernel that produces its input, one proof per block; the host

@@ -292,8 +292,13 @@ struct NttArgs {
                     // of a tile consecutive (xcd_block_coset)
     int tq_b;       // forward: pass B applies the four-step twiddles as it loads (ntt_pass_a_cos)
     int preg;       // forward pass A: coset pre-factors read from the pass tables in L2, not LDS
+    const unsigned char* skip;  // [poly]: non-zero -> the polynomial is not transformed (its blocks return
+                                // at once; launch_const_fill writes its outputs); nullptr: transform all
     Tables T;
     __device__ PassTableLayout tab() const { return {logR, logC, logbeta}; }
+    // wave-uniform (poly comes from the block index); tested before a block's first barrier and after
+    // the renumbering that yields poly
+    __device__ bool skipped(int poly) const { return skip && skip[poly]; }
 };
 
 // Workgroups are dealt round-robin over the 8 XCDs, each with its own L2. When a pass writes less
@@ -350,6 +355,7 @@ __global__ __launch_bounds__(1 << LOGT, (1 << (10 - LOGT)) >> (LOGE - 4)) void n
     else xcd_block(a.xcd & 1, bx, by);
     const int pt = by, col0 = bx * TC;
     const int poly = INV ? pt : (pt >> a.logbeta), t = INV ? 0 : (pt & ((1 << a.logbeta) - 1));
+    if (a.skipped(poly)) return;
     const u64 n = 1ULL << a.logn;
     const int logN = a.logn + a.logbeta;
     const u64 maskN = (1ULL << logN) - 1;
@@ -454,6 +460,7 @@ __global__ __launch_bounds__(256, 3) void ntt_pass_a_cos(NttArgs a) {
     u64* ltw = lds + L.tw;
     u64* pre = lds + L.pre;
     const int poly = blockIdx.y, col0 = blockIdx.x * TC;
+    if (a.skipped(poly)) return;
     const u64 n = 1ULL << a.logn;
     const int beta = 1 << a.logbeta;
     const u64* pt4 = a.pt;
@@ -523,6 +530,7 @@ __global__ __launch_bounds__(256, 4) void ntt_pass_a_cos2(NttArgs a) {
     u64* tile = lds;
     u64* comb = lds + lds_pass_a(LOGR, LOGT, LOGE, a.logC, false).tw;  // [r][k] second-step twiddles of the current coset
     const int poly = blockIdx.y, col0 = blockIdx.x * TC;
+    if (a.skipped(poly)) return;
     const u64 n = 1ULL << a.logn;
     const int beta = 1 << a.logbeta, M = beta >> 2, KP = beta / M;
     const PassTableLayout TL{LOGR, a.logC, a.logbeta};
@@ -591,6 +599,7 @@ __global__ __launch_bounds__(256, 3) void ntt_pass_a_r1024(NttArgs a) {
     int bx, by;
     xcd_block_coset(a.logbeta, bx, by);
     const int pt = by, col0 = bx * TC, poly = pt >> a.logbeta, t = pt & ((1 << a.logbeta) - 1);
+    if (a.skipped(poly)) return;
     const u64 n = 1ULL << a.logn;
     const PassTableLayout TL{LOGR, a.logC, a.logbeta};
     const u64* pre = a.pt + TL.pre((u64)t);            // g_t^j1
@@ -636,6 +645,7 @@ __global__ __launch_bounds__(256, 3) void ntt_pass_b_r1024(NttArgs a) {
     int bx, by;
     xcd_block(true, bx, by);
     const int pt = by, k10 = bx * TR;
+    if (a.skipped(pt >> a.logbeta)) return;
     const u64 n = 1ULL << a.logn;
     for (int i = threadIdx.x; i < C; i += NT) ltw[i] = a.pt[a.tab().wC() + i];
     // this thread's first-step group (stockham, SEQ_FAST): row seq0 of the tile, columns j0 + 32 r
@@ -667,6 +677,7 @@ __global__ __launch_bounds__(1 << LOGT) void ntt_pass_b(NttArgs a) {
     int bx, by;
     xcd_block(a.xcd & 2, bx, by);
     const int pt = by, k10 = bx * TR;
+    if (a.skipped(INV ? pt : (pt >> a.logbeta))) return;
     const u64 n = 1ULL << a.logn;
     if (a.pt) {
         const u64* pt4 = a.pt + a.tab().wC();
@@ -747,6 +758,7 @@ __global__ __launch_bounds__(1 << LOGT) void ntt_pass_b_tq(NttArgs a) {
     int bx, by;
     xcd_block(a.xcd & 2, bx, by);
     const int pt = by, k10 = bx * TR;
+    if (a.skipped(pt >> a.logbeta)) return;
     const u64 n = 1ULL << a.logn;
     {
         // the second step's twiddles as an [r][k] table (w_C^(r k), r, k < 16): each read is a fixed
@@ -807,19 +819,28 @@ __global__ __launch_bounds__(1 << LOGT, MINW) void ntt_pass_b_pers(NttArgs a, in
     const int per_x = gridDim.x >> 3, x = blockIdx.x & 7, slot = blockIdx.x >> 3;
     const int span = (ntiles + 7) >> 3, tend = min((x + 1) * span, ntiles);
     const int seq0 = threadIdx.x / G1, j0 = threadIdx.x % G1;
-    auto load = [&](int ti, u64* dst) {
+    // a tile's flag is read once, with its loads, and travels with them (block-uniform)
+    auto load = [&](int ti, u64* dst) -> bool {
         const int pt = ti / ntx, k10 = (ti - pt * ntx) * TR;
+        if (a.skipped(pt >> a.logbeta)) return true;  // pass A left nothing to read
         const u64* y = a.y + (u64)pt * n + ((u64)(k10 + seq0) << LOGC) + j0;
 #pragma unroll
         for (int r = 0; r < R1; r++) dst[r] = y[r * G1];
+        return false;
     };
     int ti = x * span + slot;
-    u64 yv[R1];
-    if (ti < tend) load(ti, yv);
+    u64 yv[R1] = {};
+    bool skip_cur = ti < tend && load(ti, yv);
     for (; ti < tend; ti += per_x) {
         const int pt = ti / ntx, k10 = (ti - pt * ntx) * TR;
-        u64 nx[R1];
-        if (ti + per_x < tend) load(ti + per_x, nx);
+        u64 nx[R1] = {};
+        const bool skip_nx = ti + per_x < tend && load(ti + per_x, nx);
+        if (skip_cur) {  // the whole block moves on to its next tile
+#pragma unroll
+            for (int r = 0; r < R1; r++) yv[r] = nx[r];
+            skip_cur = skip_nx;
+            continue;
+        }
         auto ldg = [&](int, int, int o) -> u64 { return yv[o / G1]; };
         u64* out = a.out + (u64)pt * n + k10;
         auto stg = [&](int, int seq, int base, int stride, u64* v) {
@@ -831,6 +852,7 @@ __global__ __launch_bounds__(1 << LOGT, MINW) void ntt_pass_b_pers(NttArgs a, in
         pass_dft<LOGC, LOGE, false, false, NT>(tile, logTR, ltw, ldg, stg, [](int, int, int, int) {});
 #pragma unroll
         for (int r = 0; r < R1; r++) yv[r] = nx[r];
+        skip_cur = skip_nx;
     }
 }
 
@@ -948,10 +970,73 @@ static void ntt_run(NttArgs& a, int npoly, bool inv, hipStream_t s) {
     ntt_launch(p.b, args, s);
 }
 
+// ---------------------------------------------------------------- constant columns
+// A column that holds one value v in every row interpolates to the constant v, and its LDE is v at
+// every point: such columns take no NTT. const_detect_kernel finds them in whatever trace arrives,
+// the NTT kernels return at once for them (NttArgs::skip), const_fill_kernel writes their outputs.
+__global__ void const_flags_init_kernel(unsigned char* flags, int count) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) flags[i] = 1;
+}
+// flags[col] (preset to 1) -> 0 where some element of cols[col][0..n) differs from element 0. One block
+// per CONST_DETECT_SPAN rows of a column (min(256, n) threads, coalesced strides); a thread that saw
+// a difference stores 0 -- every writer stores the same byte, so no atomics
+__global__ __launch_bounds__(256) void const_detect_kernel(const u64* cols, u64 n, unsigned char* flags) {
+    const int col = blockIdx.y;
+    const u64* c = cols + (u64)col * n;
+    const u64 first = c[0];
+    const u64 i0 = (u64)blockIdx.x * CONST_DETECT_SPAN, i1 = i0 + CONST_DETECT_SPAN < n ? i0 + CONST_DETECT_SPAN : n;
+    u64 diff = 0;
+    for (u64 i = i0 + threadIdx.x; i < i1; i += blockDim.x) diff |= c[i] ^ first;
+    if (diff) flags[col] = 0;
+}
+void launch_const_detect(const u64* cols, int ncols, int logn, unsigned char* flags, hipStream_t s) {
+    const u64 n = 1ULL << logn;
+    hipLaunchKernelGGL(const_flags_init_kernel, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, s, flags, ncols);
+    hipLaunchKernelGGL(const_detect_kernel, dim3((unsigned)((n + CONST_DETECT_SPAN - 1) / CONST_DETECT_SPAN), ncols),
+                       dim3((unsigned)std::min<u64>(256, n)), 0, s, cols, n, flags);
+}
+// outputs of the flagged columns, v = src[col * src_stride]: coef[col] = (v, 0, ..., 0) (n entries) and
+// lde[col][t][m] = v (N = beta n entries, the coset-major plane is simply full of v); either may be null.
+// Block x of a column writes entries [x, x + 1) * CONST_FILL_SPAN of the LDE plane and the same
+// fraction of the coefficients, in 16-byte stores (n and N are even, planes 16-byte aligned); blocks of
+// unflagged columns exit
+__global__ __launch_bounds__(256) void const_fill_kernel(const unsigned char* flags, const u64* src, u64 src_stride,
+                                                         u64* coef, u64* lde, u64 n, int logbeta) {
+    const int col = blockIdx.y;
+    if (!flags[col]) return;
+    const u64 v = src[(u64)col * src_stride];
+    const u64 i0 = (u64)blockIdx.x * CONST_FILL_SPAN;
+    if (lde) {
+        const u64 N = n << logbeta, i1 = i0 + CONST_FILL_SPAN < N ? i0 + CONST_FILL_SPAN : N;
+        u64* o = lde + (u64)col * N;
+        const u64x2 d = {v, v};
+        for (u64 i = i0 + 2 * threadIdx.x; i < i1; i += 2 * blockDim.x) *reinterpret_cast<u64x2*>(o + i) = d;
+    }
+    if (coef) {
+        // the block's share of the n coefficients (at least two per block: beta <= CONST_FILL_SPAN / 2)
+        const u64 span = lde ? (u64)CONST_FILL_SPAN >> logbeta : (u64)CONST_FILL_SPAN;
+        const u64 c0 = (u64)blockIdx.x * span, c1 = c0 + span < n ? c0 + span : n;
+        u64* o = coef + (u64)col * n;
+        for (u64 i = c0 + 2 * threadIdx.x; i < c1; i += 2 * blockDim.x) {
+            const u64x2 d = {i == 0 ? v : 0, 0};
+            *reinterpret_cast<u64x2*>(o + i) = d;
+        }
+    }
+}
+void launch_const_fill(const unsigned char* flags, const u64* src, u64 src_stride, u64* coef, u64* lde, int ncols,
+                       int logn, int logbeta, hipStream_t s) {
+    if (!coef && !lde) return;
+    const u64 n = 1ULL << logn, span = lde ? n << logbeta : n;
+    hipLaunchKernelGGL(const_fill_kernel, dim3((unsigned)((span + CONST_FILL_SPAN - 1) / CONST_FILL_SPAN), ncols),
+                       dim3(256), 0, s, flags, src, src_stride, coef, lde, n, lde ? logbeta : 0);
+}
+
 void launch_lde(const u64* coef, u64 coef_stride, u64* out, u64* scratch, int npoly, int logn, int logbeta,
-                const Tables& T, hipStream_t s) {
+                const Tables& T, hipStream_t s, const unsigned char* skip) {
     NttArgs a{coef, scratch, out, coef_stride, 0, logn};  // in, y, out, in_stride, out_stride, logn
     a.logbeta = logbeta;
+    a.skip = skip;
     a.T = T;
     const TableKind k = T.fs ? table_kind(logn, logbeta) : TableKind::none;
     a.t4 = k == TableKind::fourstep ? T.fs->fwd[logn][logbeta] : nullptr;
@@ -960,8 +1045,9 @@ void launch_lde(const u64* coef, u64 coef_stride, u64* out, u64* scratch, int np
 }
 
 void launch_interpolate(const u64* evals, u64 in_stride, u64* out, u64 out_stride, u64* scratch, int npoly, int logn,
-                        bool off7, u64 keep, const Tables& T, hipStream_t s) {
+                        bool off7, u64 keep, const Tables& T, hipStream_t s, const unsigned char* skip) {
     NttArgs a{evals, scratch, out, in_stride, out_stride, logn};  // in, y, out, in_stride, out_stride, logn
+    a.skip = skip;
     a.off7 = off7 ? 1 : 0;
     a.keep = keep;
     a.T = T;

@@ -158,6 +158,7 @@ void size_trace_lde(Lane* c, size_t B, const ProofShape& sh) {
     c->coef.ensure(B * 7 * sh.n);
     c->scratch.ensure(B * 7 * sh.N);
     c->lde.ensure(B * 7 * sh.N);
+    c->const_col.ensure((B * 7 + 3) & ~(size_t)3);
 }
 void size_constraint_eval(Lane* c, size_t B, const ProofShape& sh) {
     c->air.ensure(B);
@@ -257,7 +258,9 @@ static void upload_unit_inputs(Lane* c, ProofJob* jobs, int B, const ProofShape&
 
 void launch_trace_lde(Lane* c, const Tables& T, int B, const ProofShape& sh, bool probe) {
     hipStream_t s = c->stream;
-    launch_interpolate(c->trace.p, sh.n, c->coef.p, sh.n, c->scratch.p, B * 7, sh.logn, false, sh.n, T, s);
+    const unsigned char* skip = c->const_col.p;
+    launch_const_detect(c->trace.p, B * 7, sh.logn, c->const_col.p, s);
+    launch_interpolate(c->trace.p, sh.n, c->coef.p, sh.n, c->scratch.p, B * 7, sh.logn, false, sh.n, T, s, skip);
     if (probe) {
         if (!c->lde_ev[0]) {
             HIPCHK(hipEventCreate(&c->lde_ev[0]));
@@ -265,8 +268,11 @@ void launch_trace_lde(Lane* c, const Tables& T, int B, const ProofShape& sh, boo
         }
         HIPCHK(hipEventRecord(c->lde_ev[0], s));
     }
-    launch_lde(c->coef.p, sh.n, c->lde.p, c->scratch.p, B * 7, sh.logn, sh.logbeta, T, s);
+    launch_lde(c->coef.p, sh.n, c->lde.p, c->scratch.p, B * 7, sh.logn, sh.logbeta, T, s, skip);
     if (probe) HIPCHK(hipEventRecord(c->lde_ev[1], s));
+    // the constant columns' coefficients and LDE planes (outside the probe's window: it times the
+    // transforms of the polynomials it counts)
+    launch_const_fill(skip, c->trace.p, sh.n, c->coef.p, c->lde.p, B * 7, sh.logn, sh.logbeta, s);
 }
 
 // FRI layers (FriProver::build_layers), folding factor 8: commit -> reseed -> draw alpha -> fold,
@@ -329,6 +335,7 @@ static ReplayView pack_replay_block(Lane* c, size_t B, const ProofShape& sh) {
     const u64 o_fail = seg(c->dfail.p, B * sizeof(int));
     const u64 o_rem = seg(c->rem.p, B * DE * sh.rem_len * 8);
     const u64 o_dn2 = seg(c->dn2.p, B * DE * 8);
+    const u64 o_const = seg(c->const_col.p, (B * 7 + 3) & ~(size_t)3);  // whole words; B * 7 flags
     unsigned char* hx = c->h_xfer.ensure(words * 4);
     void* hx_dev = nullptr;
     HIPCHK(hipHostGetDevicePointer(&hx_dev, hx, 0));
@@ -342,6 +349,7 @@ static ReplayView pack_replay_block(Lane* c, size_t B, const ProofShape& sh) {
     rv.ffail = (const int*)(hx + o_fail);
     rv.remh = (const u64*)(hx + o_rem);
     rv.dn2h = (const u64*)(hx + o_dn2);
+    c->h_const_col = hx + o_const;
     return rv;
 }
 
@@ -488,6 +496,9 @@ static void prove_lane(Lane* c, const Tables& T, const u64* ce_div, ProofJob* jo
     const ReplayView rv = enqueue_commit_chain(c, T, ce_div, jobs, B, trace_host, sh, o, g, ht);
     HIPCHK(hipStreamSynchronize(c->stream));
     ht.mark("sync_rem");
+    // trace columns that went through the NTTs (the rest were constant: detected, filled in)
+    u64 live_cols = 0;
+    for (int k = 0; k < B * 7; k++) live_cols += c->h_const_col[k] ? 0 : 1;
     pool.parallel_for(B, [jobs, B, &sh, g, &rv](int b) { replay_transcript(jobs[b], b, B, sh, g, rv); });
 
     const auto t_q0 = clk::now();
@@ -511,14 +522,14 @@ static void prove_lane(Lane* c, const Tables& T, const u64* ce_div, ProofJob* jo
         serialize_proof(jobs[b], b, B, sh, o, lay[b], ix, got.gv, got.gd);
     });
     ht.mark("serialize");
-    ht.dump(B);
+    ht.dump(B, (long)((u64)B * 7 - live_cols));
     if (c->lde_probe) {  // the stream has passed both events (root / query fetches synchronised it)
         float ms = 0;
         HIPCHK(hipEventSynchronize(c->lde_ev[1]));
         HIPCHK(hipEventElapsedTime(&ms, c->lde_ev[0], c->lde_ev[1]));
         c->lde_ms += ms;
         c->lde_sets++;
-        c->lde_polys += (u64)B * 7;
+        c->lde_polys += live_cols;
     }
     if (c->timing) {
         for (int k = 0; k < 9; k++) {

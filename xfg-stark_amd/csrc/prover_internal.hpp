@@ -56,6 +56,11 @@ struct Lane {
     DBuf<DeepParams> dp;
     DBuf<DevCoin> dcoin;  // device-side transcript
     DBuf<int> dfail;
+    // [B][7] (padded to whole 32-bit words): 1 where a trace column holds one value in every row
+    // (launch_const_detect); such columns skip the interpolation and the LDE. h_const_col: the unit's
+    // flags in the replay block, for the counters
+    DBuf<unsigned char> const_col;
+    const unsigned char* h_const_col = nullptr;
     std::vector<DBuf<u64>> flayer;
     std::vector<DBuf<Digest>> fnodes;
     // pinned host staging
@@ -109,9 +114,11 @@ struct HostTrace {
     void mark(const char* what) {
         if (trace_on()) m.push_back({what, std::chrono::steady_clock::now()});
     }
-    void dump(int B) {
+    // const_cols: trace columns found constant and not transformed (-1: not a proving batch)
+    void dump(int B, long const_cols = -1) {
         if (!trace_on() || m.size() < 2) return;
         std::string line = "[xfg] B=" + std::to_string(B);
+        if (const_cols >= 0) line += " const_cols=" + std::to_string(const_cols);
         for (size_t i = 1; i < m.size(); i++) {
             char buf[96];
             snprintf(buf, sizeof buf, " %s=%.2f", m[i].first,
@@ -174,7 +181,9 @@ bool busy(xfg_ctx* c);
 void size_trace_lde(Lane* c, size_t B, const ProofShape& sh);        // trace, coef, scratch, lde
 void size_constraint_eval(Lane* c, size_t B, const ProofShape& sh);  // air, coeffs, ce
 void size_ood_deep(Lane* c, size_t B, const ProofShape& sh);  // hcoef, zpts, partial, ood, dp, carry, deep
-// trace -> coefficients -> LDE (DefaultTraceLde::new); probe: the xfg_lde_probe events around the LDE
+// trace -> coefficients -> LDE (DefaultTraceLde::new); probe: the xfg_lde_probe events around the LDE.
+// Constant columns are detected in the trace as it lies in c->trace (whatever put it there) and
+// filled in instead of transformed; the flags stay in c->const_col
 void launch_trace_lde(Lane* c, const Tables& T, int B, const ProofShape& sh, bool probe);
 
 // the kernels' subtractions (gl_sub) are exact for canonical operands only: host inputs are checked

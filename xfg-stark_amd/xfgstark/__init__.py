@@ -88,6 +88,10 @@ _lib.xfg_lde_probe.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POI
 _lib.xfg_debug_lde.argtypes = [C.c_void_p, _u64p, C.c_uint32, C.c_uint64, C.c_uint32, _u64p]
 _lib.xfg_debug_ood_deep.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p]
 _lib.xfg_debug_interpolate.argtypes = [C.c_void_p, _u64p, C.c_uint32, C.c_uint64, C.c_int, _u64p]
+if hasattr(_lib, "xfg_debug_const_columns"):  # absent from builds older than the constant-column skip (XFG_LIB A/B)
+    _lib.xfg_debug_const_columns.argtypes = [C.c_void_p, _u64p, C.c_uint32, C.c_uint32, C.c_uint64, _u8p]
+    _lib.xfg_debug_lde_skip.argtypes = [C.c_void_p, _u64p, C.c_uint32, C.c_uint64, C.c_uint32, _u8p, _u64p]
+    _lib.xfg_debug_interpolate_skip.argtypes = [C.c_void_p, _u64p, C.c_uint32, C.c_uint64, C.c_int, _u8p, _u64p]
 if hasattr(_lib, "xfg_debug_constraint_eval"):  # absent from builds older than the kernel-level parity hooks
     _lib.xfg_debug_constraint_eval.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _u64p,
                                                C.POINTER(_AirConsts), _u64p, _u64p]
@@ -683,6 +687,32 @@ class XfgBurnMintProver:
             raise self._err(st)
         return out
 
+    def debug_lde_skip(self, coef, n, blowup, skip):
+        """debug_lde with a flag per polynomial: flagged ones (vouched constant by the caller) take no
+        transform and are filled in, as the prover does for the constant columns it detects"""
+        import numpy as np
+        c = np.ascontiguousarray(np.asarray(coef, dtype=np.uint64)).reshape(-1, n)
+        f = np.ascontiguousarray(np.asarray(skip, dtype=np.uint8))
+        if f.shape != (c.shape[0],):
+            raise XfgStarkError(9, "debug_lde_skip: one flag per polynomial")
+        out = np.zeros((c.shape[0], n * blowup), dtype=np.uint64)
+        st = _lib.xfg_debug_lde_skip(self._ctx, c.ctypes.data_as(_u64p), c.shape[0], n, blowup, f.ctypes.data_as(_u8p),
+                                     out.ctypes.data_as(_u64p))
+        if st:
+            raise self._err(st)
+        return out
+
+    def debug_const_columns(self, trace):
+        """the prover's constant-column detection: trace [B,width,n] -> flags [B,width] (1 = one value in every row)"""
+        import numpy as np
+        tr = np.ascontiguousarray(trace, dtype=np.uint64)
+        B, width, n = tr.shape
+        out = np.zeros((B, width), dtype=np.uint8)
+        st = _lib.xfg_debug_const_columns(self._ctx, tr.ctypes.data_as(_u64p), B, width, n, out.ctypes.data_as(_u8p))
+        if st:
+            raise self._err(st)
+        return out
+
     def debug_ood_deep(self, coef, hcoef, zpts, coeffs):
         """OOD + DEEP kernels: coef [B,7,n], hcoef [B,n], zpts [B,2], coeffs [B,8] -> (ood [B,15], deep [B,n])"""
         import numpy as np
@@ -774,6 +804,20 @@ class XfgBurnMintProver:
         out = np.zeros_like(e)
         st = _lib.xfg_debug_interpolate(self._ctx, e.ctypes.data_as(_u64p), e.shape[0], n, 1 if offset7 else 0,
                                         out.ctypes.data_as(_u64p))
+        if st:
+            raise self._err(st)
+        return out
+
+    def debug_interpolate_skip(self, evals, n, skip, offset7=False):
+        """debug_interpolate with a flag per polynomial (see debug_lde_skip)"""
+        import numpy as np
+        e = np.ascontiguousarray(np.asarray(evals, dtype=np.uint64)).reshape(-1, n)
+        f = np.ascontiguousarray(np.asarray(skip, dtype=np.uint8))
+        if f.shape != (e.shape[0],):
+            raise XfgStarkError(9, "debug_interpolate_skip: one flag per polynomial")
+        out = np.zeros_like(e)
+        st = _lib.xfg_debug_interpolate_skip(self._ctx, e.ctypes.data_as(_u64p), e.shape[0], n, 1 if offset7 else 0,
+                                             f.ctypes.data_as(_u8p), out.ctypes.data_as(_u64p))
         if st:
             raise self._err(st)
         return out
