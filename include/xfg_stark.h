@@ -239,6 +239,21 @@ int xfg_debug_fri_fold(xfg_ctx* ctx, uint32_t count, uint32_t ext, uint32_t logn
 int xfg_debug_coin_draws(xfg_ctx* ctx, const uint32_t seed[8], uint64_t counter, uint32_t k, uint32_t ext,
                          const uint64_t reject[4], uint64_t* out_wave, uint64_t* out_seq, uint64_t counters[2],
                          int ok[2]);
+/* Merkle commitment of `count` LDEs as the prover runs it (leaf kernel, then the tree up to the root,
+ * no transcript step), every stored node copied back. lde [count][nc][blowup][n], coset-major as
+ * xfg_debug_lde's device output (row m of coset t at [t][m]); nc = 1, 2 or 7 columns, blowup 2..16,
+ * 8 <= n <= 2^24, both powers of two, count <= 65535. nodes_out [count][2n][32 bytes]: each proof's heap (slot 1 = root,
+ * slot i = H(slot 2i || slot 2i+1)); slots [1, n) are defined -- the levels below them live in
+ * registers only -- and every other slot is returned as 0xFF bytes. local_out [nentries][2 blowup][32]:
+ * the local heaps the opening kernel recomputes for rows entries[e] = proof << log2(n) | row (slot 1 =
+ * the row's node n + row of the full tree, leaf of coset t at blowup + t; slot 0 is 0xFF bytes) */
+int xfg_debug_merkle_lde(xfg_ctx* ctx, uint32_t count, uint32_t nc, uint64_t n, uint32_t blowup, const uint64_t* lde,
+                         const uint64_t* entries, uint64_t nentries, uint8_t* nodes_out, uint8_t* local_out);
+/* Merkle commitment of `count` FRI layers (leaf i = the 8 E values at natural indices i + k rows,
+ * k < 8, rows = D / 8), vals, the layout arguments and their checks as for xfg_debug_fri_fold; count <= 65535.
+ * nodes_out [count][2 rows][32 bytes]: the whole heap, slots [1, 2 rows); slot 0 is 0xFF bytes */
+int xfg_debug_merkle_fri(xfg_ctx* ctx, uint32_t count, uint32_t ext, uint32_t logn, uint32_t logbeta, int coset_major,
+                         const uint64_t* vals, uint8_t* nodes_out);
 
 #ifdef __cplusplus
 }

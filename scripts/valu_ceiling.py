@@ -52,7 +52,7 @@ def ceiling(instrs):
 
 
 def demangled_match(ledger_name, mangled):
-    # "void xfg::leaves_lde_kernel<7, 3>" -> name + template args as they appear mangled
+    # "void xfg::leaves_row_kernel<7, 3>" -> name + template args as they appear mangled
     m = re.search(r"xfg::(\w+)(<([^>]*)>)?", ledger_name)
     if not m:
         return False

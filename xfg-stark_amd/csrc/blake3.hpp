@@ -22,6 +22,8 @@ struct Digest {
 #define XFG_B3_IV5 0x9B05688Cu
 #define XFG_B3_IV6 0x1F83D9ABu
 #define XFG_B3_IV7 0x5BE0CD19u
+// all eight, as an initialiser list: the chaining value of a chunk's first block
+#define XFG_B3_IV XFG_B3_IV0, XFG_B3_IV1, XFG_B3_IV2, XFG_B3_IV3, XFG_B3_IV4, XFG_B3_IV5, XFG_B3_IV6, XFG_B3_IV7
 
 enum : uint32_t { B3_CHUNK_START = 1, B3_CHUNK_END = 2, B3_PARENT = 4, B3_ROOT = 8 };
 
@@ -172,8 +174,7 @@ __host__ __device__ __forceinline__ void b3_compress(const uint32_t cv[8], uint3
 // BLAKE3 of a single block of `len` (<= 64) bytes given as 16 LE words (zero padded)
 template <unsigned ZM = 0>
 __host__ __device__ __forceinline__ Digest b3_hash_block(uint32_t m[16], uint32_t len) {
-    const uint32_t iv[8] = {XFG_B3_IV0, XFG_B3_IV1, XFG_B3_IV2, XFG_B3_IV3,
-                            XFG_B3_IV4, XFG_B3_IV5, XFG_B3_IV6, XFG_B3_IV7};
+    const uint32_t iv[8] = {XFG_B3_IV};
     Digest d;
     b3_compress<ZM>(iv, m, len, 0, B3_CHUNK_START | B3_CHUNK_END | B3_ROOT, d.w);
     return d;
@@ -200,8 +201,7 @@ __host__ __device__ __forceinline__ Digest b3_hash_elems(const uint64_t* e) {
     if constexpr (K <= 8) {
         return b3_hash_block<0xFFFFu & ~((1u << (2 * K)) - 1u)>(m, 8 * K);  // words 2K.. are zero
     } else {
-        const uint32_t iv[8] = {XFG_B3_IV0, XFG_B3_IV1, XFG_B3_IV2, XFG_B3_IV3,
-                                XFG_B3_IV4, XFG_B3_IV5, XFG_B3_IV6, XFG_B3_IV7};
+        const uint32_t iv[8] = {XFG_B3_IV};
         uint32_t cv[8];
         b3_compress(iv, m, 64, 0, B3_CHUNK_START, cv);
 #pragma unroll

@@ -4,6 +4,7 @@
 #include <cstring>
 #include <vector>
 
+#include "dev_coin.hpp"
 #include "field_dft.hpp"
 #include "prover_internal.hpp"
 
@@ -69,6 +70,44 @@ static void launch_field_op(int op, const u64* a, const u64* b, u64* out, u64 co
         return;
     }
     hipLaunchKernelGGL(field_op_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, op, a, b, out, count);
+}
+
+// transcript self test (xfg_debug_coin_draws): from coin c0, k <= 64 draws by one wave (out_wave) and
+// one at a time (out_seq), both [k][2]; counters after each in ctr[2], success in ok[2].
+// AcceptForced: AcceptP plus forced rejections: candidate counter c in [1, 256] is rejected when bit
+// c - 1 of rej[4] is set (exercises wave_draw_e's window bookkeeping and its one-at-a-time fallback)
+struct AcceptForced {
+    const u64* rej;
+    __device__ bool operator()(u64 ctr, u64 x, u64 y, int D) const {
+        const bool forced = ctr >= 1 && ctr <= 256 && ((rej[(ctr - 1) >> 6] >> ((ctr - 1) & 63)) & 1);
+        return !forced && AcceptP()(ctr, x, y, D);
+    }
+};
+__global__ __launch_bounds__(64) void coin_draw_test_kernel(DevCoin c0, int k, int D, const u64* rej, u64* out_wave,
+                                                            u64* out_seq, u64* ctr, int* ok) {
+    const AcceptForced acc{rej};
+    DevCoin c = c0;
+    const bool okw = wave_draw_e(c, k, D, out_wave, 2, acc);
+    DevCoin q = c0;
+    bool oks = true;
+    for (int j = 0; j < k; j++) {
+        u64 a[2] = {0, 0};
+        oks &= dev_draw_e(q, a, D, acc);
+        if (threadIdx.x == 0) {
+            out_seq[2 * j] = a[0];
+            out_seq[2 * j + 1] = a[1];
+        }
+    }
+    if (threadIdx.x == 0) {
+        ctr[0] = c.counter;
+        ctr[1] = q.counter;
+        ok[0] = okw;
+        ok[1] = oks;
+    }
+}
+static void launch_coin_draw_test(const DevCoin& c0, int k, int ext, const u64* rej, u64* out_wave, u64* out_seq,
+                                  u64* ctr, int* ok, hipStream_t s) {
+    hipLaunchKernelGGL(coin_draw_test_kernel, dim3(1), dim3(64), 0, s, c0, k, ext, rej, out_wave, out_seq, ctr, ok);
 }
 
 // xfg_debug_lde / xfg_debug_lde_skip: skip (host, [npoly]) or nullptr
@@ -394,6 +433,75 @@ int xfg_debug_fri_fold(xfg_ctx* c, uint32_t count, uint32_t ext, uint32_t logn, 
         launch_fri_fold(L->f0.p, ext * D, D, coset_major != 0, (int)logn, (int)logbeta, rows, logD, L->alpha7.p,
                         L->deep.p, rows, T, (int)B, (int)ext, s);
         HIPCHK(hipMemcpyAsync(out, L->deep.p, B * ext * rows * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return XFG_OK;
+    });
+}
+
+// The two Merkle entries set the heaps to 0xFF bytes before the launches: a node a kernel fails to
+// store must show, whatever an earlier call left in the lane's buffers.
+int xfg_debug_merkle_lde(xfg_ctx* c, uint32_t count, uint32_t nc, uint64_t n, uint32_t blowup, const uint64_t* lde,
+                         const uint64_t* entries, uint64_t nentries, uint8_t* nodes_out, uint8_t* local_out) {
+    if (!c) return XFG_INVALID_ARGUMENT;
+    c->err.clear();
+    if (!lde || !nodes_out || (nentries && (!entries || !local_out)) || count == 0 || count > 0xFFFF ||
+        (nc != 1 && nc != 2 && nc != 7) || !is_pow2(blowup) || blowup < 2 || blowup > 16 || !is_pow2(n) || n < 8 ||
+        n > (1ULL << 24)) {
+        c->err = "xfg_debug_merkle_lde: null or unsupported argument";
+        return XFG_INVALID_ARGUMENT;
+    }
+    for (uint64_t e = 0; e < nentries; e++)
+        if (entries[e] >= (uint64_t)count * n) {
+            c->err = "xfg_debug_merkle_lde: entry names a proof or row out of range";
+            return XFG_INVALID_ARGUMENT;
+        }
+    return on_lane0(c, [&](Lane* L) -> int {
+        const int logn = (int)ilog2(n), logbeta = (int)ilog2(blowup);
+        const size_t B = count, nlde = B * nc * blowup * n, nloc = (size_t)nentries * 2 * blowup;
+        L->lde.ensure(nlde);
+        L->tnodes.ensure(B * 2 * n);
+        hipStream_t s = L->stream;
+        HIPCHK(hipMemcpyAsync(L->lde.p, lde, nlde * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemsetAsync(L->tnodes.p, 0xFF, B * 2 * n * sizeof(Digest), s));
+        launch_merkle_lde(L->lde.p, (int)nc, L->tnodes.p, (int)B, logn, logbeta, s);
+        HIPCHK(hipMemcpyAsync(nodes_out, L->tnodes.p, B * 2 * n * sizeof(Digest), hipMemcpyDeviceToHost, s));
+        if (nentries) {
+            L->scratch.ensure(nentries);
+            L->hnodes.ensure(nloc);
+            HIPCHK(hipMemcpyAsync(L->scratch.p, entries, nentries * 8, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemsetAsync(L->hnodes.p, 0xFF, nloc * sizeof(Digest), s));
+            launch_open_rows(L->lde.p, (int)nc, L->scratch.p, nentries, L->hnodes.p, logn, logbeta, s);
+            HIPCHK(hipMemcpyAsync(local_out, L->hnodes.p, nloc * sizeof(Digest), hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(hipStreamSynchronize(s));
+        return XFG_OK;
+    });
+}
+
+int xfg_debug_merkle_fri(xfg_ctx* c, uint32_t count, uint32_t ext, uint32_t logn, uint32_t logbeta, int coset_major,
+                         const uint64_t* vals, uint8_t* nodes_out) {
+    if (!c) return XFG_INVALID_ARGUMENT;
+    c->err.clear();
+    if (!vals || !nodes_out || count == 0 || count > 0xFFFF || (ext != 1 && ext != 2) || logn > 28 || logbeta > 28 ||
+        logn + logbeta < 4 || logn + logbeta > 28) {
+        c->err = "xfg_debug_merkle_fri: null or unsupported argument";
+        return XFG_INVALID_ARGUMENT;
+    }
+    return on_lane0(c, [&](Lane* L) -> int {
+        const size_t B = count;
+        const u64 D = 1ULL << (logn + logbeta), rows = D / 8;
+        if (!all_canonical(vals, B * ext * D)) {
+            c->err = "layer value is not a canonical field element";
+            return XFG_INVALID_ARGUMENT;
+        }
+        L->f0.ensure(B * ext * D);
+        L->tnodes.ensure(B * 2 * rows);
+        hipStream_t s = L->stream;
+        HIPCHK(hipMemcpyAsync(L->f0.p, vals, B * ext * D * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemsetAsync(L->tnodes.p, 0xFF, B * 2 * rows * sizeof(Digest), s));
+        launch_merkle_fri(L->f0.p, ext * D, D, coset_major != 0, (int)logn, (int)logbeta, rows, L->tnodes.p, (int)B,
+                          (int)ext, s);
+        HIPCHK(hipMemcpyAsync(nodes_out, L->tnodes.p, B * 2 * rows * sizeof(Digest), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return XFG_OK;
     });

@@ -41,7 +41,7 @@ struct B3Output {  // a compression whose flags are not final yet (ROOT is added
 };
 inline B3Output b3_chunk(const uint8_t* in, size_t len, uint64_t counter) {
     B3Output o;
-    const uint32_t iv[8] = {XFG_B3_IV0, XFG_B3_IV1, XFG_B3_IV2, XFG_B3_IV3, XFG_B3_IV4, XFG_B3_IV5, XFG_B3_IV6, XFG_B3_IV7};
+    const uint32_t iv[8] = {XFG_B3_IV};
     memcpy(o.cv, iv, sizeof iv);
     const size_t nblocks = len == 0 ? 1 : (len + 63) / 64;
     for (size_t b = 0; b < nblocks; b++) {
@@ -60,7 +60,7 @@ inline B3Output b3_chunk(const uint8_t* in, size_t len, uint64_t counter) {
 }
 inline B3Output b3_parent(const uint32_t l[8], const uint32_t r[8]) {
     B3Output o;
-    const uint32_t iv[8] = {XFG_B3_IV0, XFG_B3_IV1, XFG_B3_IV2, XFG_B3_IV3, XFG_B3_IV4, XFG_B3_IV5, XFG_B3_IV6, XFG_B3_IV7};
+    const uint32_t iv[8] = {XFG_B3_IV};
     memcpy(o.cv, iv, sizeof iv);
     memcpy(o.m, l, 32);
     memcpy(o.m + 8, r, 32);

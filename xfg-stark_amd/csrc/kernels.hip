@@ -2,15 +2,16 @@
 //
 // Replaces, inside Winterfell 0.8.3 `Prover::prove` as bound by the reference
 // (src/burn_mint_air.rs:479-531, called at src/burn_mint_prover.rs:124-126):
-//   - DefaultTraceLde: column interpolation + coset LDE (four-step NTT, LDS radix-2 stages)
-//   - RowMatrix::commit_to_rows / MerkleTree::new: Blake3 row hashing + binary Merkle tree
 //   - DefaultConstraintEvaluator with XfgBurnMintAir::evaluate_transition (:335-378) and the
 //     8 assertions (:380-395), batch-inverted divisors
 //   - CompositionPoly / DeepCompositionPoly: OOD evaluation, coefficient-domain DEEP combine with
 //     synthetic division expressed as a weighted suffix scan
-//   - FriProver::build_layers: fold-by-8 (apply_drp) and per-layer commitments
+//   - FriProver::build_layers: fold-by-8 (apply_drp)
+// and the gathers / packing of the openings and the replay block. The LDE is ntt.hip; the Merkle
+// commitments (trace, composition, FRI layers) and the transcript step on their roots are merkle.hip;
+// the device transcript itself is dev_coin.hpp (here: the DEEP draws, deep_coin_block).
 // All arithmetic is 64-bit Goldilocks integer work: HBM/VALU bound, no MFMA.
-#include "kernels.hpp"
+#include "dev_coin.hpp"
 #include "field_dft.hpp"
 #include <algorithm>
 
@@ -28,600 +29,6 @@ __device__ __forceinline__ u64 tw_pow(const Tables& T, int k, u64 e) {
 __device__ __forceinline__ u64 tw_ipow(const Tables& T, int k, u64 e) {
     u64 M = 1ULL << T.LM;
     return T.tw[(M - ((e << (T.LM - k)) & (M - 1))) & (M - 1)];
-}
-
-// One Merkle parent BLAKE3(l || r) (one 64-byte block: CHUNK_START | CHUNK_END | ROOT, counter 0) computed
-// by the four lanes of a quad: lane q holds column q of the state (s[q], s[4 + q], s[8 + q], s[12 + q]) and
-// all 16 message words. The column half is lane q's G function on its own column; for the diagonal half
-// rows 1-3 rotate by 1, 2, 3 lanes (DPP quad_perm, the compiler's hazard padding) so that lane q holds
-// s[q], s[4 + (q+1)%4], s[8 + (q+2)%4], s[12 + (q+3)%4], and rotate back after it. Each lane picks its
-// G's two message words of the round by a 4-way select. ~330 VALU per lane on the critical path instead of
-// one lane's ~680: the serial top levels of a tree (one compression per level) finish about twice as
-// fast, at four lanes per node. Returns (out[q], out[4 + q]).
-__device__ __forceinline__ uint32_t sel4(bool b0, bool b1, uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3) {
-    return b1 ? (b0 ? x3 : x2) : (b0 ? x1 : x0);
-}
-template <int CTRL>
-__device__ __forceinline__ uint32_t quad_perm(uint32_t x) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xF, 0xF, false);
-}
-constexpr int QP_ROT1 = 0x39, QP_ROT2 = 0x4E, QP_ROT3 = 0x93;  // lane q reads lane (q + k) % 4
-#define XFG_B3_GQ(a, b, c, d, x, y)               \
-    do {                                          \
-        a = b3_add3(a, b, (x));                   \
-        d = b3_rotr(b3_xor(d, a), 16);            \
-        c = b3_add(c, d);                         \
-        b = b3_rotr(b3_xor(b, c), 12);            \
-        a = b3_add3(a, b, (y));                   \
-        d = b3_rotr(b3_xor(d, a), 8);             \
-        c = b3_add(c, d);                         \
-        b = b3_rotr(b3_xor(b, c), 7);             \
-    } while (0)
-// (any chaining value, block length and flags, counter 0: b3_compress_quad; the Merkle parent: b3_merge_quad)
-__device__ __forceinline__ uint2 b3_compress_quad(const uint32_t cv[8], uint32_t m[16], uint32_t len, uint32_t flags,
-                                                  int q) {
-    const bool q0 = q & 1, q1 = (q & 2) != 0;
-    uint32_t a = sel4(q0, q1, cv[0], cv[1], cv[2], cv[3]);
-    uint32_t b = sel4(q0, q1, cv[4], cv[5], cv[6], cv[7]);
-    uint32_t c = sel4(q0, q1, XFG_B3_IV0, XFG_B3_IV1, XFG_B3_IV2, XFG_B3_IV3);
-    uint32_t d = sel4(q0, q1, 0u, 0u, len, flags);
-#pragma unroll
-    for (int r = 0; r < 7; r++) {
-        XFG_B3_GQ(a, b, c, d, sel4(q0, q1, m[0], m[2], m[4], m[6]), sel4(q0, q1, m[1], m[3], m[5], m[7]));
-        b = quad_perm<QP_ROT1>(b);
-        c = quad_perm<QP_ROT2>(c);
-        d = quad_perm<QP_ROT3>(d);
-        XFG_B3_GQ(a, b, c, d, sel4(q0, q1, m[8], m[10], m[12], m[14]), sel4(q0, q1, m[9], m[11], m[13], m[15]));
-        b = quad_perm<QP_ROT3>(b);
-        c = quad_perm<QP_ROT2>(c);
-        d = quad_perm<QP_ROT1>(d);
-        if (r < 6) XFG_B3_PERMUTE(m);
-    }
-    return make_uint2(a ^ c, b ^ d);
-}
-__device__ __forceinline__ uint2 b3_merge_quad(uint32_t m[16], int q) {
-    const uint32_t iv[8] = {XFG_B3_IV0, XFG_B3_IV1, XFG_B3_IV2, XFG_B3_IV3, XFG_B3_IV4, XFG_B3_IV5, XFG_B3_IV6, XFG_B3_IV7};
-    return b3_compress_quad(iv, m, 64, B3_CHUNK_START | B3_CHUNK_END | B3_ROOT, q);
-}
-// a wave-uniform compression (every lane holding the same block: the transcript steps) split over each
-// quad as above, the eight output words then broadcast to the quad's lanes (DPP quad_perm [k,k,k,k])
-__device__ __forceinline__ void b3_compress_uniform(const uint32_t cv[8], uint32_t m[16], uint32_t len, uint32_t flags,
-                                                    uint32_t out[8]) {
-    const uint2 o = b3_compress_quad(cv, m, len, flags, (int)(threadIdx.x & 3));
-    out[0] = quad_perm<0x00>(o.x);
-    out[1] = quad_perm<0x55>(o.x);
-    out[2] = quad_perm<0xAA>(o.x);
-    out[3] = quad_perm<0xFF>(o.x);
-    out[4] = quad_perm<0x00>(o.y);
-    out[5] = quad_perm<0x55>(o.y);
-    out[6] = quad_perm<0xAA>(o.y);
-    out[7] = quad_perm<0xFF>(o.y);
-}
-
-// ============================================================================ device transcript
-// winter-crypto DefaultRandomCoin<Blake3_256> on the device (host twin: host_common.hpp Coin). The
-// transcript steps run inside the kernels that produce their inputs: the coefficient, OOD-point and
-// FRI alpha draws in the block that computes the Merkle root (tree_top_kernel), the DEEP draws in the
-// block that finishes the OOD sums (ood_final_kernel).
-__device__ __forceinline__ Digest dev_merge_int(const Digest& seed, u64 v) {
-    uint32_t m[16];
-#pragma unroll
-    for (int i = 0; i < 8; i++) m[i] = seed.w[i];
-    m[8] = (uint32_t)v;
-    m[9] = (uint32_t)(v >> 32);
-#pragma unroll
-    for (int i = 10; i < 16; i++) m[i] = 0;
-    return b3_hash_block<0xFC00u>(m, 40);  // words 10..15 are zero
-}
-// the same for a (seed, v) every lane of the wave holds: four lanes per compression (b3_compress_uniform)
-__device__ __forceinline__ Digest dev_merge_int_uniform(const Digest& seed, u64 v) {
-    const uint32_t iv[8] = {XFG_B3_IV0, XFG_B3_IV1, XFG_B3_IV2, XFG_B3_IV3, XFG_B3_IV4, XFG_B3_IV5, XFG_B3_IV6, XFG_B3_IV7};
-    uint32_t m[16];
-#pragma unroll
-    for (int i = 0; i < 8; i++) m[i] = seed.w[i];
-    m[8] = (uint32_t)v;
-    m[9] = (uint32_t)(v >> 32);
-#pragma unroll
-    for (int i = 10; i < 16; i++) m[i] = 0;
-    Digest d;
-    b3_compress_uniform(iv, m, 40, B3_CHUNK_START | B3_CHUNK_END | B3_ROOT, d.w);
-    return d;
-}
-// acceptance of a drawn candidate (counter, first two LE words): every element < p
-struct AcceptP {
-    __device__ bool operator()(u64, u64 x, u64 y, int D) const { return x < P && (D == 1 || y < P); }
-};
-// Coin::draw_e: the first 8 D digest bytes as D LE elements, retried while any is >= p
-template <class A = AcceptP>
-__device__ __forceinline__ bool dev_draw_e(DevCoin& c, u64* out, int D, A acc = A()) {
-    for (int i = 0; i < 1000; i++) {
-        const Digest v = dev_merge_int_uniform(c.seed, ++c.counter);
-        const u64 x = (u64)v.w[0] | ((u64)v.w[1] << 32), y = (u64)v.w[2] | ((u64)v.w[3] << 32);
-        if (acc(c.counter, x, y, D)) {
-            out[0] = x;
-            out[1] = D == 2 ? y : 0;
-            return true;
-        }
-    }
-    return false;
-}
-__device__ __forceinline__ void dev_reseed(DevCoin& c, const Digest& d) {
-    const uint32_t iv[8] = {XFG_B3_IV0, XFG_B3_IV1, XFG_B3_IV2, XFG_B3_IV3, XFG_B3_IV4, XFG_B3_IV5, XFG_B3_IV6, XFG_B3_IV7};
-    uint32_t m[16];
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        m[i] = c.seed.w[i];
-        m[8 + i] = d.w[i];
-    }
-    b3_compress_uniform(iv, m, 64, B3_CHUNK_START | B3_CHUNK_END | B3_ROOT, c.seed.w);
-    c.counter = 0;
-}
-// Blake3_256::hash_elements of cnt <= 128 elements: one chunk of ceil(8 cnt / 64) blocks. Like dev_reseed and
-// dev_draw_e, called by a whole wave with the same inputs in every lane (four lanes per compression)
-__device__ Digest dev_hash_elems(const u64* e, int cnt) {
-    uint32_t cv[8] = {XFG_B3_IV0, XFG_B3_IV1, XFG_B3_IV2, XFG_B3_IV3, XFG_B3_IV4, XFG_B3_IV5, XFG_B3_IV6, XFG_B3_IV7};
-    const int len = 8 * cnt, nb = (len + 63) / 64;
-    Digest d;
-    for (int blk = 0; blk < nb; blk++) {
-        uint32_t m[16];
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            const int k = 8 * blk + i;
-            const u64 v = k < cnt ? e[k] : 0;
-            m[2 * i] = (uint32_t)v;
-            m[2 * i + 1] = (uint32_t)(v >> 32);
-        }
-        const bool last = blk == nb - 1;
-        const uint32_t flags = (blk == 0 ? B3_CHUNK_START : 0u) | (last ? B3_CHUNK_END | B3_ROOT : 0u);
-        uint32_t out[8];
-        b3_compress_uniform(cv, m, last ? (uint32_t)(len - 64 * blk) : 64u, flags, out);
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            cv[i] = out[i];
-            d.w[i] = out[i];
-        }
-    }
-    return d;
-}
-// k <= 64 consecutive draws of E by one full wave, every lane holding the same coin: lane i hashes
-// counter + 1 + i at once, and the accepted candidates in counter order are exactly the draws
-// Coin::draw_e makes one after another (a rejected candidate is the one its retry skips). Draw j
-// goes to out[j S .. j S + D) (S = stride >= D). If the window holds fewer than k accepted candidates (>= 50
-// rejections of probability 2^-32 each) the rest are drawn one at a time after the last accepted.
-// The latency is one compression instead of k: these draws sit between two launches of the chain.
-template <class A = AcceptP>
-__device__ bool wave_draw_e(DevCoin& c, int k, int D, u64* out, int S, A acc = A()) {
-    const int lane = threadIdx.x & 63;
-    const Digest v = dev_merge_int(c.seed, c.counter + 1 + lane);
-    const u64 x = (u64)v.w[0] | ((u64)v.w[1] << 32), y = (u64)v.w[2] | ((u64)v.w[3] << 32);
-    const bool ok = acc(c.counter + 1 + lane, x, y, D);
-    const u64 mask = __ballot(ok);
-    const int idx = __popcll(mask & ((1ULL << lane) - 1));
-    if (ok && idx < k) {
-        out[idx * S] = x;
-        if (D == 2) out[idx * S + 1] = y;
-    }
-    const int got = __popcll(mask);
-    if (got >= k) {
-        u64 m = mask;
-        for (int i = 1; i < k; i++) m &= m - 1;  // lowest set bit = the k-th accepted candidate
-        c.counter += __ffsll((unsigned long long)m);
-        return true;
-    }
-    if (got > 0) c.counter += 64 - __clzll(mask);  // just past the last accepted candidate
-    bool all = true;
-    for (int j = got; j < k; j++) {
-        u64 a[2] = {0, 0};
-        all &= dev_draw_e(c, a, D, acc);
-        if (lane == 0)
-            for (int d = 0; d < D; d++) out[j * S + d] = a[d];
-    }
-    return all;
-}
-// one wave (all lanes, uniform) of the block that computed proof b's root: reseed with the root,
-// then the draws that follow that commitment in Prover::prove
-__device__ void coin_root_step(const CoinStep& cs, int b, const Digest& root) {
-    const int D = cs.ext, lane = threadIdx.x;
-    DevCoin c = cs.coins[b];
-    dev_reseed(c, root);
-    bool ok;
-    if (cs.kind == CoinStep::COEFFS) {  // 7 transition + 8 boundary composition coefficients
-        ok = wave_draw_e(c, 15, D, cs.out + (u64)b * 15 * D, D);
-    } else {
-        u64 a[2] = {0, 0};
-        ok = dev_draw_e(c, a, D);
-        if (cs.kind == CoinStep::OOD_POINT) {  // z, and z g; z = 0 leaves no DEEP quotient
-            if (a[0] == 0 && a[1] == 0) ok = false;
-            if (lane == 0)
-                for (int k = 0; k < D; k++) {
-                    cs.out[(u64)b * 2 * D + k] = a[k];
-                    cs.out[(u64)b * 2 * D + D + k] = gl_mul(a[k], cs.g);
-                }
-        } else if (lane == 0) {  // FRI layer alpha, stored as alpha * 7^-1 for the fold
-            const u64 inv7 = 0x249249246DB6DB6EULL;
-            for (int k = 0; k < D; k++) cs.out[(u64)b * D + k] = gl_mul(a[k], inv7);
-            if (cs.hist)
-                for (int k = 0; k < D; k++) cs.hist[(u64)b * D + k] = a[k];
-        }
-    }
-    if (lane == 0) {
-        if (!ok) cs.fail[b] = 1;
-        cs.coins[b] = c;
-        if (cs.root_out) cs.root_out[b] = root;
-    }
-}
-
-// ============================================================================ Merkle
-// Heap layout per tree: nodes[1] = root, nodes[i] = H(nodes[2i] || nodes[2i+1]), leaf k at L + k
-// (MerkleTree::new / build_merkle_nodes, winter-crypto 0.8.3). For the LDE commitments only the
-// levels >= log2(beta) are stored (heap [1, 2n)): the 2^log2(beta) leaves of LDE row m (one per
-// coset, coset-major layout) form a register-resident subtree whose top is heap node n + m. The
-// few leaves / low nodes a proof opens are recomputed from the LDE by open_rows_kernel.
-
-// subtree over the leaves t = T0 .. T0 + 2^LOG - 1 of LDE row m; compile-time recursion keeps
-// every intermediate digest in registers. If `local` is non-null the nodes are also written to
-// a local heap (slot 1 = top, leaves at 2^LOGB + t).
-template <int NC, int LOGB, int LOG, int T0>
-__device__ __forceinline__ Digest lde_subtree(const u64* base, u64 n, u64 m, Digest* local) {
-    if constexpr (LOG == 0) {
-        u64 row[NC];
-#pragma unroll
-        for (int c = 0; c < NC; c++) row[c] = base[((u64)c * (1 << LOGB) + T0) * n + m];
-        Digest d = b3_hash_elems<NC>(row);
-        if (local) local[(1 << LOGB) + T0] = d;
-        return d;
-    } else {
-        Digest l = lde_subtree<NC, LOGB, LOG - 1, T0>(base, n, m, local);
-        Digest r = lde_subtree<NC, LOGB, LOG - 1, T0 + (1 << (LOG - 1))>(base, n, m, local);
-        Digest p = b3_merge(l, r);
-        if (local) local[((1 << LOGB) + T0) >> LOG] = p;
-        return p;
-    }
-}
-
-struct Digest2 {
-    Digest a, b;
-};
-// subtrees of two adjacent LDE rows (m, m+1) over cosets T0 .. T0 + 2^LOG - 1, evaluated depth
-// first: each leaf pair is loaded (one 16-byte load per column) right before it is hashed, so
-// only O(LOGB) digests per row are live
-template <int NC, int LOGB, int LOG, int T0>
-__device__ __forceinline__ Digest2 pair_subtree(const u64* base, u64 n, u64 m) {
-    if constexpr (LOG == 0) {
-        u64 r0[NC], r1[NC];
-#pragma unroll
-        for (int c = 0; c < NC; c++) {
-            const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(base + ((u64)c * (1 << LOGB) + T0) * n + m);
-            r0[c] = v.x;
-            r1[c] = v.y;
-        }
-        return Digest2{b3_hash_elems<NC>(r0), b3_hash_elems<NC>(r1)};
-    } else {
-        Digest2 l = pair_subtree<NC, LOGB, LOG - 1, T0>(base, n, m);
-        Digest2 r = pair_subtree<NC, LOGB, LOG - 1, T0 + (1 << (LOG - 1))>(base, n, m);
-        return Digest2{b3_merge(l.a, r.a), b3_merge(l.b, r.b)};
-    }
-}
-
-// Block-level continuation of a Merkle level: thread t of a block of T (power of two) threads
-// holds the digest of node blockIdx.x * T + t of the level with `count` nodes (heap [count,
-// 2 count)). The block merges its T nodes up log2(T) levels through LDS, storing every parent, so
-// only count / T nodes are left for launch_tree_top.
-// Levels stop once a level has `wmin` nodes per block (lanes of narrower levels would idle).
-__device__ __forceinline__ void block_tree_up(Digest d, Digest* nodes, u64 count, Digest* lds, int wmin) {
-    const int t = threadIdx.x;
-    u64 c = count;
-    for (int w = blockDim.x; w > wmin; w >>= 1) {
-        lds[t] = d;
-        __syncthreads();
-        c >>= 1;
-        if (t < w / 2) {
-            d = b3_merge(lds[2 * t], lds[2 * t + 1]);
-            nodes[c + (u64)blockIdx.x * (w / 2) + t] = d;
-        }
-        __syncthreads();
-    }
-}
-
-// two consecutive LDE rows per thread: 2 * 2^LOGB leaves, subtree top at level LOGB + 1 =
-// heap node n/2 + m/2; then log2(blockDim) levels more in LDS
-template <int NC, int LOGB>
-__global__ __launch_bounds__(256) void leaves_lde_kernel(const u64* lde, Digest* nodes_all, u64 node_stride,
-                                                         int logn, int wmin) {
-    __shared__ Digest lds[256];
-    const u64 n = 1ULL << logn;
-    const int proof = blockIdx.y;
-    const u64 m2 = (u64)blockIdx.x * blockDim.x + threadIdx.x;  // row pair (grid covers n/2 exactly)
-    const u64* base = lde + (u64)proof * NC * (1 << LOGB) * n;
-    Digest2 d = pair_subtree<NC, LOGB, LOGB, 0>(base, n, 2 * m2);
-    Digest top = b3_merge(d.a, d.b);
-    Digest* nodes = nodes_all + (u64)proof * node_stride;
-    nodes[n / 2 + m2] = top;
-    block_tree_up(top, nodes, n / 2, lds, wmin);
-}
-
-// one LDE row per thread: the row's 2^LOGB-leaf subtree (top at heap level log2(beta), not stored),
-// then through LDS the row-pair level (heap n/2 + m/2) and one more (n/4 + m/4): 256 rows -> 64 nodes
-// per block, n/4 left for launch_tree_top. Against leaves_lde_kernel (two rows per thread) a thread
-// holds one row and one pending digest per subtree level -- 49-56 instead of 83-105 VGPRs, 8
-// instead of 4-5 waves per SIMD -- for the same compressions: the trace leaves 3.3 % faster, the
-// composition leaves unchanged (profiles/r05/leaves_row.txt).
-template <int NC, int LOGB>
-__global__ __launch_bounds__(256) void leaves_row_kernel(const u64* lde, Digest* nodes_all, u64 node_stride,
-                                                         int logn) {
-    __shared__ Digest lds[256];
-    const u64 n = 1ULL << logn;
-    const int proof = blockIdx.y, t = threadIdx.x;
-    const u64 m = (u64)blockIdx.x * 256 + t;
-    const u64* base = lde + (u64)proof * NC * (1 << LOGB) * n;
-    Digest d = lde_subtree<NC, LOGB, LOGB, 0>(base, n, m, nullptr);
-    Digest* nodes = nodes_all + (u64)proof * node_stride;
-    u64 c = n / 2;
-    for (int w = 128; w >= 64; w >>= 1, c >>= 1) {
-        lds[t] = d;
-        __syncthreads();
-        if (t < w) {
-            d = b3_merge(lds[2 * t], lds[2 * t + 1]);
-            nodes[c + (u64)blockIdx.x * w + t] = d;
-        }
-        __syncthreads();
-    }
-}
-
-// The same levels for small launch sets (a lone proof: one wave per SIMD, each running the row's
-// 2 beta - 1 compressions in sequence): 2^LOGL lanes per row, each the subtree of beta / 2^LOGL cosets,
-// merged across the lane group (__shfl_xor, every lane of the group merging at every level), then the
-// row-pair level and one more through LDS: 256 / 2^LOGL rows -> a quarter as many nodes per block.
-// 2^LOGL times the waves, and a chain of beta / 2^LOGL + log2 beta + 2 compressions instead of 2 beta + 1.
-constexpr int LEAF_LANES_LOG = 1;  // 2 lanes per row (4: 42.5 + 40.4 against 31.8 + 27.9 µs, profiles/r06/leaves_small_ab.txt)
-template <int LOGB>
-constexpr int leaf_lanes_log() { return LOGB < LEAF_LANES_LOG ? LOGB : LEAF_LANES_LOG; }
-template <int NC, int LOGB>
-__global__ __launch_bounds__(256) void leaves_row2_kernel(const u64* lde, Digest* nodes_all, u64 node_stride,
-                                                          int logn) {
-    constexpr int LOGL = leaf_lanes_log<LOGB>(), RB = 256 >> LOGL;  // lanes per row (log2), rows per block
-    __shared__ Digest lds[RB];
-    const u64 n = 1ULL << logn;
-    const int proof = blockIdx.y, t = threadIdx.x, h = t & ((1 << LOGL) - 1), rl = t >> LOGL;
-    const u64 m = (u64)blockIdx.x * RB + rl;
-    const u64* base = lde + (u64)proof * NC * (1 << LOGB) * n + (u64)h * (1 << (LOGB - LOGL)) * n;
-    Digest d = lde_subtree<NC, LOGB, LOGB - LOGL, 0>(base, n, m, nullptr);
-#pragma unroll
-    for (int k = 0; k < LOGL; k++) {
-        Digest r;
-#pragma unroll
-        for (int w = 0; w < 8; w++) r.w[w] = __shfl_xor(d.w[w], 1 << k);
-        d = (h >> k) & 1 ? b3_merge(r, d) : b3_merge(d, r);
-    }
-    Digest* nodes = nodes_all + (u64)proof * node_stride;
-    if (h == 0) lds[rl] = d;
-    __syncthreads();
-    if (t < RB / 2) {
-        d = b3_merge(lds[2 * t], lds[2 * t + 1]);
-        nodes[n / 2 + (u64)blockIdx.x * (RB / 2) + t] = d;
-    }
-    __syncthreads();
-    if (t < RB / 2) lds[t] = d;
-    __syncthreads();
-    if (t < RB / 4) nodes[n / 4 + (u64)blockIdx.x * (RB / 4) + t] = b3_merge(lds[2 * t], lds[2 * t + 1]);
-}
-// openings: recompute the local subtree heaps of selected rows; entry e = proof << logn | m. One
-// lane per leaf (coset t of row m, 2^LOGB lanes per entry inside a wave): the leaf, then LOGB
-// merge levels with the right child taken from lane l ^ 2^(k-1) -- 1 + LOGB dependent compressions
-// per entry instead of the 2^(LOGB+1) - 1 one lane ran in sequence (a lone proof waits on them).
-// Every lane of a group merges at every level (no divergence around the shuffles); the lanes with
-// t % 2^k == 0 hold level k's nodes and store them to the local heap (slot 1 = top).
-template <int NC, int LOGB>
-__global__ __launch_bounds__(64) void open_rows_kernel(const u64* lde, const u64* entries, u64 count, Digest* out,
-                                                       int logn) {
-    const u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    const u64 e = g >> LOGB;
-    const int t = (int)(g & ((1 << LOGB) - 1));
-    if (e >= count) return;  // whole groups: count is per entry, groups never straddle a wave
-    const u64 n = 1ULL << logn, ent = entries[e];
-    const u64 proof = ent >> logn, m = ent & (n - 1);
-    const u64* base = lde + proof * NC * (1 << LOGB) * n;
-    Digest* local = out + e * (2 << LOGB);
-    u64 row[NC];
-#pragma unroll
-    for (int c = 0; c < NC; c++) row[c] = base[((u64)c * (1 << LOGB) + t) * n + m];
-    Digest d = b3_hash_elems<NC>(row);
-    local[(1 << LOGB) + t] = d;
-#pragma unroll
-    for (int k = 1; k <= LOGB; k++) {
-        Digest r;
-#pragma unroll
-        for (int w = 0; w < 8; w++) r.w[w] = __shfl_xor(d.w[w], 1 << (k - 1));
-        d = b3_merge(d, r);
-        if ((t & ((1 << k) - 1)) == 0) local[((1 << LOGB) + t) >> k] = d;
-    }
-}
-
-#define XFG_LOGB_DISPATCH(KERNEL, NC, logbeta, ...)                                            \
-    switch (logbeta) {                                                                          \
-        case 1: hipLaunchKernelGGL((KERNEL<NC, 1>), __VA_ARGS__); break;                        \
-        case 2: hipLaunchKernelGGL((KERNEL<NC, 2>), __VA_ARGS__); break;                        \
-        case 3: hipLaunchKernelGGL((KERNEL<NC, 3>), __VA_ARGS__); break;                        \
-        case 4: hipLaunchKernelGGL((KERNEL<NC, 4>), __VA_ARGS__); break;                        \
-        default: break;                                                                         \
-    }
-
-// in-block Merkle levels continue while a level keeps >= 64 nodes per block (full waves only); the
-// narrower levels go to launch_tree_top
-static int up_wmin(u64 T) { return (int)std::min<u64>(T, 64); }
-u64 launch_leaves_lde(const u64* lde, int nc, Digest* nodes, u64 node_stride, int npoly, int logn, int logbeta,
-                      hipStream_t s) {
-    const u64 n = 1ULL << logn, T = std::min<u64>(256, n / 2);
-    if (n >= 1024 && logbeta >= 1 && (u64)npoly * (n / 256) < 1024) {  // under one wave per SIMD
-        const int logl = logbeta < LEAF_LANES_LOG ? logbeta : LEAF_LANES_LOG;
-        dim3 g((unsigned)(n >> (8 - logl)), npoly), b(256);
-        if (nc == 7) { XFG_LOGB_DISPATCH(leaves_row2_kernel, 7, logbeta, g, b, 0, s, lde, nodes, node_stride, logn) }
-        else if (nc == 2) { XFG_LOGB_DISPATCH(leaves_row2_kernel, 2, logbeta, g, b, 0, s, lde, nodes, node_stride, logn) }
-        else { XFG_LOGB_DISPATCH(leaves_row2_kernel, 1, logbeta, g, b, 0, s, lde, nodes, node_stride, logn) }
-        XFG_CHECK_LAUNCH();
-        return n / 4;
-    }
-    if (n >= 1024) {
-        dim3 g((unsigned)(n / 256), npoly), b(256);
-        if (nc == 7) { XFG_LOGB_DISPATCH(leaves_row_kernel, 7, logbeta, g, b, 0, s, lde, nodes, node_stride, logn) }
-        else if (nc == 2) { XFG_LOGB_DISPATCH(leaves_row_kernel, 2, logbeta, g, b, 0, s, lde, nodes, node_stride, logn) }
-        else { XFG_LOGB_DISPATCH(leaves_row_kernel, 1, logbeta, g, b, 0, s, lde, nodes, node_stride, logn) }
-        XFG_CHECK_LAUNCH();
-        return n / 4;
-    }
-    const int wmin = up_wmin(T);
-    dim3 g((unsigned)(n / 2 / T), npoly), b((unsigned)T);
-    if (nc == 7) { XFG_LOGB_DISPATCH(leaves_lde_kernel, 7, logbeta, g, b, 0, s, lde, nodes, node_stride, logn, wmin) }
-    else if (nc == 2) { XFG_LOGB_DISPATCH(leaves_lde_kernel, 2, logbeta, g, b, 0, s, lde, nodes, node_stride, logn, wmin) }
-    else { XFG_LOGB_DISPATCH(leaves_lde_kernel, 1, logbeta, g, b, 0, s, lde, nodes, node_stride, logn, wmin) }
-    XFG_CHECK_LAUNCH();
-    return n / 2 / T * wmin;
-}
-void launch_open_rows(const u64* lde, int nc, const u64* entries, u64 count, Digest* out, int logn, int logbeta,
-                      hipStream_t s) {
-    if (!count) return;
-    dim3 g((unsigned)(((count << logbeta) + 63) / 64)), b(64);
-    if (nc == 7) { XFG_LOGB_DISPATCH(open_rows_kernel, 7, logbeta, g, b, 0, s, lde, entries, count, out, logn) }
-    else if (nc == 2) { XFG_LOGB_DISPATCH(open_rows_kernel, 2, logbeta, g, b, 0, s, lde, entries, count, out, logn) }
-    else { XFG_LOGB_DISPATCH(open_rows_kernel, 1, logbeta, g, b, 0, s, lde, entries, count, out, logn) }
-    XFG_CHECK_LAUNCH();
-}
-
-// last levels (count <= 512): one block per tree, four lanes per node (b3_merge_quad), the levels
-// through LDS; then the transcript step `cs` on the root
-__global__ __launch_bounds__(1024) void tree_top_kernel(Digest* nodes_all, u64 node_stride, u64 count, CoinStep cs) {
-    __shared__ Digest lds[256];
-    Digest* nodes = nodes_all + (u64)blockIdx.x * node_stride;
-    const int tid = threadIdx.x, i = tid >> 2, q = tid & 3;
-    for (u64 c = count; c > 1; c >>= 1) {
-        const u64 half = c >> 1;
-        const bool act = i < (int)half;  // whole quads
-        uint2 o = make_uint2(0, 0);
-        if (act) {
-            const Digest* src = c == count ? nodes + c + 2 * i : lds + 2 * i;
-            uint32_t m[16];
-#pragma unroll
-            for (int w = 0; w < 8; w++) {
-                m[w] = src[0].w[w];
-                m[8 + w] = src[1].w[w];
-            }
-            o = b3_merge_quad(m, q);
-        }
-        __syncthreads();
-        if (act) {
-            lds[i].w[q] = o.x;
-            lds[i].w[4 + q] = o.y;
-            nodes[half + i].w[q] = o.x;
-            nodes[half + i].w[4 + q] = o.y;
-        }
-        __syncthreads();
-    }
-    if (cs.kind != CoinStep::NONE && tid < 64) coin_root_step(cs, blockIdx.x, count > 1 ? lds[0] : nodes[1]);
-}
-// middle levels: a block merges 512 consecutive nodes of level `count` (two per thread, coalesced)
-// and continues through LDS while a level keeps full waves, writing every parent: 64 nodes per block,
-// count / 8 remain. (Merging on down to one node per block ran six more levels on one part-filled
-// wave each: 13 wave-compressions per block for the work of 8.)
-constexpr int TREE_MID_WMIN = 64, TREE_MID_SHRINK = 8;
-__global__ __launch_bounds__(256) void tree_mid_kernel(Digest* nodes_all, u64 node_stride, u64 count) {
-    __shared__ Digest lds[256];
-    Digest* nodes = nodes_all + (u64)blockIdx.y * node_stride;
-    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
-    const Digest d = b3_merge(nodes[count + 2 * i], nodes[count + 2 * i + 1]);
-    nodes[count / 2 + i] = d;
-    block_tree_up(d, nodes, count / 2, lds, TREE_MID_WMIN);
-}
-// the same three levels for small launch sets (under one block per CU: a lone proof's trees), four lanes
-// per parent (b3_merge_quad): 128 nodes in, 16 out per block, each level's latency about half
-__global__ __launch_bounds__(256) void tree_mid4_kernel(Digest* nodes_all, u64 node_stride, u64 count) {
-    __shared__ Digest lds[64];
-    Digest* nodes = nodes_all + (u64)blockIdx.y * node_stride;
-    const int tid = threadIdx.x, i = tid >> 2, q = tid & 3;
-    u64 c = count, first = (u64)blockIdx.x * 64;  // level being merged; this block's first parent in it
-    for (int w = 64; w >= 16; w >>= 1, c >>= 1, first >>= 1) {
-        const bool act = i < w;  // whole quads
-        uint2 o = make_uint2(0, 0);
-        if (act) {
-            const Digest* src = w == 64 ? nodes + c + 2 * (first + i) : lds + 2 * i;
-            uint32_t m[16];
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                m[k] = src[0].w[k];
-                m[8 + k] = src[1].w[k];
-            }
-            o = b3_merge_quad(m, q);
-        }
-        __syncthreads();
-        if (act) {
-            lds[i].w[q] = o.x;
-            lds[i].w[4 + q] = o.y;
-            Digest* dst = nodes + c / 2 + first + i;
-            dst->w[q] = o.x;
-            dst->w[4 + q] = o.y;
-        }
-        __syncthreads();
-    }
-}
-void launch_tree_top(Digest* nodes, u64 node_stride, u64 count, int npoly, hipStream_t s, const CoinStep& cs) {
-    while (count > 512) {
-        if ((count / 512) * (u64)npoly < 256)
-            hipLaunchKernelGGL(tree_mid4_kernel, dim3((unsigned)(count / 128), npoly), dim3(256), 0, s, nodes,
-                               node_stride, count);
-        else
-            hipLaunchKernelGGL(tree_mid_kernel, dim3((unsigned)(count / 512), npoly), dim3(256), 0, s, nodes,
-                               node_stride, count);
-        count /= TREE_MID_SHRINK;
-    }
-    if (count > 1 || cs.kind != CoinStep::NONE) {
-        int threads = (int)(2 * count);  // four lanes per node of the widest level
-        threads = threads < 64 ? 64 : threads;
-        hipLaunchKernelGGL(tree_top_kernel, dim3(npoly), dim3(threads), 0, s, nodes, node_stride, count, cs);
-    }
-    XFG_CHECK_LAUNCH();
-}
-
-// FRI layer value at natural index K of a layer stored coset-major (layer 0) or natural
-__device__ __forceinline__ u64 layer_at(const u64* base, bool coset_major, int logn, int logbeta, u64 K) {
-    if (!coset_major) return base[K];
-    u64 t = K & ((1ULL << logbeta) - 1), m = K >> logbeta;
-    return base[(t << logn) + m];
-}
-
-// FRI layer leaves (hash_values::<H, E, 8> over transpose_slice rows): leaf i = H(values at
-// natural indices i + k*rows, k < 8). All leaves are stored (layers are N/8 and smaller).
-// E-valued layers are D coordinate planes `comp_stride` elements apart (per proof: D planes)
-template <int D>
-__global__ __launch_bounds__(256) void fri_leaves_kernel(const u64* vals, u64 val_stride, u64 comp_stride,
-                                                         int coset_major, int logn, int logbeta, u64 rows,
-                                                         Digest* nodes_all, u64 node_stride, int wmin) {
-    __shared__ Digest lds[256];
-    const int proof = blockIdx.y;
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;  // grid covers rows exactly
-    const u64* base = vals + (u64)proof * val_stride;
-    u64 v[8 * D];
-#pragma unroll
-    for (int k = 0; k < 8; k++)
-#pragma unroll
-        for (int c = 0; c < D; c++)
-            v[k * D + c] = layer_at(base + c * comp_stride, coset_major, logn, logbeta, i + (u64)k * rows);
-    Digest d = b3_hash_elems<8 * D>(v);
-    Digest* nodes = nodes_all + (u64)proof * node_stride;
-    nodes[rows + i] = d;
-    block_tree_up(d, nodes, rows, lds, wmin);
-}
-u64 launch_fri_leaves(const u64* vals, u64 val_stride, u64 comp_stride, bool coset_major, int logn, int logbeta,
-                      u64 rows, Digest* nodes, u64 node_stride, int npoly, int ext, hipStream_t s) {
-    const u64 T = std::min<u64>(256, rows);
-    const int wmin = up_wmin(T);
-    dim3 g((unsigned)(rows / T), npoly);
-    if (ext == 2)
-        hipLaunchKernelGGL(fri_leaves_kernel<2>, g, dim3((unsigned)T), 0, s, vals, val_stride, comp_stride,
-                           coset_major ? 1 : 0, logn, logbeta, rows, nodes, node_stride, wmin);
-    else
-        hipLaunchKernelGGL(fri_leaves_kernel<1>, g, dim3((unsigned)T), 0, s, vals, val_stride, comp_stride,
-                           coset_major ? 1 : 0, logn, logbeta, rows, nodes, node_stride, wmin);
-    XFG_CHECK_LAUNCH();
-    return rows / T * wmin;
 }
 
 // ============================================================================ AIR
@@ -1167,44 +574,6 @@ void launch_fri_fold(const u64* vals, u64 val_stride, u64 comp_stride, bool cose
     dim3 g((unsigned)((rows + threads - 1) / threads), npoly);
     if (ext == 2) hipLaunchKernelGGL(fri_fold_kernel<2>, g, dim3(threads), 0, s, a);
     else hipLaunchKernelGGL(fri_fold_kernel<1>, g, dim3(threads), 0, s, a);
-    XFG_CHECK_LAUNCH();
-}
-
-// ============================================================================ transcript self test
-// AcceptP plus forced rejections: candidate counter c in [1, 256] is rejected when bit c - 1 of
-// rej[4] is set (exercises wave_draw_e's window bookkeeping and its one-at-a-time fallback)
-struct AcceptForced {
-    const u64* rej;
-    __device__ bool operator()(u64 ctr, u64 x, u64 y, int D) const {
-        const bool forced = ctr >= 1 && ctr <= 256 && ((rej[(ctr - 1) >> 6] >> ((ctr - 1) & 63)) & 1);
-        return !forced && AcceptP()(ctr, x, y, D);
-    }
-};
-__global__ __launch_bounds__(64) void coin_draw_test_kernel(DevCoin c0, int k, int D, const u64* rej, u64* out_wave,
-                                                            u64* out_seq, u64* ctr, int* ok) {
-    const AcceptForced acc{rej};
-    DevCoin c = c0;
-    const bool okw = wave_draw_e(c, k, D, out_wave, 2, acc);
-    DevCoin q = c0;
-    bool oks = true;
-    for (int j = 0; j < k; j++) {
-        u64 a[2] = {0, 0};
-        oks &= dev_draw_e(q, a, D, acc);
-        if (threadIdx.x == 0) {
-            out_seq[2 * j] = a[0];
-            out_seq[2 * j + 1] = a[1];
-        }
-    }
-    if (threadIdx.x == 0) {
-        ctr[0] = c.counter;
-        ctr[1] = q.counter;
-        ok[0] = okw;
-        ok[1] = oks;
-    }
-}
-void launch_coin_draw_test(const DevCoin& c0, int k, int ext, const u64* rej, u64* out_wave, u64* out_seq, u64* ctr,
-                           int* ok, hipStream_t s) {
-    hipLaunchKernelGGL(coin_draw_test_kernel, dim3(1), dim3(64), 0, s, c0, k, ext, rej, out_wave, out_seq, ctr, ok);
     XFG_CHECK_LAUNCH();
 }
 

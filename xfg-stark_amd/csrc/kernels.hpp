@@ -80,7 +80,7 @@ struct DevCoin {
     u64 counter;
     u64 pad;
 };
-// step run on a Merkle root by launch_tree_top: reseed with the root, then
+// step run on a Merkle root by launch_merkle_lde / launch_merkle_fri: reseed with the root, then
 //   COEFFS (trace root): the 15 composition coefficients -> out = coeffs [B][15][D]
 //   OOD_POINT (composition root): z -> out = zpts [B][2][D] = (z, z g)
 //   FRI_ALPHA (FRI layer root): alpha -> out = alpha7 [B][D] = alpha * 7^-1
@@ -105,31 +105,23 @@ struct DeepCoinStep {
     u64 ginv = 0;  // g^-1
 };
 
-// self test of the draw paths (xfg_debug_coin_draws): from coin c0, k <= 64 draws by one wave
-// (out_wave) and one at a time (out_seq), both [k][2]; counters after each in ctr[2], success in ok[2]
-void launch_coin_draw_test(const DevCoin& c0, int k, int ext, const u64* rej, u64* out_wave, u64* out_seq, u64* ctr,
-                           int* ok, hipStream_t s);
-
-// ---- Merkle (heap layout: nodes[1] = root, nodes[L + i] = leaf i) ----
-// LDE commitments store levels >= log2(beta) + 1 only: node_stride >= 2n; the subtree over rows
-// (2j, 2j+1) tops out at heap node n/2 + j; launch_tree_top(nodes, stride, n / 2, ...) finishes
-// also merges each block's nodes a few levels up; returns the node count of the highest level
-// written (finish with launch_tree_top(nodes, stride, returned count, ...))
-u64 launch_leaves_lde(const u64* lde, int nc, Digest* nodes, u64 node_stride, int npoly, int logn, int logbeta,
-                      hipStream_t s);
+// ---- Merkle (merkle.hip; heap layout: nodes[1] = root, nodes[L + i] = leaf i) ----
+// A commitment is one call: the leaves, every level above them up to the root, then the transcript
+// step `cs` on the root. Which kernels run, and the level each stops at, is merkle.hip's business.
+// LDE commitment of npoly trees over lde [npoly][nc][beta][n] (coset-major): nodes [npoly][2n], of which
+// the levels from the row pairs up are stored (heap [1, n)); the subtree over the beta leaves of row m
+// tops out at heap node n + m and stays in registers. nc in {1, 2, 7}, beta in {2, 4, 8, 16}: any
+// other pair throws std::invalid_argument
+void launch_merkle_lde(const u64* lde, int nc, Digest* nodes, int npoly, int logn, int logbeta, hipStream_t s,
+                       const CoinStep& cs = CoinStep{});
 // recompute the local subtree heap (2 * beta digests, slot 1 = top, leaf t at beta + t) of LDE
 // rows entries[e] = proof << logn | m, for Merkle openings
 void launch_open_rows(const u64* lde, int nc, const u64* entries, u64 count, Digest* out, int logn, int logbeta,
                       hipStream_t s);
-// FRI layer leaves: row i = values at natural indices i + k*rows, k < 8 (coset-major source when
-// coset_major, else natural); all leaves stored at nodes[rows + i]
-// (returns the node count left for launch_tree_top, like launch_leaves_lde)
-u64 launch_fri_leaves(const u64* vals, u64 val_stride, u64 comp_stride, bool coset_major, int logn, int logbeta,
-                      u64 rows, Digest* nodes, u64 node_stride, int npoly, int ext, hipStream_t s);
-// completes the tree above level `count` (nodes [count, 2count) present) up to the root, then runs
-// the transcript step `cs` on it
-void launch_tree_top(Digest* nodes, u64 node_stride, u64 count, int npoly, hipStream_t s,
-                     const CoinStep& cs = CoinStep{});
+// FRI layer commitment: leaf i = values at natural indices i + k*rows, k < 8 (coset-major source when
+// coset_major, else natural); nodes [npoly][2 rows], every level stored (leaves at nodes[rows + i])
+void launch_merkle_fri(const u64* vals, u64 val_stride, u64 comp_stride, bool coset_major, int logn, int logbeta,
+                       u64 rows, Digest* nodes, int npoly, int ext, hipStream_t s, const CoinStep& cs = CoinStep{});
 
 // ---- AIR ----
 void launch_trace_gen(const AirConst* air, u64* trace, int logn, int npoly, hipStream_t s);
@@ -150,6 +142,12 @@ void launch_deep(const u64* coef, const u64* hcoef, const DeepParams* dp, const 
                  int logn, int npoly, int ext, hipStream_t s);
 
 // ---- FRI ----
+// FRI layer value at natural index K of a layer stored coset-major (layer 0) or natural
+__device__ __forceinline__ u64 layer_at(const u64* base, bool coset_major, int logn, int logbeta, u64 K) {
+    if (!coset_major) return base[K];
+    u64 t = K & ((1ULL << logbeta) - 1), m = K >> logbeta;
+    return base[(t << logn) + m];
+}
 // alpha7 [B][D] = alpha * 7^-1; E values as D planes comp_stride apart; out planes [B][D][out_stride]
 void launch_fri_fold(const u64* vals, u64 val_stride, u64 comp_stride, bool coset_major, int logn, int logbeta,
                      u64 rows, int logD, const u64* alpha7, u64* out, u64 out_stride, const Tables& T, int npoly,

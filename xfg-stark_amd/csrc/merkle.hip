@@ -1,0 +1,367 @@
+// Merkle commitments (RowMatrix::commit_to_rows / MerkleTree::new, FriProver's layer commitments) for
+// gfx950: the leaf kernels, the tree levels above them, the transcript step on the root and the
+// recomputation of opened rows.
+//
+// Heap layout per tree: nodes[1] = root, nodes[i] = H(nodes[2i] || nodes[2i+1]), leaf k at L + k
+// (MerkleTree::new / build_merkle_nodes, winter-crypto 0.8.3). For the LDE commitments only the
+// levels >= log2(beta) + 1 are stored (heap [1, n)): the 2^log2(beta) leaves of LDE row m (one per
+// coset, coset-major layout) form a register-resident subtree whose top is heap node n + m. The
+// few leaves / low nodes a proof opens are recomputed from the LDE by open_rows_kernel. A tree of
+// L leaf slots lives in 2 L digests (node stride 2n for an LDE, 2 rows for a FRI layer).
+//
+// A commitment is a leaf kernel, which also merges each block's nodes a few levels up through LDS,
+// then tree_mid / tree_mid4 launches while more than TREE_TOP_MAX nodes are left, then one
+// tree_top block per tree. The route, all of it in launch_merkle_lde / launch_merkle_fri / finish_tree:
+//   LDE leaves   n >= ROW2_MIN_N and npoly n / 256 < ROW2_MAX_BLOCKS: leaves_row2_kernel, else leaves_row_kernel
+//   middle       (count / 512) npoly < MID4_MAX_BLOCKS: tree_mid4_kernel, else tree_mid_kernel
+#include "dev_coin.hpp"
+#include <algorithm>
+#include <stdexcept>
+#include <type_traits>
+
+namespace xfg {
+
+#define XFG_CHECK_LAUNCH() (void)hipGetLastError()
+
+// ---- routing thresholds
+// leaves_row2_kernel (LEAF_LANES lanes per row) serves small launch sets, under one wave per SIMD of
+// one-lane-per-row blocks (a lone proof), of trees with at least four whole blocks of rows
+constexpr u64 ROW2_MIN_N = 1024, ROW2_MAX_BLOCKS = 1024;
+constexpr int LEAF_LANES_LOG = 1;  // 2 lanes per row (4: 42.5 + 40.4 against 31.8 + 27.9 µs, profiles/r06/leaves_small_ab.txt)
+// in-block Merkle levels continue while a level keeps >= 64 nodes per block (full waves only); the
+// narrower levels go to the kernels above
+constexpr int UP_WMIN = 64;
+// tree_mid_kernel: 512 nodes in, 64 out per block. (Merging on down to one node per block ran six more
+// levels on one part-filled wave each: 13 wave-compressions per block for the work of 8.)
+constexpr int TREE_MID_WMIN = 64, TREE_MID_SHRINK = 8;
+// tree_mid4_kernel (four lanes per parent) instead, for launch sets under one block per CU
+constexpr u64 MID4_MAX_BLOCKS = 256;
+// tree_top_kernel takes the last levels from here: 512 nodes = 256 parents of four lanes = 1024 threads
+constexpr u64 TREE_TOP_MAX = 512;
+
+// ============================================================================ level helpers
+// One Merkle level through LDS: the threads with `have` hold node `slot` of the block's part of a
+// level in d; after the barrier thread t < half merges nodes 2t, 2t + 1, keeps the parent in d and
+// stores it to dst[t]. The caller places the barrier that frees the LDS for the next level.
+__device__ __forceinline__ void lds_level(Digest& d, bool have, int slot, Digest* lds, int half, Digest* dst) {
+    const int t = threadIdx.x;
+    if (have) lds[slot] = d;
+    __syncthreads();
+    if (t < half) {
+        d = b3_merge(lds[2 * t], lds[2 * t + 1]);
+        dst[t] = d;
+    }
+}
+// Block-level continuation of a Merkle level: thread t of a block of T (power of two) threads
+// holds the digest of node blockIdx.x * T + t of the level with `count` nodes (heap [count,
+// 2 count)). The block merges its T nodes up through LDS, storing every parent, until a level has
+// `wmin` nodes per block (lanes of narrower levels would idle): count / T * wmin nodes are left.
+__device__ __forceinline__ void block_tree_up(Digest d, Digest* nodes, u64 count, Digest* lds, int wmin) {
+    u64 c = count;
+    for (int w = blockDim.x; w > wmin; w >>= 1) {
+        c >>= 1;
+        lds_level(d, true, threadIdx.x, lds, w / 2, nodes + c + (u64)blockIdx.x * (w / 2));
+        __syncthreads();
+    }
+}
+// One level at four lanes per parent (b3_merge_quad): quad i of the active ones (whole quads) merges
+// src[2i], src[2i + 1] and writes the parent, two words per lane, to lds[i] and dst[i]. src may be the
+// LDS of the previous level: every quad has read it before the first barrier.
+__device__ __forceinline__ void quad_level(const Digest* src, bool act, int i, int q, Digest* lds, Digest* dst) {
+    uint2 o = make_uint2(0, 0);
+    if (act) {
+        uint32_t m[16];
+#pragma unroll
+        for (int w = 0; w < 8; w++) {
+            m[w] = src[2 * i].w[w];
+            m[8 + w] = src[2 * i + 1].w[w];
+        }
+        o = b3_merge_quad(m, q);
+    }
+    __syncthreads();
+    if (act) {
+        lds[i].w[q] = o.x;
+        lds[i].w[4 + q] = o.y;
+        dst[i].w[q] = o.x;
+        dst[i].w[4 + q] = o.y;
+    }
+    __syncthreads();
+}
+
+// ============================================================================ LDE leaves
+// subtree over the leaves t = T0 .. T0 + 2^LOG - 1 of LDE row m; compile-time recursion keeps
+// every intermediate digest in registers.
+template <int NC, int LOGB, int LOG, int T0>
+__device__ __forceinline__ Digest lde_subtree(const u64* base, u64 n, u64 m) {
+    if constexpr (LOG == 0) {
+        u64 row[NC];
+#pragma unroll
+        for (int c = 0; c < NC; c++) row[c] = base[((u64)c * (1 << LOGB) + T0) * n + m];
+        return b3_hash_elems<NC>(row);
+    } else {
+        Digest l = lde_subtree<NC, LOGB, LOG - 1, T0>(base, n, m);
+        Digest r = lde_subtree<NC, LOGB, LOG - 1, T0 + (1 << (LOG - 1))>(base, n, m);
+        return b3_merge(l, r);
+    }
+}
+
+// one LDE row per thread, min(256, n) rows per block: the row's 2^LOGB-leaf subtree (top at heap level
+// log2(beta), not stored), then through LDS the row-pair level (heap n/2 + m/2) and one more (n/4 + m/4):
+// 256 rows -> 64 nodes per block, n/4 left for the levels above. Against two rows per thread (the
+// kernel this one replaced) a thread holds one row and one pending digest per subtree level -- 49-56
+// instead of 83-105 VGPRs, 8 instead of 4-5 waves per SIMD -- for the same compressions: the trace
+// leaves 3.3 % faster, the composition leaves unchanged (profiles/r05/leaves_row.txt).
+template <int NC, int LOGB>
+__global__ __launch_bounds__(256) void leaves_row_kernel(const u64* lde, Digest* nodes_all, u64 node_stride,
+                                                         int logn) {
+    __shared__ Digest lds[256];
+    const u64 n = 1ULL << logn;
+    const int proof = blockIdx.y;
+    const u64 m = (u64)blockIdx.x * blockDim.x + threadIdx.x;  // grid covers n exactly
+    const u64* base = lde + (u64)proof * NC * (1 << LOGB) * n;
+    Digest d = lde_subtree<NC, LOGB, LOGB, 0>(base, n, m);
+    block_tree_up(d, nodes_all + (u64)proof * node_stride, n, lds, blockDim.x / 4);
+}
+
+// The same levels for small launch sets (a lone proof: one wave per SIMD, each running the row's
+// 2 beta - 1 compressions in sequence): 2^LOGL lanes per row, each the subtree of beta / 2^LOGL cosets,
+// merged across the lane group (__shfl_xor, every lane of the group merging at every level), then the
+// row-pair level and one more through LDS: 256 / 2^LOGL rows -> a quarter as many nodes per block.
+// 2^LOGL times the waves, and a chain of beta / 2^LOGL + log2 beta + 2 compressions instead of 2 beta + 1.
+template <int LOGB>
+constexpr int leaf_lanes_log() { return LOGB < LEAF_LANES_LOG ? LOGB : LEAF_LANES_LOG; }
+template <int NC, int LOGB>
+__global__ __launch_bounds__(256) void leaves_row2_kernel(const u64* lde, Digest* nodes_all, u64 node_stride,
+                                                          int logn) {
+    constexpr int LOGL = leaf_lanes_log<LOGB>(), RB = 256 >> LOGL;  // lanes per row (log2), rows per block
+    __shared__ Digest lds[RB];
+    const u64 n = 1ULL << logn;
+    const int proof = blockIdx.y, t = threadIdx.x, h = t & ((1 << LOGL) - 1), rl = t >> LOGL;
+    const u64 m = (u64)blockIdx.x * RB + rl;
+    const u64* base = lde + (u64)proof * NC * (1 << LOGB) * n + (u64)h * (1 << (LOGB - LOGL)) * n;
+    Digest d = lde_subtree<NC, LOGB, LOGB - LOGL, 0>(base, n, m);
+#pragma unroll
+    for (int k = 0; k < LOGL; k++) {
+        Digest r;
+#pragma unroll
+        for (int w = 0; w < 8; w++) r.w[w] = __shfl_xor(d.w[w], 1 << k);
+        d = (h >> k) & 1 ? b3_merge(r, d) : b3_merge(d, r);
+    }
+    Digest* nodes = nodes_all + (u64)proof * node_stride;
+    lds_level(d, h == 0, rl, lds, RB / 2, nodes + n / 2 + (u64)blockIdx.x * (RB / 2));
+    __syncthreads();
+    lds_level(d, t < RB / 2, t, lds, RB / 4, nodes + n / 4 + (u64)blockIdx.x * (RB / 4));
+}
+
+// openings: recompute the local subtree heaps of selected rows; entry e = proof << logn | m. One
+// lane per leaf (coset t of row m, 2^LOGB lanes per entry inside a wave): the leaf, then LOGB
+// merge levels with the right child taken from lane l ^ 2^(k-1) -- 1 + LOGB dependent compressions
+// per entry instead of the 2^(LOGB+1) - 1 one lane ran in sequence (a lone proof waits on them).
+// Every lane of a group merges at every level (no divergence around the shuffles); the lanes with
+// t % 2^k == 0 hold level k's nodes and store them to the local heap (slot 1 = top).
+template <int NC, int LOGB>
+__global__ __launch_bounds__(64) void open_rows_kernel(const u64* lde, const u64* entries, u64 count, Digest* out,
+                                                       int logn) {
+    const u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    const u64 e = g >> LOGB;
+    const int t = (int)(g & ((1 << LOGB) - 1));
+    if (e >= count) return;  // whole groups: count is per entry, groups never straddle a wave
+    const u64 n = 1ULL << logn, ent = entries[e];
+    const u64 proof = ent >> logn, m = ent & (n - 1);
+    const u64* base = lde + proof * NC * (1 << LOGB) * n;
+    Digest* local = out + e * (2 << LOGB);
+    u64 row[NC];
+#pragma unroll
+    for (int c = 0; c < NC; c++) row[c] = base[((u64)c * (1 << LOGB) + t) * n + m];
+    Digest d = b3_hash_elems<NC>(row);
+    local[(1 << LOGB) + t] = d;
+#pragma unroll
+    for (int k = 1; k <= LOGB; k++) {
+        Digest r;
+#pragma unroll
+        for (int w = 0; w < 8; w++) r.w[w] = __shfl_xor(d.w[w], 1 << (k - 1));
+        d = b3_merge(d, r);
+        if ((t & ((1 << k) - 1)) == 0) local[((1 << LOGB) + t) >> k] = d;
+    }
+}
+
+// The one (columns, log2 blowup) dispatch of the three kernel families above: f(NC, LOGB) with both as
+// integral constants, for nc in {7, 2, 1} and blowup 2..16. Any other pair has no kernel: refused,
+// never skipped (the ABI entries validate both before anything is launched).
+template <int V>
+using IntC = std::integral_constant<int, V>;
+template <int NC, class F>
+static bool with_logbeta(int logbeta, F f) {
+    switch (logbeta) {
+        case 1: f(IntC<NC>{}, IntC<1>{}); return true;
+        case 2: f(IntC<NC>{}, IntC<2>{}); return true;
+        case 3: f(IntC<NC>{}, IntC<3>{}); return true;
+        case 4: f(IntC<NC>{}, IntC<4>{}); return true;
+        default: return false;
+    }
+}
+template <class F>
+static void with_nc_logbeta(int nc, int logbeta, F f) {
+    const bool found = nc == 7   ? with_logbeta<7>(logbeta, f)
+                       : nc == 2 ? with_logbeta<2>(logbeta, f)
+                       : nc == 1 ? with_logbeta<1>(logbeta, f)
+                                 : false;
+    if (!found) throw std::invalid_argument("Merkle kernels: no instantiation for this column count and blowup");
+}
+
+void launch_open_rows(const u64* lde, int nc, const u64* entries, u64 count, Digest* out, int logn, int logbeta,
+                      hipStream_t s) {
+    if (!count) return;
+    dim3 g((unsigned)(((count << logbeta) + 63) / 64)), b(64);
+    with_nc_logbeta(nc, logbeta, [&](auto NC, auto LB) {
+        hipLaunchKernelGGL((open_rows_kernel<decltype(NC)::value, decltype(LB)::value>), g, b, 0, s, lde, entries, count, out, logn);
+    });
+    XFG_CHECK_LAUNCH();
+}
+
+// ============================================================================ transcript step
+// one wave (all lanes, uniform) of the block that computed proof b's root: reseed with the root,
+// then the draws that follow that commitment in Prover::prove
+__device__ void coin_root_step(const CoinStep& cs, int b, const Digest& root) {
+    const int D = cs.ext, lane = threadIdx.x;
+    DevCoin c = cs.coins[b];
+    dev_reseed(c, root);
+    bool ok;
+    if (cs.kind == CoinStep::COEFFS) {  // 7 transition + 8 boundary composition coefficients
+        ok = wave_draw_e(c, 15, D, cs.out + (u64)b * 15 * D, D);
+    } else {
+        u64 a[2] = {0, 0};
+        ok = dev_draw_e(c, a, D);
+        if (cs.kind == CoinStep::OOD_POINT) {  // z, and z g; z = 0 leaves no DEEP quotient
+            if (a[0] == 0 && a[1] == 0) ok = false;
+            if (lane == 0)
+                for (int k = 0; k < D; k++) {
+                    cs.out[(u64)b * 2 * D + k] = a[k];
+                    cs.out[(u64)b * 2 * D + D + k] = gl_mul(a[k], cs.g);
+                }
+        } else if (lane == 0) {  // FRI layer alpha, stored as alpha * 7^-1 for the fold
+            const u64 inv7 = 0x249249246DB6DB6EULL;
+            for (int k = 0; k < D; k++) cs.out[(u64)b * D + k] = gl_mul(a[k], inv7);
+            if (cs.hist)
+                for (int k = 0; k < D; k++) cs.hist[(u64)b * D + k] = a[k];
+        }
+    }
+    if (lane == 0) {
+        if (!ok) cs.fail[b] = 1;
+        cs.coins[b] = c;
+        if (cs.root_out) cs.root_out[b] = root;
+    }
+}
+
+// ============================================================================ levels above the leaf kernel
+// last levels (count <= TREE_TOP_MAX): one block per tree, four lanes per node, the levels
+// through LDS; then the transcript step `cs` on the root
+__global__ __launch_bounds__(1024) void tree_top_kernel(Digest* nodes_all, u64 node_stride, u64 count, CoinStep cs) {
+    __shared__ Digest lds[256];
+    Digest* nodes = nodes_all + (u64)blockIdx.x * node_stride;
+    const int tid = threadIdx.x, i = tid >> 2, q = tid & 3;
+    for (u64 c = count; c > 1; c >>= 1) {
+        const u64 half = c >> 1;
+        quad_level(c == count ? nodes + c : lds, i < (int)half, i, q, lds, nodes + half);
+    }
+    if (cs.kind != CoinStep::NONE && tid < 64) coin_root_step(cs, blockIdx.x, count > 1 ? lds[0] : nodes[1]);
+}
+// middle levels: a block merges 512 consecutive nodes of level `count` (two per thread, coalesced)
+// and continues through LDS while a level keeps full waves, writing every parent: 64 nodes per block,
+// count / TREE_MID_SHRINK remain.
+__global__ __launch_bounds__(256) void tree_mid_kernel(Digest* nodes_all, u64 node_stride, u64 count) {
+    __shared__ Digest lds[256];
+    Digest* nodes = nodes_all + (u64)blockIdx.y * node_stride;
+    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+    const Digest d = b3_merge(nodes[count + 2 * i], nodes[count + 2 * i + 1]);
+    nodes[count / 2 + i] = d;
+    block_tree_up(d, nodes, count / 2, lds, TREE_MID_WMIN);
+}
+// the same three levels for small launch sets (under one block per CU: a lone proof's trees), four lanes
+// per parent (b3_merge_quad): 128 nodes in, 16 out per block, each level's latency about half
+__global__ __launch_bounds__(256) void tree_mid4_kernel(Digest* nodes_all, u64 node_stride, u64 count) {
+    __shared__ Digest lds[64];
+    Digest* nodes = nodes_all + (u64)blockIdx.y * node_stride;
+    const int tid = threadIdx.x, i = tid >> 2, q = tid & 3;
+    u64 c = count, first = (u64)blockIdx.x * 64;  // level being merged; this block's first parent in it
+    for (int w = 64; w >= 16; w >>= 1, c >>= 1, first >>= 1)
+        quad_level(w == 64 ? nodes + c + 2 * first : lds, i < w, i, q, lds, nodes + c / 2 + first);
+}
+// completes the tree above level `count` (nodes [count, 2 count) present) up to the root, then runs
+// the transcript step `cs` on it
+static void finish_tree(Digest* nodes, u64 node_stride, u64 count, int npoly, hipStream_t s, const CoinStep& cs) {
+    while (count > TREE_TOP_MAX) {
+        if ((count / 512) * (u64)npoly < MID4_MAX_BLOCKS)
+            hipLaunchKernelGGL(tree_mid4_kernel, dim3((unsigned)(count / 128), npoly), dim3(256), 0, s, nodes,
+                               node_stride, count);
+        else
+            hipLaunchKernelGGL(tree_mid_kernel, dim3((unsigned)(count / 512), npoly), dim3(256), 0, s, nodes,
+                               node_stride, count);
+        count /= TREE_MID_SHRINK;
+    }
+    if (count > 1 || cs.kind != CoinStep::NONE) {
+        int threads = (int)(2 * count);  // four lanes per node of the widest level
+        threads = threads < 64 ? 64 : threads;
+        hipLaunchKernelGGL(tree_top_kernel, dim3(npoly), dim3(threads), 0, s, nodes, node_stride, count, cs);
+    }
+    XFG_CHECK_LAUNCH();
+}
+
+void launch_merkle_lde(const u64* lde, int nc, Digest* nodes, int npoly, int logn, int logbeta, hipStream_t s,
+                       const CoinStep& cs) {
+    const u64 n = 1ULL << logn, node_stride = 2 * n;
+    if (n >= ROW2_MIN_N && (u64)npoly * (n / 256) < ROW2_MAX_BLOCKS) {  // under one wave per SIMD
+        const int logl = logbeta < LEAF_LANES_LOG ? logbeta : LEAF_LANES_LOG;
+        dim3 g((unsigned)(n >> (8 - logl)), npoly), b(256);
+        with_nc_logbeta(nc, logbeta, [&](auto NC, auto LB) {
+            hipLaunchKernelGGL((leaves_row2_kernel<decltype(NC)::value, decltype(LB)::value>), g, b, 0, s, lde, nodes, node_stride, logn);
+        });
+    } else {
+        const unsigned T = (unsigned)std::min<u64>(256, n);
+        dim3 g((unsigned)(n / T), npoly), b(T);
+        with_nc_logbeta(nc, logbeta, [&](auto NC, auto LB) {
+            hipLaunchKernelGGL((leaves_row_kernel<decltype(NC)::value, decltype(LB)::value>), g, b, 0, s, lde, nodes, node_stride, logn);
+        });
+    }
+    XFG_CHECK_LAUNCH();
+    finish_tree(nodes, node_stride, n / 4, npoly, s, cs);  // both leaf kernels: the row level and two more
+}
+
+// FRI layer leaves (hash_values::<H, E, 8> over transpose_slice rows): leaf i = H(values at
+// natural indices i + k*rows, k < 8). All leaves are stored (layers are N/8 and smaller).
+// E-valued layers are D coordinate planes `comp_stride` elements apart (per proof: D planes)
+template <int D>
+__global__ __launch_bounds__(256) void fri_leaves_kernel(const u64* vals, u64 val_stride, u64 comp_stride,
+                                                         int coset_major, int logn, int logbeta, u64 rows,
+                                                         Digest* nodes_all, u64 node_stride, int wmin) {
+    __shared__ Digest lds[256];
+    const int proof = blockIdx.y;
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;  // grid covers rows exactly
+    const u64* base = vals + (u64)proof * val_stride;
+    u64 v[8 * D];
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+#pragma unroll
+        for (int c = 0; c < D; c++)
+            v[k * D + c] = layer_at(base + c * comp_stride, coset_major, logn, logbeta, i + (u64)k * rows);
+    Digest d = b3_hash_elems<8 * D>(v);
+    Digest* nodes = nodes_all + (u64)proof * node_stride;
+    nodes[rows + i] = d;
+    block_tree_up(d, nodes, rows, lds, wmin);
+}
+void launch_merkle_fri(const u64* vals, u64 val_stride, u64 comp_stride, bool coset_major, int logn, int logbeta,
+                       u64 rows, Digest* nodes, int npoly, int ext, hipStream_t s, const CoinStep& cs) {
+    const u64 T = std::min<u64>(256, rows), node_stride = 2 * rows;
+    const int wmin = (int)std::min<u64>(T, UP_WMIN);
+    dim3 g((unsigned)(rows / T), npoly);
+    if (ext == 2)
+        hipLaunchKernelGGL(fri_leaves_kernel<2>, g, dim3((unsigned)T), 0, s, vals, val_stride, comp_stride,
+                           coset_major ? 1 : 0, logn, logbeta, rows, nodes, node_stride, wmin);
+    else
+        hipLaunchKernelGGL(fri_leaves_kernel<1>, g, dim3((unsigned)T), 0, s, vals, val_stride, comp_stride,
+                           coset_major ? 1 : 0, logn, logbeta, rows, nodes, node_stride, wmin);
+    XFG_CHECK_LAUNCH();
+    finish_tree(nodes, node_stride, rows / T * wmin, npoly, s, cs);
+}
+
+}  // namespace xfg

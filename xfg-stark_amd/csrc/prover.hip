@@ -288,13 +288,11 @@ static void enqueue_fri_layers(Lane* c, const Tables& T, int B, const ProofShape
         const bool cm = (l == 0);
         const u64* src = cm ? c->f0.p : c->flayer[l].p;
         const u64 cstride = cm ? sh.N : sh.D[l], sstride = DE * cstride;
-        u64 top = launch_fri_leaves(src, sstride, cstride, cm, sh.logn, sh.logbeta, rows, c->fnodes[l].p, 2 * rows, B,
-                                    DE, s);
         cs.kind = CoinStep::FRI_ALPHA;
         cs.out = c->alpha7.p;
         cs.hist = c->falpha.p + (size_t)l * B * DE;  // the raw alpha of this layer, for the replay
         cs.root_out = c->droots.p + (size_t)(2 + l) * B;
-        launch_tree_top(c->fnodes[l].p, 2 * rows, top, B, s, cs);
+        launch_merkle_fri(src, sstride, cstride, cm, sh.logn, sh.logbeta, rows, c->fnodes[l].p, B, DE, s, cs);
         launch_fri_fold(src, sstride, cstride, cm, sh.logn, sh.logbeta, rows, (int)ilog2(sh.D[l]), c->alpha7.p,
                         c->flayer[l + 1].p, rows, T, B, DE, s);
     }
@@ -377,8 +375,7 @@ static ReplayView enqueue_commit_chain(Lane* c, const Tables& T, const u64* ce_d
     cs.kind = CoinStep::COEFFS;
     cs.out = c->coeffs.p;
     cs.root_out = c->droots.p;
-    launch_tree_top(c->tnodes.p, 2 * n, launch_leaves_lde(c->lde.p, 7, c->tnodes.p, 2 * n, B, logn, logbeta, s), B,
-                    s, cs);
+    launch_merkle_lde(c->lde.p, 7, c->tnodes.p, B, logn, logbeta, s, cs);
     stage_mark(c, 2);
     // ---- 3. constraint evaluation + composition polynomial + commitment
     launch_constraint_eval(c->lde.p, c->air.p, c->coeffs.p, ce_div, c->ce.p, logn, logbeta, B, DE, s);
@@ -391,8 +388,7 @@ static ReplayView enqueue_commit_chain(Lane* c, const Tables& T, const u64* ce_d
     cs.out = c->zpts.p;
     cs.root_out = c->droots.p + B;
     cs.g = g;
-    launch_tree_top(c->hnodes.p, 2 * n, launch_leaves_lde(c->hlde.p, DE, c->hnodes.p, 2 * n, B, logn, logbeta, s), B,
-                    s, cs);
+    launch_merkle_lde(c->hlde.p, DE, c->hnodes.p, B, logn, logbeta, s, cs);
     stage_mark(c, 5);
     DeepCoinStep dc;
     dc.coins = c->dcoin.p;

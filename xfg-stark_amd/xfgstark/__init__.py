@@ -102,6 +102,11 @@ if hasattr(_lib, "xfg_debug_field"):  # absent from builds older than the primit
 if hasattr(_lib, "xfg_debug_coin_draws"):  # absent from builds older than the device transcript
     _lib.xfg_debug_coin_draws.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.c_uint32,
                                           _u64p, _u64p, _u64p, _u64p, C.POINTER(C.c_int)]
+if hasattr(_lib, "xfg_debug_merkle_lde"):  # absent from builds older than the whole-heap Merkle test
+    _lib.xfg_debug_merkle_lde.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, _u64p, _u64p,
+                                          C.c_uint64, _u8p, _u8p]
+    _lib.xfg_debug_merkle_fri.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _u64p,
+                                          _u8p]
 
 
 class XfgStarkError(Exception):
@@ -797,6 +802,37 @@ class XfgBurnMintProver:
         if st:
             raise self._err(st)
         return ow, osq, (int(ctr[0]), int(ctr[1])), (ok[0], ok[1])
+
+    def debug_merkle_lde(self, lde, entries=()):
+        """Merkle commitment of LDEs as the prover runs it (xfg_debug_merkle_lde): lde [B,nc,blowup,n]
+        coset-major, entries = proof << log2(n) | row. Returns (heaps [B,2n,8] u32 words -- slots
+        [1, n) defined, the rest 0xFFFFFFFF -- and the opening kernel's local heaps [len(entries),2 blowup,8])"""
+        import numpy as np
+        v = np.ascontiguousarray(lde, dtype=np.uint64)
+        ent = np.ascontiguousarray(entries, dtype=np.uint64)
+        B, nc, blowup, n = v.shape
+        nodes = np.zeros((B, 2 * n, 8), dtype="<u4")
+        local = np.zeros((ent.size, 2 * blowup, 8), dtype="<u4")
+        st = _lib.xfg_debug_merkle_lde(self._ctx, B, nc, n, blowup, v.ctypes.data_as(_u64p), ent.ctypes.data_as(_u64p),
+                                       ent.size, nodes.ctypes.data_as(_u8p), local.ctypes.data_as(_u8p))
+        if st:
+            raise self._err(st)
+        return nodes, local
+
+    def debug_merkle_fri(self, vals, logn, logbeta, coset_major):
+        """Merkle commitment of FRI layers (xfg_debug_merkle_fri): vals as for debug_fri_fold. Returns the
+        heaps [B,2 rows,8] u32 words, rows = 2^(logn + logbeta) / 8 (slot 0: 0xFFFFFFFF)"""
+        import numpy as np
+        v = np.ascontiguousarray(vals, dtype=np.uint64)
+        B, ext, D = v.shape
+        if D != 1 << (logn + logbeta):
+            raise XfgStarkError(9, "debug_merkle_fri: vals [B,ext,2^(logn+logbeta)]")
+        nodes = np.zeros((B, D // 4, 8), dtype="<u4")
+        st = _lib.xfg_debug_merkle_fri(self._ctx, B, ext, logn, logbeta, 1 if coset_major else 0,
+                                       v.ctypes.data_as(_u64p), nodes.ctypes.data_as(_u8p))
+        if st:
+            raise self._err(st)
+        return nodes
 
     def debug_interpolate(self, evals, n, offset7=False):
         import numpy as np
