@@ -46,7 +46,9 @@ typedef enum {
     XFG_ZERO_TX_HASH = 3,        /* u64 LE of tx_prefix_hash[0..8] == 0 */
     XFG_BAD_RECIPIENT_LEN = 4,   /* recipient address not 20 bytes */
     XFG_SHORT_SECRET = 5,        /* secret shorter than 8 bytes (reference: error <4, panic 4..7) */
-    XFG_PROVER_ERROR = 6,        /* Winterfell prover error / unsupported options */
+    XFG_PROVER_ERROR = 6,        /* Winterfell prover error / options outside the supported set (FRI
+                                    folding factor not 2, 4, 8 or 16, a last FRI layer smaller than the
+                                    blowup, an NTT size without a kernel) */
     XFG_DEVICE_ERROR = 7,        /* HIP runtime failure */
     XFG_BUFFER_TOO_SMALL = 8,
     XFG_INVALID_ARGUMENT = 9,
@@ -59,7 +61,7 @@ typedef struct {
     uint32_t blowup_factor;
     uint32_t grinding_factor;
     uint32_t field_extension; /* 1 = FieldExtension::None */
-    uint32_t fri_folding_factor;
+    uint32_t fri_folding_factor; /* 2, 4, 8 or 16 */
     uint32_t fri_remainder_max_degree;
 } xfg_options;
 
@@ -230,6 +232,10 @@ int xfg_debug_constraint_eval(xfg_ctx* ctx, uint32_t count, uint64_t n, uint32_t
  * All inputs canonical; D >= 16 */
 int xfg_debug_fri_fold(xfg_ctx* ctx, uint32_t count, uint32_t ext, uint32_t logn, uint32_t logbeta, int coset_major,
                        const uint64_t* vals, const uint64_t* alpha, uint64_t* out);
+/* the same for folding factor fold = 2, 4, 8 or 16: out [count][ext][D / fold], D >= 2 fold
+ * (xfg_debug_fri_fold is this entry with fold = 8) */
+int xfg_debug_fri_fold_f(xfg_ctx* ctx, uint32_t count, uint32_t ext, uint32_t logn, uint32_t logbeta, int coset_major,
+                         uint32_t fold, const uint64_t* vals, const uint64_t* alpha, uint64_t* out);
 /* device Fiat-Shamir draws (DefaultRandomCoin<Blake3_256>::draw::<E>) from the coin (seed as 8 LE
  * u32 words, counter): k <= 64 draws of E (ext 1 or 2) by one wave -- the prover's coefficient and
  * DEEP draws -- and one at a time -- its FRI alpha draws. Besides the >= p rule, a candidate whose
@@ -254,6 +260,10 @@ int xfg_debug_merkle_lde(xfg_ctx* ctx, uint32_t count, uint32_t nc, uint64_t n, 
  * nodes_out [count][2 rows][32 bytes]: the whole heap, slots [1, 2 rows); slot 0 is 0xFF bytes */
 int xfg_debug_merkle_fri(xfg_ctx* ctx, uint32_t count, uint32_t ext, uint32_t logn, uint32_t logbeta, int coset_major,
                          const uint64_t* vals, uint8_t* nodes_out);
+/* the same for folding factor fold = 2, 4, 8 or 16: leaf i = the fold E values at natural indices
+ * i + k rows, k < fold, rows = D / fold, D >= 2 fold (xfg_debug_merkle_fri is this entry with fold = 8) */
+int xfg_debug_merkle_fri_f(xfg_ctx* ctx, uint32_t count, uint32_t ext, uint32_t logn, uint32_t logbeta, int coset_major,
+                           uint32_t fold, const uint64_t* vals, uint8_t* nodes_out);
 
 #ifdef __cplusplus
 }

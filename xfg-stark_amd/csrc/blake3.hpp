@@ -1,9 +1,11 @@
 // BLAKE3 compression for the Merkle commitments and Fiat-Shamir transcript of the burn-proof
 // STARK (winter-crypto `Blake3_256`, reference src/burn_mint_air.rs:483-485).
-// Everything on the hot path is a single 64-byte-or-shorter block: leaf = one trace row
-// (7 elements = 56 B), FRI leaf = 8 elements (64 B), Merkle node = two digests (64 B),
-// coin step = digest||u64 (40 B). Digests are 8 little-endian u32 words, so field elements map
-// to message words directly (lo, hi) -- no byte shuffling on the GPU.
+// Nearly everything on the hot path is a single 64-byte-or-shorter block: leaf = one trace row
+// (7 elements = 56 B), FRI leaf = 8 elements (64 B) at folding factor 8 in the base field, Merkle
+// node = two digests (64 B), coin step = digest||u64 (40 B); FRI leaves of other factors or of the
+// quadratic extension are 16 to 256 bytes, up to four blocks of one chunk (b3_hash_elems). Digests
+// are 8 little-endian u32 words, so field elements map to message words directly (lo, hi) -- no
+// byte shuffling on the GPU.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -186,10 +188,12 @@ __host__ __device__ __forceinline__ Digest b3_merge(const Digest& a, const Diges
     for (int i = 0; i < 8; i++) { m[i] = a.w[i]; m[8 + i] = b.w[i]; }
     return b3_hash_block(m, 64);
 }
-// Blake3_256::hash_elements for up to 16 field elements (one or two blocks of one chunk)
+// Blake3_256::hash_elements for up to 32 field elements: one to four blocks of one chunk (the FRI
+// leaves of folding factor 16 over the quadratic extension are 256 bytes), CHUNK_START on the first
+// block, CHUNK_END | ROOT on the last
 template <int K>
 __host__ __device__ __forceinline__ Digest b3_hash_elems(const uint64_t* e) {
-    static_assert(K >= 1 && K <= 16, "one- or two-block element hash");
+    static_assert(K >= 1 && K <= 32, "element hash of one to four blocks");
     uint32_t m[16];
     constexpr int K0 = K <= 8 ? K : 8;
 #pragma unroll
@@ -201,17 +205,31 @@ __host__ __device__ __forceinline__ Digest b3_hash_elems(const uint64_t* e) {
     if constexpr (K <= 8) {
         return b3_hash_block<0xFFFFu & ~((1u << (2 * K)) - 1u)>(m, 8 * K);  // words 2K.. are zero
     } else {
+        constexpr int LAST = (K - 1) / 8, KL = K - 8 * LAST;  // index of the last block, its elements
         const uint32_t iv[8] = {XFG_B3_IV};
         uint32_t cv[8];
         b3_compress(iv, m, 64, 0, B3_CHUNK_START, cv);
 #pragma unroll
+        for (int b = 1; b < LAST; b++) {  // whole middle blocks
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                uint64_t v = e[8 * b + i];
+                m[2 * i] = (uint32_t)v;
+                m[2 * i + 1] = (uint32_t)(v >> 32);
+            }
+            uint32_t nx[8];
+            b3_compress(cv, m, 64, 0, 0, nx);
+#pragma unroll
+            for (int i = 0; i < 8; i++) cv[i] = nx[i];
+        }
+#pragma unroll
         for (int i = 0; i < 8; i++) {
-            uint64_t v = 8 + i < K ? e[8 + i] : 0;
+            uint64_t v = i < KL ? e[8 * LAST + i] : 0;
             m[2 * i] = (uint32_t)v;
             m[2 * i + 1] = (uint32_t)(v >> 32);
         }
         Digest d;
-        b3_compress<0xFFFFu & ~((1u << (2 * (K - 8))) - 1u)>(cv, m, 8 * (K - 8), 0, B3_CHUNK_END | B3_ROOT, d.w);
+        b3_compress<0xFFFFu & ~((1u << (2 * KL)) - 1u)>(cv, m, 8 * KL, 0, B3_CHUNK_END | B3_ROOT, d.w);
         return d;
     }
 }

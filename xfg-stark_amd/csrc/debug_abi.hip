@@ -401,19 +401,28 @@ int xfg_debug_constraint_eval(xfg_ctx* c, uint32_t count, uint64_t n, uint32_t b
     });
 }
 
+// log2 of a folding factor the kernels have (2, 4, 8, 16), else 0
+static unsigned debug_logf(uint32_t fold) { return fold == 2 ? 1 : fold == 4 ? 2 : fold == 8 ? 3 : fold == 16 ? 4 : 0; }
+
 int xfg_debug_fri_fold(xfg_ctx* c, uint32_t count, uint32_t ext, uint32_t logn, uint32_t logbeta, int coset_major,
                        const uint64_t* vals, const uint64_t* alpha, uint64_t* out) {
+    return xfg_debug_fri_fold_f(c, count, ext, logn, logbeta, coset_major, 8, vals, alpha, out);
+}
+
+int xfg_debug_fri_fold_f(xfg_ctx* c, uint32_t count, uint32_t ext, uint32_t logn, uint32_t logbeta, int coset_major,
+                         uint32_t fold, const uint64_t* vals, const uint64_t* alpha, uint64_t* out) {
     if (!c) return XFG_INVALID_ARGUMENT;
     c->err.clear();
-    if (!vals || !alpha || !out || count == 0 || (ext != 1 && ext != 2) || logn > 28 || logbeta > 28 ||
-        logn + logbeta < 4 || logn + logbeta > 28) {
+    const unsigned logf = debug_logf(fold);  // D >= 2 fold
+    if (!vals || !alpha || !out || count == 0 || (ext != 1 && ext != 2) || logn > 28 || logbeta > 28 || !logf ||
+        logn + logbeta < logf + 1 || logn + logbeta > 28) {
         c->err = "xfg_debug_fri_fold: null or unsupported argument";
         return XFG_INVALID_ARGUMENT;
     }
     return on_lane0(c, [&](Lane* L) -> int {
         const size_t B = count;
         const int logD = (int)(logn + logbeta);
-        const u64 D = 1ULL << logD, rows = D / 8;
+        const u64 D = 1ULL << logD, rows = D / fold;
         if (!all_canonical(vals, B * ext * D) || !all_canonical(alpha, B * ext)) {
             c->err = "layer value or alpha is not a canonical field element";
             return XFG_INVALID_ARGUMENT;
@@ -431,7 +440,7 @@ int xfg_debug_fri_fold(xfg_ctx* c, uint32_t count, uint32_t ext, uint32_t logn, 
         HIPCHK(hipMemcpy(L->f0.p, vals, B * ext * D * 8, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(L->alpha7.p, a7.data(), a7.size() * 8, hipMemcpyHostToDevice));
         launch_fri_fold(L->f0.p, ext * D, D, coset_major != 0, (int)logn, (int)logbeta, rows, logD, L->alpha7.p,
-                        L->deep.p, rows, T, (int)B, (int)ext, s);
+                        L->deep.p, rows, T, (int)B, (int)ext, (int)fold, s);
         HIPCHK(hipMemcpyAsync(out, L->deep.p, B * ext * rows * 8, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return XFG_OK;
@@ -480,16 +489,22 @@ int xfg_debug_merkle_lde(xfg_ctx* c, uint32_t count, uint32_t nc, uint64_t n, ui
 
 int xfg_debug_merkle_fri(xfg_ctx* c, uint32_t count, uint32_t ext, uint32_t logn, uint32_t logbeta, int coset_major,
                          const uint64_t* vals, uint8_t* nodes_out) {
+    return xfg_debug_merkle_fri_f(c, count, ext, logn, logbeta, coset_major, 8, vals, nodes_out);
+}
+
+int xfg_debug_merkle_fri_f(xfg_ctx* c, uint32_t count, uint32_t ext, uint32_t logn, uint32_t logbeta, int coset_major,
+                           uint32_t fold, const uint64_t* vals, uint8_t* nodes_out) {
     if (!c) return XFG_INVALID_ARGUMENT;
     c->err.clear();
+    const unsigned logf = debug_logf(fold);  // D >= 2 fold
     if (!vals || !nodes_out || count == 0 || count > 0xFFFF || (ext != 1 && ext != 2) || logn > 28 || logbeta > 28 ||
-        logn + logbeta < 4 || logn + logbeta > 28) {
+        !logf || logn + logbeta < logf + 1 || logn + logbeta > 28) {
         c->err = "xfg_debug_merkle_fri: null or unsupported argument";
         return XFG_INVALID_ARGUMENT;
     }
     return on_lane0(c, [&](Lane* L) -> int {
         const size_t B = count;
-        const u64 D = 1ULL << (logn + logbeta), rows = D / 8;
+        const u64 D = 1ULL << (logn + logbeta), rows = D / fold;
         if (!all_canonical(vals, B * ext * D)) {
             c->err = "layer value is not a canonical field element";
             return XFG_INVALID_ARGUMENT;
@@ -500,7 +515,7 @@ int xfg_debug_merkle_fri(xfg_ctx* c, uint32_t count, uint32_t ext, uint32_t logn
         HIPCHK(hipMemcpyAsync(L->f0.p, vals, B * ext * D * 8, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemsetAsync(L->tnodes.p, 0xFF, B * 2 * rows * sizeof(Digest), s));
         launch_merkle_fri(L->f0.p, ext * D, D, coset_major != 0, (int)logn, (int)logbeta, rows, L->tnodes.p, (int)B,
-                          (int)ext, s);
+                          (int)ext, (int)fold, s);
         HIPCHK(hipMemcpyAsync(nodes_out, L->tnodes.p, B * 2 * rows * sizeof(Digest), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return XFG_OK;

@@ -36,7 +36,7 @@ static inline const char* check_options(u64 n, const Opts& o) {
     if (o.q < 1 || o.q > 255) return "number of queries must be in [1, 255]";
     if (o.grind > 32) return "grinding factor cannot be greater than 32";
     if (o.ext != 1 && o.ext != 2) return "field extension must be None (1) or Quadratic (2)";
-    if (o.fold != 8) return "only FRI folding factor 8 is supported by this prover";
+    if (o.fold != 2 && o.fold != 4 && o.fold != 8 && o.fold != 16) return "FRI folding factor must be 2, 4, 8 or 16";
     if (o.remdeg > 255 || !is_pow2(o.remdeg + 1)) return "FRI remainder max degree must be one less than a power of two";
     if (o.q >= n * o.beta) return "number of queries must be smaller than the LDE domain size";
     return nullptr;
@@ -49,6 +49,11 @@ static inline unsigned num_fri_layers(u64 N, const Opts& o) {
         k++;
     }
     return k;
+}
+// size of the last FRI layer (the domain the remainder is interpolated over): N / fold^num_fri_layers
+static inline u64 last_fri_domain(u64 N, const Opts& o) {
+    for (unsigned k = num_fri_layers(N, o); k > 0; k--) N /= o.fold;
+    return N;
 }
 // Context::to_elements (TraceInfo, modulus bytes, options) -- DESIGN.md "Transcript"
 static inline void context_elements(u64 n, const Opts& o, u64* e) {

@@ -6,7 +6,7 @@
 //     8 assertions (:380-395), batch-inverted divisors
 //   - CompositionPoly / DeepCompositionPoly: OOD evaluation, coefficient-domain DEEP combine with
 //     synthetic division expressed as a weighted suffix scan
-//   - FriProver::build_layers: fold-by-8 (apply_drp)
+//   - FriProver::build_layers: fold by 2, 4, 8 or 16 (apply_drp)
 // and the gathers / packing of the openings and the replay block. The LDE is ntt.hip; the Merkle
 // commitments (trace, composition, FRI layers) and the transcript step on their roots are merkle.hip;
 // the device transcript itself is dev_coin.hpp (here: the DEEP draws, deep_coin_block).
@@ -14,6 +14,7 @@
 #include "dev_coin.hpp"
 #include "field_dft.hpp"
 #include <algorithm>
+#include <stdexcept>
 
 namespace xfg {
 
@@ -508,8 +509,9 @@ void launch_deep(const u64* coef, const u64* hcoef, const DeepParams* dp, const 
 }
 
 // ============================================================================ FRI fold
-// apply_drp for folding factor 8 with Winterfell's constant domain offset 7 on every layer:
-// row i = {v_k at 7 w_D^i zeta^k}; c = iDFT_8(v)/8 ; result = sum_j c_j (alpha / (7 w_D^i))^j
+// apply_drp for folding factor F = 2^LOGF (2, 4, 8, 16) with Winterfell's constant domain offset 7 on
+// every layer: row i = {v_k at 7 w_D^i zeta^k}, zeta = w_D^rows = w_F;
+// c = iDFT_F(v)/F ; result = sum_j c_j (alpha / (7 w_D^i))^j
 struct FoldArgs {
     const u64* vals;
     u64 val_stride, comp_stride;
@@ -521,50 +523,61 @@ struct FoldArgs {
     u64 out_stride;
     Tables T;
 };
-template <int D>
+template <int D, int LOGF>
 __global__ __launch_bounds__(256) void fri_fold_kernel(FoldArgs a) {
     using F = FE<D>;
+    constexpr int NF = 1 << LOGF;
     const int proof = blockIdx.y;
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.rows) return;
     const u64* base = a.vals + (u64)proof * a.val_stride;
-    // the size-8 inverse DFT per coordinate (base-field twiddles w_8^-k = powers of two: shifts),
-    // natural order in and out, outputs canonicalised for the Horner adds
-    u64 c[D][8];
+    // the size-F inverse DFT per coordinate (base-field twiddles w_F^-k = powers of two for every
+    // F <= 16: shifts), natural order in and out, outputs canonicalised for the Horner adds
+    u64 c[D][NF];
 #pragma unroll
-    for (int k = 0; k < 8; k++) {
+    for (int k = 0; k < NF; k++) {
         const u64 K = i + (u64)k * a.rows;
         c[0][k] = layer_at(base, a.coset_major, a.logn, a.logbeta, K);
         if constexpr (D == 2) c[1][k] = layer_at(base + a.comp_stride, a.coset_major, a.logn, a.logbeta, K);
     }
-    F v[8];
+    F v[NF];
 #pragma unroll
     for (int d = 0; d < D; d++) {
-        dft_reg<3, true>(c[d]);
+        dft_reg<LOGF, true>(c[d]);
 #pragma unroll
-        for (int k = 0; k < 8; k++) {
+        for (int k = 0; k < NF; k++) {
             if (d == 0) v[k].a = canon(c[d][k]);
             if constexpr (D == 2) if (d == 1) v[k].b = canon(c[d][k]);
         }
     }
     // y = alpha * 7^-1 * w_D^-i ; Horner
     const F y = fe_mulb(F::load(a.alpha7 + (u64)proof * D), tw_ipow(a.T, a.logD, i));
-    F r = v[7];
+    F r = v[NF - 1];
 #pragma unroll
-    for (int j = 6; j >= 0; j--) r = fe_add(fe_mul(r, y), v[j]);
-    // 1/8 = 2^-3 = 2^189 = -2^93
+    for (int j = NF - 2; j >= 0; j--) r = fe_add(fe_mul(r, y), v[j]);
+    // 1/F = 2^-LOGF = 2^(192 - LOGF) = -2^(96 - LOGF)
 #pragma unroll
     for (int d = 0; d < D; d++) {
-        const u64 x = gl_neg(mul_pow2<93>(r.c(d)));
+        const u64 x = gl_neg(mul_pow2<96 - LOGF>(r.c(d)));
         if (d == 0) r.a = x;
         if constexpr (D == 2) if (d == 1) r.b = x;
     }
 #pragma unroll
     for (int c = 0; c < D; c++) a.out[((u64)proof * D + c) * a.out_stride + i] = r.c(c);
 }
+template <int D>
+static void fold_launch(int fold, dim3 g, dim3 b, hipStream_t s, const FoldArgs& a) {
+    switch (fold) {
+        case 2: hipLaunchKernelGGL((fri_fold_kernel<D, 1>), g, b, 0, s, a); break;
+        case 4: hipLaunchKernelGGL((fri_fold_kernel<D, 2>), g, b, 0, s, a); break;
+        case 8: hipLaunchKernelGGL((fri_fold_kernel<D, 3>), g, b, 0, s, a); break;
+        case 16: hipLaunchKernelGGL((fri_fold_kernel<D, 4>), g, b, 0, s, a); break;
+        default: throw std::invalid_argument("FRI fold: no kernel for this folding factor");
+    }
+}
 void launch_fri_fold(const u64* vals, u64 val_stride, u64 comp_stride, bool coset_major, int logn, int logbeta,
                      u64 rows, int logD, const u64* alpha7, u64* out, u64 out_stride, const Tables& T, int npoly,
-                     int ext, hipStream_t s) {
+                     int ext, int fold, hipStream_t s) {
     FoldArgs a;
     a.vals = vals; a.val_stride = val_stride; a.comp_stride = comp_stride; a.coset_major = coset_major ? 1 : 0;
     a.logn = logn; a.logbeta = logbeta; a.rows = rows; a.logD = logD; a.alpha7 = alpha7; a.out = out;
@@ -572,8 +585,8 @@ void launch_fri_fold(const u64* vals, u64 val_stride, u64 comp_stride, bool cose
     a.T = T;
     int threads = rows < 256 ? (int)rows : 256;
     dim3 g((unsigned)((rows + threads - 1) / threads), npoly);
-    if (ext == 2) hipLaunchKernelGGL(fri_fold_kernel<2>, g, dim3(threads), 0, s, a);
-    else hipLaunchKernelGGL(fri_fold_kernel<1>, g, dim3(threads), 0, s, a);
+    if (ext == 2) fold_launch<2>(fold, g, dim3(threads), s, a);
+    else fold_launch<1>(fold, g, dim3(threads), s, a);
     XFG_CHECK_LAUNCH();
 }
 

@@ -118,10 +118,12 @@ void launch_merkle_lde(const u64* lde, int nc, Digest* nodes, int npoly, int log
 // rows entries[e] = proof << logn | m, for Merkle openings
 void launch_open_rows(const u64* lde, int nc, const u64* entries, u64 count, Digest* out, int logn, int logbeta,
                       hipStream_t s);
-// FRI layer commitment: leaf i = values at natural indices i + k*rows, k < 8 (coset-major source when
-// coset_major, else natural); nodes [npoly][2 rows], every level stored (leaves at nodes[rows + i])
+// FRI layer commitment: leaf i = values at natural indices i + k*rows, k < fold (coset-major source when
+// coset_major, else natural); nodes [npoly][2 rows], every level stored (leaves at nodes[rows + i]).
+// fold in {2, 4, 8, 16}, ext in {1, 2}: anything else throws std::invalid_argument
 void launch_merkle_fri(const u64* vals, u64 val_stride, u64 comp_stride, bool coset_major, int logn, int logbeta,
-                       u64 rows, Digest* nodes, int npoly, int ext, hipStream_t s, const CoinStep& cs = CoinStep{});
+                       u64 rows, Digest* nodes, int npoly, int ext, int fold, hipStream_t s,
+                       const CoinStep& cs = CoinStep{});
 
 // ---- AIR ----
 void launch_trace_gen(const AirConst* air, u64* trace, int logn, int npoly, hipStream_t s);
@@ -148,10 +150,11 @@ __device__ __forceinline__ u64 layer_at(const u64* base, bool coset_major, int l
     u64 t = K & ((1ULL << logbeta) - 1), m = K >> logbeta;
     return base[(t << logn) + m];
 }
-// alpha7 [B][D] = alpha * 7^-1; E values as D planes comp_stride apart; out planes [B][D][out_stride]
+// alpha7 [B][D] = alpha * 7^-1; E values as D planes comp_stride apart; out planes [B][D][out_stride];
+// rows = 2^logD / fold, fold in {2, 4, 8, 16} (any other throws std::invalid_argument)
 void launch_fri_fold(const u64* vals, u64 val_stride, u64 comp_stride, bool coset_major, int logn, int logbeta,
                      u64 rows, int logD, const u64* alpha7, u64* out, u64 out_stride, const Tables& T, int npoly,
-                     int ext, hipStream_t s);
+                     int ext, int fold, hipStream_t s);
 
 // ---- openings ----
 // several gathers in one launch: segment k copies src[k][idx[first[k] + j]] to dst[k][j],

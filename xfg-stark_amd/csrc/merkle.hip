@@ -327,39 +327,57 @@ void launch_merkle_lde(const u64* lde, int nc, Digest* nodes, int npoly, int log
     finish_tree(nodes, node_stride, n / 4, npoly, s, cs);  // both leaf kernels: the row level and two more
 }
 
-// FRI layer leaves (hash_values::<H, E, 8> over transpose_slice rows): leaf i = H(values at
-// natural indices i + k*rows, k < 8). All leaves are stored (layers are N/8 and smaller).
+// FRI layer leaves (hash_values::<H, E, F> over transpose_slice rows, F = 2^LOGF the folding factor):
+// leaf i = H(values at natural indices i + k*rows, k < F), 16 to 256 bytes. All leaves are stored
+// (layers are N/F and smaller).
 // E-valued layers are D coordinate planes `comp_stride` elements apart (per proof: D planes)
-template <int D>
+template <int D, int LOGF>
 __global__ __launch_bounds__(256) void fri_leaves_kernel(const u64* vals, u64 val_stride, u64 comp_stride,
                                                          int coset_major, int logn, int logbeta, u64 rows,
                                                          Digest* nodes_all, u64 node_stride, int wmin) {
     __shared__ Digest lds[256];
+    constexpr int NF = 1 << LOGF;
     const int proof = blockIdx.y;
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;  // grid covers rows exactly
     const u64* base = vals + (u64)proof * val_stride;
-    u64 v[8 * D];
+    u64 v[NF * D];
 #pragma unroll
-    for (int k = 0; k < 8; k++)
+    for (int k = 0; k < NF; k++)
 #pragma unroll
         for (int c = 0; c < D; c++)
             v[k * D + c] = layer_at(base + c * comp_stride, coset_major, logn, logbeta, i + (u64)k * rows);
-    Digest d = b3_hash_elems<8 * D>(v);
+    Digest d = b3_hash_elems<NF * D>(v);
     Digest* nodes = nodes_all + (u64)proof * node_stride;
     nodes[rows + i] = d;
     block_tree_up(d, nodes, rows, lds, wmin);
 }
+// f(D, LOGF) as integral constants for ext in {1, 2} and folding factor 2, 4, 8, 16; any other pair has
+// no kernel: refused, never skipped
+template <class F>
+static void with_ext_fold(int ext, int fold, F f) {
+    const int logf = fold == 2 ? 1 : fold == 4 ? 2 : fold == 8 ? 3 : fold == 16 ? 4 : 0;
+    if ((ext != 1 && ext != 2) || !logf)
+        throw std::invalid_argument("FRI leaf kernel: no instantiation for this extension degree and folding factor");
+    auto by_fold = [&](auto DC) {
+        switch (logf) {
+            case 1: f(DC, IntC<1>{}); break;
+            case 2: f(DC, IntC<2>{}); break;
+            case 3: f(DC, IntC<3>{}); break;
+            default: f(DC, IntC<4>{}); break;
+        }
+    };
+    if (ext == 2) by_fold(IntC<2>{});
+    else by_fold(IntC<1>{});
+}
 void launch_merkle_fri(const u64* vals, u64 val_stride, u64 comp_stride, bool coset_major, int logn, int logbeta,
-                       u64 rows, Digest* nodes, int npoly, int ext, hipStream_t s, const CoinStep& cs) {
+                       u64 rows, Digest* nodes, int npoly, int ext, int fold, hipStream_t s, const CoinStep& cs) {
     const u64 T = std::min<u64>(256, rows), node_stride = 2 * rows;
     const int wmin = (int)std::min<u64>(T, UP_WMIN);
     dim3 g((unsigned)(rows / T), npoly);
-    if (ext == 2)
-        hipLaunchKernelGGL(fri_leaves_kernel<2>, g, dim3((unsigned)T), 0, s, vals, val_stride, comp_stride,
-                           coset_major ? 1 : 0, logn, logbeta, rows, nodes, node_stride, wmin);
-    else
-        hipLaunchKernelGGL(fri_leaves_kernel<1>, g, dim3((unsigned)T), 0, s, vals, val_stride, comp_stride,
-                           coset_major ? 1 : 0, logn, logbeta, rows, nodes, node_stride, wmin);
+    with_ext_fold(ext, fold, [&](auto DC, auto LF) {
+        hipLaunchKernelGGL((fri_leaves_kernel<decltype(DC)::value, decltype(LF)::value>), g, dim3((unsigned)T), 0, s, vals,
+                           val_stride, comp_stride, coset_major ? 1 : 0, logn, logbeta, rows, nodes, node_stride, wmin);
+    });
     XFG_CHECK_LAUNCH();
     finish_tree(nodes, node_stride, rows / T * wmin, npoly, s, cs);
 }

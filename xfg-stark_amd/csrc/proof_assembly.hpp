@@ -229,13 +229,13 @@ static inline void plan_queries(ProofJob& j, int b, const ProofShape& sh, const 
     });
     std::vector<u64> fp = pos;
     for (unsigned l = 0; l < nl; l++) {
-        u64 rows = sh.D[l] / 8;
+        u64 rows = sh.D[l] / o.fold;
         fp = fold_positions(fp, rows);
         L.fpos.push_back(fp);
         auto& vf = L.vf[l];
         vf.clear();
         for (u64 i : fp)
-            for (u64 k = 0; k < 8; k++) {
+            for (u64 k = 0; k < o.fold; k++) {
                 const u64 K = i + k * rows;
                 for (int cc = 0; cc < DE; cc++) {
                     if (l == 0)
@@ -328,7 +328,7 @@ static inline void serialize_proof(ProofJob& j, int b, int B, const ProofShape& 
     };
     const u64 nu = j.pos.size();
     BW w(j.bytes);
-    w.reserve(j.commitments.size() + nu * 8 * (7 + DE + 8 * DE * nl) + (2 + nl) * nu * 32 * ilog2(sh.N) +
+    w.reserve(j.commitments.size() + nu * 8 * (7 + DE + o.fold * DE * nl) + (2 + nl) * nu * 32 * ilog2(sh.N) +
               rem_len * 8 * DE + 1024);
     // Context
     w.u8(7); w.u8(0); w.u8(sh.logn); w.u16(0);
@@ -356,8 +356,8 @@ static inline void serialize_proof(ProofJob& j, int b, int B, const ProofShape& 
     w.u8(nl);
     for (unsigned l = 0; l < nl; l++) {
         u64 nk = Lb.fpos[l].size();
-        w.u32(nk * 8 * 8 * DE);
-        w.u64s(&gv[ix.vcur[(size_t)(2 + l) * B + b]], nk * 8 * DE);
+        w.u32(nk * o.fold * 8 * DE);
+        w.u64s(&gv[ix.vcur[(size_t)(2 + l) * B + b]], nk * o.fold * DE);
         write_paths(w, Lb.fops[l], ix.dcur[(size_t)(2 + l) * B + b]);
     }
     w.u16(rem_len * 8 * DE);

@@ -205,9 +205,9 @@ static void size_lane_buffers(Lane* c, size_t B, const ProofShape& sh, const Opt
     // upper bounds once, so steady-state calls never re-allocate (hipHostMalloc would serialise
     // the device and the other lanes)
     const size_t q = o.q, depth = sh.logn + sh.logbeta;
-    const size_t vals = B * q * (7 + DE + 8 * DE * nl);
+    const size_t vals = B * q * (7 + DE + o.fold * DE * nl);
     size_t digs = B * q * 2 * depth;
-    for (unsigned l = 0; l < nl; l++) digs += B * q * ilog2(sh.D[l] / 8);
+    for (unsigned l = 0; l < nl; l++) digs += B * q * ilog2(sh.D[l] / o.fold);
     const size_t opens = B * q * 2 * 2 * 2 * sh.beta;
     c->h_idx.ensure(vals + digs + B * 2 * q);
     c->h_gv.ensure(vals);
@@ -275,16 +275,17 @@ void launch_trace_lde(Lane* c, const Tables& T, int B, const ProofShape& sh, boo
     launch_const_fill(skip, c->trace.p, sh.n, c->coef.p, c->lde.p, B * 7, sh.logn, sh.logbeta, s);
 }
 
-// FRI layers (FriProver::build_layers), folding factor 8: commit -> reseed -> draw alpha -> fold,
+// FRI layers (FriProver::build_layers), folding factor `fold`: commit -> reseed -> draw alpha -> fold,
 // every round on the device; then the remainder: interpolate the last layer over 7*<w_D>, keep
 // D/blowup coefficients (with no folding layer this is the DEEP polynomial's own coefficients),
 // planes [b][c][rem_len]
-static void enqueue_fri_layers(Lane* c, const Tables& T, int B, const ProofShape& sh, CoinStep& cs, HostTrace& ht) {
+static void enqueue_fri_layers(Lane* c, const Tables& T, int B, const ProofShape& sh, int fold, CoinStep& cs,
+                               HostTrace& ht) {
     hipStream_t s = c->stream;
     const int DE = sh.DE;
     const unsigned nl = sh.nl;
     for (unsigned l = 0; l < nl; l++) {
-        const u64 rows = sh.D[l] / 8;
+        const u64 rows = sh.D[l] / fold;
         const bool cm = (l == 0);
         const u64* src = cm ? c->f0.p : c->flayer[l].p;
         const u64 cstride = cm ? sh.N : sh.D[l], sstride = DE * cstride;
@@ -292,9 +293,9 @@ static void enqueue_fri_layers(Lane* c, const Tables& T, int B, const ProofShape
         cs.out = c->alpha7.p;
         cs.hist = c->falpha.p + (size_t)l * B * DE;  // the raw alpha of this layer, for the replay
         cs.root_out = c->droots.p + (size_t)(2 + l) * B;
-        launch_merkle_fri(src, sstride, cstride, cm, sh.logn, sh.logbeta, rows, c->fnodes[l].p, B, DE, s, cs);
+        launch_merkle_fri(src, sstride, cstride, cm, sh.logn, sh.logbeta, rows, c->fnodes[l].p, B, DE, fold, s, cs);
         launch_fri_fold(src, sstride, cstride, cm, sh.logn, sh.logbeta, rows, (int)ilog2(sh.D[l]), c->alpha7.p,
-                        c->flayer[l + 1].p, rows, T, B, DE, s);
+                        c->flayer[l + 1].p, rows, T, B, DE, fold, s);
     }
     ht.mark("chain_launch");
     if (nl > 0) {
@@ -405,7 +406,7 @@ static ReplayView enqueue_commit_chain(Lane* c, const Tables& T, const u64* ce_d
     HIPCHK(hipMemcpy2DAsync(c->dn2.p, 8, c->deep.p + (n - 2), n * 8, 8, (size_t)B * DE, hipMemcpyDeviceToDevice, s));
     stage_mark(c, 7);
     // ---- 6. FRI layers and remainder, then the replay's inputs
-    enqueue_fri_layers(c, T, B, sh, cs, ht);
+    enqueue_fri_layers(c, T, B, sh, (int)o.fold, cs, ht);
     const ReplayView rv = pack_replay_block(c, B, sh);
     stage_mark(c, 8);
     ht.mark("launch_rem");
@@ -853,6 +854,14 @@ static int check_request(xfg_ctx* c, u64 n, const Opts& o) {
         return XFG_PROVER_ERROR;
     }
     const ProofShape sh(n, o);
+    // folding factors 2, 4, 16: a last layer smaller than the blowup leaves the remainder no coefficient
+    // (what factor 8 does on such a shape is as it was)
+    if (o.fold != 8 && sh.D[sh.nl] < sh.beta) {
+        c->err = "Prover error: folding factor " + std::to_string(o.fold) + " takes the " + std::to_string(sh.N) +
+                 "-point LDE domain down to a last FRI layer of " + std::to_string(sh.D[sh.nl]) +
+                 ", smaller than the blowup factor " + std::to_string(sh.beta) + ": the remainder would be empty";
+        return XFG_PROVER_ERROR;
+    }
     const u64 rem = sh.nl > 0 ? sh.D[sh.nl] : 0;  // size the FRI remainder is interpolated at
     const char* what = nullptr;
     u64 size = 0;

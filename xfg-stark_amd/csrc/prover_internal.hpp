@@ -158,7 +158,7 @@ struct xfg_ctx {
     struct {
         xfg::HBuf<uint8_t> stage;  // pinned: proof blob + task lists, one DMA
         xfg::DBuf<uint8_t> dstage;
-        xfg::DBuf<uint32_t> flags;
+        xfg::DBuf<xfg::u64> flags;  // one 64-bit word per proof (verifier.hpp VF_*)
         std::vector<xfg::VState> st;        // per-proof transcript states, reused between calls
         std::vector<xfg::VerifyPlan> frag;  // per-proof plan fragments, reused between calls
     } vb;

@@ -255,23 +255,25 @@ static void air_transition(const AirConst& a, const E2 cur[7], const E2 nxt[7], 
     r[6] = e2_sub(cur[6], e2(a.commitment));
 }
 
-// FRI apply_drp on one row (folding 8, domain offset 7): interpolate the 8 values on the coset
-// x * <w_8> (per coordinate: base-field weights) and evaluate at alpha
-static E2 fold_row(const E2 v[8], u64 x, E2 alpha) {
-    const u64 winv = gl_inv(gl_root(3)), inv8 = gl_inv(8);
-    E2 c[8];
-    for (int k = 0; k < 8; k++) {
+// FRI apply_drp on one row (folding factor F = 2^logf <= 16, domain offset 7): interpolate the F
+// values on the coset x * <w_F> (the size-F inverse DFT scaled by 1 / F, per coordinate: base-field
+// weights) and evaluate at alpha
+static E2 fold_row(const E2* v, unsigned logf, u64 x, E2 alpha) {
+    const int F = 1 << logf;
+    const u64 winv = gl_inv(gl_root(logf)), invf = gl_inv((u64)F);
+    E2 c[16];
+    for (int k = 0; k < F; k++) {
         E2 s{0, 0};
         u64 wk = gl_pow(winv, (u64)k), p = 1;
-        for (int j = 0; j < 8; j++) {
+        for (int j = 0; j < F; j++) {
             s = e2_add(s, e2_mulb(v[j], p));
             p = gl_mul(p, wk);
         }
-        c[k] = e2_mulb(s, inv8);
+        c[k] = e2_mulb(s, invf);
     }
     const E2 t = e2_mulb(alpha, gl_inv(x));
     E2 r{0, 0};
-    for (int k = 7; k >= 0; k--) r = e2_add(e2_mul(r, t), c[k]);
+    for (int k = F - 1; k >= 0; k--) r = e2_add(e2_mul(r, t), c[k]);
     return r;
 }
 // E element i of a span of DE-coordinate elements
@@ -288,6 +290,9 @@ std::string verify_transcript(const uint8_t* bytes, size_t len, const AirConst& 
     if (memcmp(&o, &acceptable, sizeof o)) return "UnacceptableProofOptions";  // AcceptableOptions::OptionSet
     const u64 n = 1ULL << pf.logn;
     if (check_options(n, o)) return "UnacceptableProofOptions";
+    // folding factors 2, 4, 16: options whose last layer is smaller than the blowup leave the remainder no
+    // coefficient (the prover refuses them too, check_request); every layer below then has >= 1 row
+    if (o.fold != 8 && last_fri_domain(n * o.beta, o) < o.beta) return "UnacceptableProofOptions";
     // VerifierChannel::new: the section contents and the element sections are deserialised now
     e = parse_contents(pf);
     if (!e.empty()) return e;
@@ -407,6 +412,9 @@ std::string verify_queries_host(const VState& st) {
     const int de = st.de;
     const u64 N = st.N, beta = st.beta, nu = pf.num_unique, depthN = ilog2(N);
     const unsigned nl = st.nl;
+    const u64 fold = pf.o.fold;  // 2, 4, 8 or 16 (check_options)
+    const unsigned logf = ilog2(fold);
+    const size_t rowb = (size_t)fold * 8 * de;  // bytes of an opened FRI row
     const std::vector<u64>& pos = st.pos;
     const E2 z = st.z, zg = st.zg, hz = st.hz, gam = st.gam;
     const E2* ood = st.ood;
@@ -443,25 +451,25 @@ std::string verify_queries_host(const VState& st) {
     std::vector<u64> cur = pos;
     u64 D = N;
     for (unsigned l = 0; l < nl; l++) {
-        const u64 rows = D / 8;
+        const u64 rows = D / fold;
         std::vector<u64> fp = fold_positions(cur, rows);
         const Span& vals = pf.fri_vals[l];
-        if (vals.n != fp.size() * 64 * de) return "FriVerificationFailed(InvalidLayerCommitment)";
+        if (vals.n != fp.size() * rowb) return "FriVerificationFailed(InvalidLayerCommitment)";
         std::vector<Digest> lv(fp.size());
-        for (size_t i = 0; i < fp.size(); i++) lv[i] = leaf_hash(vals.p + i * 64 * de, 64 * de);
+        for (size_t i = 0; i < fp.size(); i++) lv[i] = leaf_hash(vals.p + i * rowb, rowb);
         if (!batch_root(fp, lv, pf.fri_paths[l], rows, root) || !same(root, pf.com[2 + l]))
             return "FriVerificationFailed(LayerCommitmentMismatch)";
         for (size_t i = 0; i < cur.size(); i++) {
             const u64 ri = cur[i] & (rows - 1), k = cur[i] / rows;
             const size_t at = std::find(fp.begin(), fp.end(), ri) - fp.begin();
-            if (!e2_eq(elem_e(vals, at * 8 + k, de), ev[i])) return "FriVerificationFailed(InvalidLayerFolding)";
+            if (!e2_eq(elem_e(vals, at * fold + k, de), ev[i])) return "FriVerificationFailed(InvalidLayerFolding)";
         }
         const u64 wD = gl_root(ilog2(D));
         std::vector<E2> nev(fp.size());
         for (size_t i = 0; i < fp.size(); i++) {
-            E2 v[8];
-            for (int k = 0; k < 8; k++) v[k] = elem_e(vals, i * 8 + k, de);
-            nev[i] = fold_row(v, gl_mul(GEN, gl_pow(wD, fp[i])), falpha[l]);
+            E2 v[16];
+            for (u64 k = 0; k < fold; k++) v[k] = elem_e(vals, i * fold + k, de);
+            nev[i] = fold_row(v, logf, gl_mul(GEN, gl_pow(wD, fp[i])), falpha[l]);
         }
         cur.swap(fp);
         ev.swap(nev);
@@ -495,6 +503,9 @@ bool plan_proof(const VState& st, size_t blob_off, VerifyPlan& plan, std::string
     const int de = st.de;
     const u64 N = st.N, nu = pf.num_unique;
     const unsigned nl = st.nl;
+    const u64 fold = pf.o.fold;
+    const unsigned logf = ilog2(fold);
+    const size_t rowb = (size_t)fold * 8 * de;  // bytes of an opened FRI row
     plan.trees.clear();
     plan.tleaves.clear();
     plan.vecs.clear();
@@ -512,9 +523,9 @@ bool plan_proof(const VState& st, size_t blob_off, VerifyPlan& plan, std::string
         const std::vector<u64>* cur = &st.pos;
         u64 D = N;
         for (unsigned l = 0; l < nl; l++) {
-            const u64 rows = D / 8;
+            const u64 rows = D / fold;
             fps[l] = fold_positions(*cur, rows);
-            if (pf.fri_vals[l].n != fps[l].size() * 64 * de) {
+            if (pf.fri_vals[l].n != fps[l].size() * rowb) {
                 err = "FriVerificationFailed(InvalidLayerCommitment)";
                 return false;
             }
@@ -530,7 +541,7 @@ bool plan_proof(const VState& st, size_t blob_off, VerifyPlan& plan, std::string
     // one VTree per batch opening: the opened rows sorted by leaf index, the node vectors as the
     // proof holds them; the device checks that they fit the opening (BatchMerkleProof::get_root)
     auto add_tree = [&](const u64* idx, size_t cnt, const Paths& paths, unsigned depth, const uint8_t* row0,
-                        size_t stride, uint32_t words, unsigned com, uint32_t bit) {
+                        size_t stride, uint32_t words, unsigned com, u64 bit) {
         VTree t{};
         t.root_off = off(pf.com_p + 32 * com);
         t.leaf0 = (uint32_t)plan.tleaves.size();
@@ -552,8 +563,8 @@ bool plan_proof(const VState& st, size_t blob_off, VerifyPlan& plan, std::string
     add_tree(st.pos.data(), nu, pf.constraint_paths, depthN, pf.constraint_rows.p, 8 * de, (uint32_t)de, 1,
              VF_CONSTRAINT);
     for (unsigned l = 0; l < nl; l++)
-        add_tree(fps[l].data(), fps[l].size(), pf.fri_paths[l], depthN - 3 * (l + 1), pf.fri_vals[l].p, 64 * de,
-                 (uint32_t)(8 * de), 2 + l, 1u << (VF_LAYER_COMMIT + l));
+        add_tree(fps[l].data(), fps[l].size(), pf.fri_paths[l], depthN - logf * (l + 1), pf.fri_vals[l].p, rowb,
+                 (uint32_t)(fold * de), 2 + l, 1ULL << (VF_LAYER_COMMIT + l));
     // field checks
     VFieldProof& F = plan.fproof;
     F = VFieldProof{};
@@ -576,9 +587,9 @@ bool plan_proof(const VState& st, size_t blob_off, VerifyPlan& plan, std::string
         Q.cons_off = off(pf.constraint_rows.p + i * 8 * de);
         u64 p = st.pos[i], D = N;
         for (unsigned l = 0; l < nl; l++) {
-            const u64 rows = D / 8, r = p & (rows - 1);
+            const u64 rows = D / fold, r = p & (rows - 1);
             const size_t at = std::find(fps[l].begin(), fps[l].end(), r) - fps[l].begin();
-            Q.row_off[l] = off(pf.fri_vals[l].p + at * 64 * de);
+            Q.row_off[l] = off(pf.fri_vals[l].p + at * rowb);
             p = r;
             D = rows;
         }
@@ -587,13 +598,13 @@ bool plan_proof(const VState& st, size_t blob_off, VerifyPlan& plan, std::string
     return true;
 }
 
-std::string finish_proof(const VState& st, uint32_t flags) {
+std::string finish_proof(const VState& st, u64 flags) {
     const ParsedProof& pf = st.pf;
     if (flags & VF_TRACE) return "TraceQueryDoesNotMatchCommitment";
     if (flags & VF_CONSTRAINT) return "ConstraintQueryDoesNotMatchCommitment";
     for (unsigned l = 0; l < st.nl; l++) {
-        if (flags & (1u << (VF_LAYER_COMMIT + l))) return "FriVerificationFailed(LayerCommitmentMismatch)";
-        if (flags & (1u << l)) return "FriVerificationFailed(InvalidLayerFolding)";
+        if (flags & (1ULL << (VF_LAYER_COMMIT + l))) return "FriVerificationFailed(LayerCommitmentMismatch)";
+        if (flags & (1ULL << l)) return "FriVerificationFailed(InvalidLayerFolding)";
     }
     const u64 rl = pf.fri_rem.n / (8 * st.de);
     std::vector<u64> raw(rl * st.de);

@@ -85,18 +85,21 @@ namespace xfg {
 // ---- batched GPU verification: the host replays every transcript and lists, per proof, its 2 + nl
 // batch Merkle openings and its queries; the device then verifies every opening with one workgroup
 // (leaf hashes, BatchMerkleProof::get_root level by level, root comparison: vtree_kernel) and runs
-// the per-query DEEP / FRI / remainder checks (vfield_kernel).
-constexpr int VMAXL = 12;  // FRI layers
-// flags[proof] bits set by the device: 0..11 FRI layer l folding, 16..27 FRI layer l commitment,
-// 29 constraint commitment, 30 trace commitment, 31 remainder folding
-constexpr uint32_t VF_TRACE = 1u << 30, VF_CONSTRAINT = 1u << 29, VF_REMAINDER = 1u << 31;
-constexpr int VF_LAYER_COMMIT = 16;
+// the per-query DEEP / FRI / remainder checks (vfield_kernel<LOGF>; every planned proof has the acceptable
+// options' folding factor `fold`, which launch_verify takes: 2, 4, 8 or 16, anything else throws).
+// FRI layers: N <= 2^25 folded by two down to a last layer of at least 8 is 22
+constexpr int VMAXL = 24;
+// flags[proof] (64 bits) set by the device: 0..23 FRI layer l folding, 32..55 FRI layer l commitment,
+// 61 constraint commitment, 62 trace commitment, 63 remainder folding
+constexpr u64 VF_TRACE = 1ULL << 62, VF_CONSTRAINT = 1ULL << 61, VF_REMAINDER = 1ULL << 63;
+constexpr int VF_LAYER_COMMIT = 32;
 struct VTree {
     u64 root_off;           // blob offset of the commitment the root must equal
     uint32_t leaf0, nidx;   // opened leaves: tleaves[leaf0 .. leaf0 + nidx), sorted by index
     uint32_t vec0, nvec;    // node vectors: vecs[vec0 .. vec0 + nvec), in the proof's order
-    uint32_t words, depth;  // u64 words per leaf (1, 2, 7, 8 or 16); log2 leaves
-    uint32_t proof, bit;    // on failure: flags[proof] |= bit
+    uint32_t words, depth;  // u64 words per leaf (1, 2, 4, 7, 8, 16 or 32); log2 leaves
+    uint32_t proof, pad;
+    u64 bit;                // on failure: flags[proof] |= bit
 };
 struct VTreeLeaf {
     u64 index;    // leaf index
@@ -115,7 +118,7 @@ struct VFieldProof {
 struct VFieldQuery {
     uint32_t proof, pad;
     u64 pos, trace_off, cons_off;
-    u64 row_off[VMAXL];  // layer l: blob offset of the opened row of 8 E values
+    u64 row_off[VMAXL];  // layer l: blob offset of the opened row of `fold` E values
 };
 // one proof's part of a batch (blob offsets already global; tree / vector / proof indices local)
 struct VerifyPlan {
@@ -129,9 +132,9 @@ struct VerifyPlan {
 // a structural error the host verifier reports before any opening is checked
 bool plan_proof(const VState& st, size_t blob_off, VerifyPlan& plan, std::string& err);
 // the host part after the device work: first failing check in the verifier's order, "" if none
-std::string finish_proof(const VState& st, uint32_t flags);
+std::string finish_proof(const VState& st, u64 flags);
 
 void launch_verify(const uint8_t* blob, const VTree* trees, u64 ntrees, const VTreeLeaf* tleaves, const VVec* vecs,
-                   const VFieldProof* fp, const VFieldQuery* fq, u64 nq, uint32_t* flags, hipStream_t s);
+                   const VFieldProof* fp, const VFieldQuery* fq, u64 nq, int fold, u64* flags, hipStream_t s);
 
 }  // namespace xfg

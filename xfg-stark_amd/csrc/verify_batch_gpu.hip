@@ -105,18 +105,19 @@ extern "C" int xfg_verify_batch_gpu(xfg_ctx* c, uint32_t count, const uint8_t* c
             }
         });
         ht.mark("plan_merge");
-        std::vector<uint32_t> flags(E.fp, 0);
+        std::vector<u64> flags(E.fp, 0);
         if (E.fp > 0) {
             hipStream_t s = L0->stream;
             V.dstage.ensure(total_b);
             V.flags.ensure(E.fp);
             HIPCHK(hipMemcpyAsync(V.dstage.p, H, total_b, hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemsetAsync(V.flags.p, 0, E.fp * 4, s));
+            HIPCHK(hipMemsetAsync(V.flags.p, 0, E.fp * 8, s));
             ht.mark("upload_enqueue");
             uint8_t* D = V.dstage.p;
             launch_verify(D + o_blob, (const VTree*)(D + o_t), E.t, (const VTreeLeaf*)(D + o_lf), (const VVec*)(D + o_v),
-                          (const VFieldProof*)(D + o_fp), (const VFieldQuery*)(D + o_fq), E.q, V.flags.p, s);
-            HIPCHK(hipMemcpyAsync(flags.data(), V.flags.p, flags.size() * 4, hipMemcpyDeviceToHost, s));
+                          (const VFieldProof*)(D + o_fp), (const VFieldQuery*)(D + o_fq), E.q, (int)acc.fold, V.flags.p,
+                          s);
+            HIPCHK(hipMemcpyAsync(flags.data(), V.flags.p, flags.size() * 8, hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
             ht.mark("device");
         }

@@ -3,6 +3,8 @@
 // out as flat task lists (verifier.cpp plan_proof); see xfg_verify_batch_gpu in verify_batch_gpu.hip.
 // Replaces the serial BatchBurnMintVerifier loops of the reference (src/burn_mint_verifier.rs:
 // 326-338, 386-408), each of which runs winterfell::verify on the CPU.
+#include <stdexcept>
+
 #include "verifier.hpp"
 
 namespace xfg {
@@ -24,12 +26,14 @@ __device__ __forceinline__ Digest hash_words(const uint8_t* p) {
     return b3_hash_elems<K>(v);
 }
 __device__ Digest hash_row(const uint8_t* p, uint32_t words) {
-    switch (words) {  // trace row 7, constraint value 1 / 2, FRI row 8 / 16
+    switch (words) {  // trace row 7, constraint value 1 / 2, FRI row 2, 4, 8, 16 or 32 (fold x extension degree)
         case 1: return hash_words<1>(p);
         case 2: return hash_words<2>(p);
+        case 4: return hash_words<4>(p);
         case 7: return hash_words<7>(p);
         case 8: return hash_words<8>(p);
-        default: return hash_words<16>(p);
+        case 16: return hash_words<16>(p);
+        default: return hash_words<32>(p);
     }
 }
 __device__ __forceinline__ Digest ld_digest(const uint8_t* p) {
@@ -68,7 +72,7 @@ __device__ __forceinline__ int block_scan(bool f, int* wsum, int& total) {
 // nodes the walk takes (nodes past them are ignored, as winter-crypto 0.8's get_root ignores them:
 // verifier.cpp merkle_symbolic) and the root equals the commitment; else flags[proof] |= bit.
 __global__ __launch_bounds__(256) void vtree_kernel(const uint8_t* blob, const VTree* trees, const VTreeLeaf* tleaves,
-                                                    const VVec* vecs, uint32_t* flags) {
+                                                    const VVec* vecs, u64* flags) {
     __shared__ Digest leaf[512];
     __shared__ Digest dg[2][256];
     __shared__ u64 hx[2][256];
@@ -160,34 +164,38 @@ __global__ __launch_bounds__(256) void vtree_kernel(const uint8_t* blob, const V
         const Digest root = ld_digest(blob + T.root_off);
         bool ok = !bad && nn == 1 && hx[cb][0] == 1;
         for (int w = 0; w < 8; w++) ok = ok && dg[cb][0].w[w] == root.w[w];
-        if (!ok) atomicOr(&flags[T.proof], T.bit);
+        if (!ok) atomicOr((unsigned long long*)&flags[T.proof], (unsigned long long)T.bit);
     }
 }
 
-// apply_drp of one row: iDFT_8 on the coset x<w_8> (per coordinate), evaluate at alpha
-__device__ E2 vfold(const E2 v[8], u64 x, E2 alpha) {
-    const u64 winv = gl_inv(gl_root(3)), inv8 = gl_inv(8);
-    E2 c[8];
-    for (int k = 0; k < 8; k++) {
+// apply_drp of one row of F = 2^LOGF values: iDFT_F on the coset x<w_F> (per coordinate), evaluate at alpha
+template <int LOGF>
+__device__ E2 vfold(const E2* v, u64 x, E2 alpha) {
+    constexpr int F = 1 << LOGF;
+    const u64 winv = gl_inv(gl_root(LOGF)), invf = gl_inv((u64)F);
+    E2 c[F];
+    for (int k = 0; k < F; k++) {
         E2 s{0, 0};
         u64 wk = gl_pow(winv, (u64)k), p = 1;
-        for (int j = 0; j < 8; j++) {
+        for (int j = 0; j < F; j++) {
             s = e2_add(s, e2_mulb(v[j], p));
             p = gl_mul(p, wk);
         }
-        c[k] = e2_mulb(s, inv8);
+        c[k] = e2_mulb(s, invf);
     }
     const E2 t = e2_mulb(alpha, gl_inv(x));
     E2 r{0, 0};
-    for (int k = 7; k >= 0; k--) r = e2_add(e2_mul(r, t), c[k]);
+    for (int k = F - 1; k >= 0; k--) r = e2_add(e2_mul(r, t), c[k]);
     return r;
 }
 
 // one thread per (proof, query): DEEP value at the query point, then every FRI layer's opened value
 // against the running fold, then the remainder polynomial; failures set bits of flags[proof]
-// (bit l: layer l folding, bit 31: remainder)
+// (bit l: layer l folding, VF_REMAINDER: remainder). F = 2^LOGF: the folding factor of every proof of the
+// batch (the acceptable options')
+template <int LOGF>
 __global__ __launch_bounds__(64) void vfield_kernel(const uint8_t* blob, const VFieldProof* fp, const VFieldQuery* fq,
-                                                    u64 nq, uint32_t* flags) {
+                                                    u64 nq, u64* flags) {
     const u64 qi = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (qi >= nq) return;
     const VFieldQuery& Q = fq[qi];
@@ -205,16 +213,17 @@ __global__ __launch_bounds__(64) void vfield_kernel(const uint8_t* blob, const V
     E2 ev = e2_add(e2_mul(s1, izx), e2_mul(s2, izgx));
     ev = e2_add(ev, e2_mul(e2_mul(P.gam, e2_sub(ld_e(blob + Q.cons_off, de), P.hz)), izx));
     u64 D = N, p = Q.pos;
-    uint32_t bad = 0;
+    u64 bad = 0;
+    constexpr int F = 1 << LOGF;
     for (uint32_t l = 0; l < P.nl; l++) {
-        const u64 rows = D / 8, i = p & (rows - 1), k = p / rows;
+        const u64 rows = D / F, i = p & (rows - 1), k = p / rows;
         const uint8_t* row = blob + Q.row_off[l];
-        E2 v[8];
-        for (int j = 0; j < 8; j++) v[j] = ld_e(row + 8 * de * j, de);
-        if (!e2_eq(v[k], ev)) bad |= 1u << l;
+        E2 v[F];
+        for (int j = 0; j < F; j++) v[j] = ld_e(row + 8 * de * j, de);
+        if (!e2_eq(v[k], ev)) bad |= 1ULL << l;
         int logD = 0;
         while ((1ULL << logD) < D) logD++;
-        ev = vfold(v, gl_mul(GEN, gl_pow(gl_root(logD), i)), P.falpha[l]);
+        ev = vfold<LOGF>(v, gl_mul(GEN, gl_pow(gl_root(logD), i)), P.falpha[l]);
         p = i;
         D = rows;
     }
@@ -223,16 +232,23 @@ __global__ __launch_bounds__(64) void vfield_kernel(const uint8_t* blob, const V
     const E2 xr = e2(gl_mul(GEN, gl_pow(gl_root(logD), p)));
     E2 r{0, 0};
     for (uint32_t k = P.rem_len; k-- > 0;) r = e2_add(e2_mul(r, xr), ld_e(blob + P.rem_off + 8 * de * k, de));
-    if (!e2_eq(r, ev)) bad |= 1u << 31;
-    if (bad) atomicOr(&flags[Q.proof], bad);
+    if (!e2_eq(r, ev)) bad |= VF_REMAINDER;
+    if (bad) atomicOr((unsigned long long*)&flags[Q.proof], (unsigned long long)bad);
 }
 
 static unsigned blocks_for(u64 n, unsigned t) { return (unsigned)((n + t - 1) / t); }
 
 void launch_verify(const uint8_t* blob, const VTree* trees, u64 ntrees, const VTreeLeaf* tleaves, const VVec* vecs,
-                   const VFieldProof* fp, const VFieldQuery* fq, u64 nq, uint32_t* flags, hipStream_t s) {
+                   const VFieldProof* fp, const VFieldQuery* fq, u64 nq, int fold, u64* flags, hipStream_t s) {
     if (ntrees) hipLaunchKernelGGL(vtree_kernel, dim3((unsigned)ntrees), dim3(256), 0, s, blob, trees, tleaves, vecs, flags);
-    if (nq) hipLaunchKernelGGL(vfield_kernel, dim3(blocks_for(nq, 64)), dim3(64), 0, s, blob, fp, fq, nq, flags);
+    const dim3 g(blocks_for(nq, 64)), b(64);
+    if (nq) switch (fold) {
+        case 2: hipLaunchKernelGGL(vfield_kernel<1>, g, b, 0, s, blob, fp, fq, nq, flags); break;
+        case 4: hipLaunchKernelGGL(vfield_kernel<2>, g, b, 0, s, blob, fp, fq, nq, flags); break;
+        case 8: hipLaunchKernelGGL(vfield_kernel<3>, g, b, 0, s, blob, fp, fq, nq, flags); break;
+        case 16: hipLaunchKernelGGL(vfield_kernel<4>, g, b, 0, s, blob, fp, fq, nq, flags); break;
+        default: throw std::invalid_argument("batch verifier: no kernel for this folding factor");
+    }
     (void)hipGetLastError();
 }
 

@@ -107,6 +107,11 @@ if hasattr(_lib, "xfg_debug_merkle_lde"):  # absent from builds older than the w
                                           C.c_uint64, _u8p, _u8p]
     _lib.xfg_debug_merkle_fri.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _u64p,
                                           _u8p]
+if hasattr(_lib, "xfg_debug_fri_fold_f"):  # absent from builds older than folding factors 2, 4 and 16
+    _lib.xfg_debug_fri_fold_f.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                          C.c_uint32, _u64p, _u64p, _u64p]
+    _lib.xfg_debug_merkle_fri_f.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                            C.c_uint32, _u64p, _u8p]
 
 
 class XfgStarkError(Exception):
@@ -753,18 +758,21 @@ class XfgBurnMintProver:
             raise self._err(st)
         return ce
 
-    def debug_fri_fold(self, vals, alpha, logn, logbeta, coset_major):
-        """FRI fold kernel (factor 8): vals [B,ext,D] with D = 2^(logn + logbeta), natural order or
-        coset-major (natural index K at (K mod beta) n + K // beta), alpha [B,ext] -> [B,ext,D/8]"""
+    def debug_fri_fold(self, vals, alpha, logn, logbeta, coset_major, fold=8):
+        """FRI fold kernel (folding factor `fold` = 2, 4, 8 or 16): vals [B,ext,D] with D = 2^(logn + logbeta)
+        >= 2 fold, natural order or coset-major (natural index K at (K mod beta) n + K // beta), alpha [B,ext]
+        -> [B,ext,D/fold] (xfg_debug_fri_fold_f, which refuses any other fold or a smaller D)"""
         import numpy as np
         v = np.ascontiguousarray(vals, dtype=np.uint64)
         al = np.ascontiguousarray(alpha, dtype=np.uint64)
         B, ext, D = v.shape
         if D != 1 << (logn + logbeta) or al.shape != (B, ext):
             raise XfgStarkError(9, "debug_fri_fold: vals [B,ext,2^(logn+logbeta)], alpha [B,ext]")
-        out = np.zeros((B, ext, D // 8), dtype=np.uint64)
-        st = _lib.xfg_debug_fri_fold(self._ctx, B, ext, logn, logbeta, 1 if coset_major else 0,
-                                     v.ctypes.data_as(_u64p), al.ctypes.data_as(_u64p), out.ctypes.data_as(_u64p))
+        if not 0 < fold < 1 << 32:
+            raise XfgStarkError(9, "debug_fri_fold: fold is 2, 4, 8 or 16")
+        out = np.zeros((B, ext, D // fold), dtype=np.uint64)
+        st = _lib.xfg_debug_fri_fold_f(self._ctx, B, ext, logn, logbeta, 1 if coset_major else 0, fold,
+                                       v.ctypes.data_as(_u64p), al.ctypes.data_as(_u64p), out.ctypes.data_as(_u64p))
         if st:
             raise self._err(st)
         return out
@@ -819,17 +827,19 @@ class XfgBurnMintProver:
             raise self._err(st)
         return nodes, local
 
-    def debug_merkle_fri(self, vals, logn, logbeta, coset_major):
-        """Merkle commitment of FRI layers (xfg_debug_merkle_fri): vals as for debug_fri_fold. Returns the
-        heaps [B,2 rows,8] u32 words, rows = 2^(logn + logbeta) / 8 (slot 0: 0xFFFFFFFF)"""
+    def debug_merkle_fri(self, vals, logn, logbeta, coset_major, fold=8):
+        """Merkle commitment of FRI layers (xfg_debug_merkle_fri_f): vals and fold as for debug_fri_fold. Returns the heaps [B,2 rows,8] u32 words, rows = 2^(logn + logbeta) / fold
+        (slot 0: 0xFFFFFFFF)"""
         import numpy as np
         v = np.ascontiguousarray(vals, dtype=np.uint64)
         B, ext, D = v.shape
         if D != 1 << (logn + logbeta):
             raise XfgStarkError(9, "debug_merkle_fri: vals [B,ext,2^(logn+logbeta)]")
-        nodes = np.zeros((B, D // 4, 8), dtype="<u4")
-        st = _lib.xfg_debug_merkle_fri(self._ctx, B, ext, logn, logbeta, 1 if coset_major else 0,
-                                       v.ctypes.data_as(_u64p), nodes.ctypes.data_as(_u8p))
+        if not 0 < fold < 1 << 32:
+            raise XfgStarkError(9, "debug_merkle_fri: fold is 2, 4, 8 or 16")
+        nodes = np.zeros((B, 2 * (D // fold), 8), dtype="<u4")
+        st = _lib.xfg_debug_merkle_fri_f(self._ctx, B, ext, logn, logbeta, 1 if coset_major else 0, fold,
+                                         v.ctypes.data_as(_u64p), nodes.ctypes.data_as(_u8p))
         if st:
             raise self._err(st)
         return nodes
