@@ -264,6 +264,14 @@ int xfg_debug_merkle_fri(xfg_ctx* ctx, uint32_t count, uint32_t ext, uint32_t lo
  * i + k rows, k < fold, rows = D / fold, D >= 2 fold (xfg_debug_merkle_fri is this entry with fold = 8) */
 int xfg_debug_merkle_fri_f(xfg_ctx* ctx, uint32_t count, uint32_t ext, uint32_t logn, uint32_t logbeta, int coset_major,
                            uint32_t fold, const uint64_t* vals, uint8_t* nodes_out);
+/* xfg_verify_batch_gpu (the same body, same rules for pending batches) with what the device decided:
+ * flags[i] = the 64-bit word the two verifier kernels set for proof i (bit l < 24: layer l folding,
+ * 32 + l: layer l commitment, 61 / 62: constraint / trace commitment, 63: remainder folding), 0 for a
+ * proof rejected before it was planned; errs + i * err_stride = the VerifierError text of proof i as
+ * xfg_verify reports it ("" when accepted), cut to err_stride - 1 characters */
+int xfg_debug_verify_batch_gpu(xfg_ctx* ctx, uint32_t count, const uint8_t* const* proofs, const size_t* lens,
+                               const xfg_air_consts* airs, const xfg_options* acceptable, int* results,
+                               uint64_t* flags, char* errs, size_t err_stride);
 
 #ifdef __cplusplus
 }

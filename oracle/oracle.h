@@ -19,6 +19,12 @@
  * "parity unpinned" against real Winterfell: the reference cannot be built here (no Rust
  * toolchain) and its prove_burn_mint panics for every input; no reference test
  * holds proof bytes. The corrected-AIR contract is SURVEY.md Appendix A.
+ *
+ * FAULT INJECTION (orc_prove_faulty, test infrastructure only): the same prover body with up to four
+ * algebraic errors, each added before the values it alters are hashed, so the transcript, the Merkle
+ * trees, the grinding and the openings are all consistent with them. Every commitment check of a
+ * verifier then passes and only one algebraic check (DEEP value, a layer's fold, the remainder) can
+ * reject the proof; the verifier tests use it to reach those checks one at a time.
  */
 #ifndef XFG_ORACLE_H
 #define XFG_ORACLE_H
@@ -88,6 +94,20 @@ void orc_build_trace(const orc_air* air, uint64_t n, uint64_t* trace);
  * proof bytes are identical either way. out == NULL -> *out_len = required size. */
 int orc_prove(const orc_air* air, const uint64_t* trace, uint64_t n, const orc_options* opt, int faithful,
               uint8_t* out, size_t* out_len, orc_debug* dbg);
+/* orc_prove (faithful = 0) with `nfaults` <= 4 injected errors; each adds `delta` (an E value, non-zero,
+ * canonical; delta[1] is ignored by base-field proofs) at the place its kind names, before that value
+ * is hashed or committed:
+ *   OOD_NEXT   index = column c < 7: to ood[2c+1] = T_c(z g), which also enters the DEEP construction
+ *   DEEP_COEF  index = j <= n-2: to coefficient j of the finished DEEP polynomial (the caller keeps
+ *              coefficient n-2 non-zero, else the prover's own degree assertion fails)
+ *   LAYER      index = l, 1 <= l < layers: to every value of FRI layer l after it is folded
+ *   REMAINDER  index = k < remainder length: to remainder coefficient k
+ * ORC_PROVER_ERROR for an index out of range, an unknown kind or a zero delta. nfaults == 0 gives
+ * orc_prove's bytes. */
+enum { ORC_FAULT_OOD_NEXT = 1, ORC_FAULT_DEEP_COEF = 2, ORC_FAULT_LAYER = 3, ORC_FAULT_REMAINDER = 4 };
+typedef struct { uint32_t kind; uint32_t index; uint64_t delta[2]; } orc_fault;
+int orc_prove_faulty(const orc_air* air, const uint64_t* trace, uint64_t n, const orc_options* opt,
+                     const orc_fault* faults, uint32_t nfaults, uint8_t* out, size_t* out_len, orc_debug* dbg);
 /* `count` proofs over `threads` OpenMP threads (bench.py's CPU baseline: 1 thread faithful, and all
  * cores); stage_ms[ORC_NSTAGE] = summed CPU ms per stage: trace LDE, trace commitment, constraint
  * evaluation, composition (+ commitment), OOD + DEEP, FRI, grinding + queries, serialisation.

@@ -405,12 +405,26 @@ static void fold_positions(const uint64_t* in, uint64_t k, uint64_t target, uint
 
 /* ============================================================ prover */
 static int orc_prove_quad(const orc_air* air, const uint64_t* trace, uint64_t n, const orc_options* opt, int faithful,
-                          uint8_t* out, size_t* out_len, orc_debug* dbg);
+                          const orc_fault* faults, uint32_t nfaults, uint8_t* out, size_t* out_len, orc_debug* dbg);
 static int orc_verify_quad(const orc_air* air, const uint8_t* proof, size_t len, const orc_options* opt);
-int orc_prove(const orc_air* air, const uint64_t* trace, uint64_t n, const orc_options* opt, int faithful,
-              uint8_t* out, size_t* out_len, orc_debug* dbg) {
+/* fault injection (orc_prove_faulty): the sum of the deltas of the faults of one kind and index; 0 when
+ * there is none (every proof of orc_prove: nfaults == 0) */
+static int fault_delta(const orc_fault* faults, uint32_t nfaults, uint32_t kind, uint32_t index, uint64_t d[2]) {
+    int hit = 0;
+    d[0] = d[1] = 0;
+    for (uint32_t i = 0; i < nfaults; i++)
+        if (faults[i].kind == kind && faults[i].index == index) {
+            d[0] = orc_add(d[0], faults[i].delta[0]);
+            d[1] = orc_add(d[1], faults[i].delta[1]);
+            hit = 1;
+        }
+    return hit;
+}
+static int prove_body(const orc_air* air, const uint64_t* trace, uint64_t n, const orc_options* opt, int faithful,
+                      const orc_fault* faults, uint32_t nfaults, uint8_t* out, size_t* out_len, orc_debug* dbg) {
     if (check_options(n, opt)) return ORC_PROVER_ERROR;
-    if (opt->field_extension == 2) return orc_prove_quad(air, trace, n, opt, faithful, out, out_len, dbg);
+    if (opt->field_extension == 2)
+        return orc_prove_quad(air, trace, n, opt, faithful, faults, nfaults, out, out_len, dbg);
     const uint64_t beta = opt->blowup, N = n * beta, nce = CE_BLOWUP * n, f = opt->fri_folding;
     const uint64_t g = orc_root(ilog2u(n));
     int status = ORC_OK;
@@ -502,6 +516,10 @@ int orc_prove(const orc_air* air, const uint64_t* trace, uint64_t n, const orc_o
         ood[2 * c + 1] = horner(coef + c * n, n, zg);
     }
     hz = horner(hcoef, n, z);
+    for (uint32_t c = 0; c < W; c++) {
+        uint64_t fd[2];
+        if (fault_delta(faults, nfaults, ORC_FAULT_OOD_NEXT, c, fd)) ood[2 * c + 1] = orc_add(ood[2 * c + 1], fd[0]);
+    }
     uint8_t dtmp[32];
     hash_elems(ood, 2 * W, dtmp);
     coin_reseed(&coin, dtmp);
@@ -534,6 +552,8 @@ int orc_prove(const orc_air* air, const uint64_t* trace, uint64_t n, const orc_o
     hcoef[0] = orc_sub(hcoef[0], hz);
     syn_div(hcoef, n, z);
     for (uint64_t j = 0; j < n; j++) t1[j] = orc_add(t1[j], orc_mul(gam, hcoef[j]));
+    for (uint32_t i = 0; i < nfaults; i++)
+        if (faults[i].kind == ORC_FAULT_DEEP_COEF) t1[faults[i].index] = orc_add(t1[faults[i].index], faults[i].delta[0]);
     uint64_t deg = 0;
     for (uint64_t j = 0; j < n; j++) if (t1[j]) deg = j;
     if (deg != n - 2) status = ORC_PROVER_ERROR; /* assert_eq!(trace_length - 2, degree) */
@@ -567,6 +587,9 @@ int orc_prove(const orc_air* air, const uint64_t* trace, uint64_t n, const orc_o
             for (uint64_t k = 0; k < f; k++) v[k] = layer[l][i + k * rows];
             layer[l + 1][i] = fri_fold_row(v, (uint32_t)f, xi, a);
         }
+        uint64_t fd[2];
+        if (fault_delta(faults, nfaults, ORC_FAULT_LAYER, l + 1, fd))
+            for (uint64_t i = 0; i < rows; i++) layer[l + 1][i] = orc_add(layer[l + 1][i], fd[0]);
         D = rows;
     }
     /* remainder: interpolate over 7*<w_D>, keep D/blowup coefficients, commit hash */
@@ -574,6 +597,8 @@ int orc_prove(const orc_air* air, const uint64_t* trace, uint64_t n, const orc_o
     memcpy(rem, layer[nl], D * sizeof(uint64_t));
     orc_interpolate(rem, D, ORC_GEN);
     uint64_t rem_len = D / beta;
+    for (uint32_t i = 0; i < nfaults; i++)
+        if (faults[i].kind == ORC_FAULT_REMAINDER) rem[faults[i].index] = orc_add(rem[faults[i].index], faults[i].delta[0]);
     hash_elems(rem, rem_len, dtmp);
     bb_put(&commitments, dtmp, 32);
     coin_reseed(&coin, dtmp);
@@ -667,6 +692,34 @@ int orc_prove(const orc_air* air, const uint64_t* trace, uint64_t n, const orc_o
     free(t1); free(t2); free(hcoef); free(hlde); free(ce); free(leaves); free(coef); free(lde);
     mtree_free(&ttree); mtree_free(&htree);
     return status;
+}
+int orc_prove(const orc_air* air, const uint64_t* trace, uint64_t n, const orc_options* opt, int faithful,
+              uint8_t* out, size_t* out_len, orc_debug* dbg) {
+    return prove_body(air, trace, n, opt, faithful, NULL, 0, out, out_len, dbg);
+}
+/* the cheating prover of the verifier tests: every fault is applied before the altered values are
+ * hashed, so the transcript, the commitments, the grinding and the openings all follow from them */
+int orc_prove_faulty(const orc_air* air, const uint64_t* trace, uint64_t n, const orc_options* opt,
+                     const orc_fault* faults, uint32_t nfaults, uint8_t* out, size_t* out_len, orc_debug* dbg) {
+    if (check_options(n, opt) || nfaults > 4 || (nfaults && !faults)) return ORC_PROVER_ERROR;
+    const uint64_t N = n * opt->blowup;
+    uint32_t nl = num_fri_layers(N, opt);
+    uint64_t D = N;
+    for (uint32_t l = 0; l < nl; l++) D /= opt->fri_folding;
+    const uint64_t rem_len = D / opt->blowup;
+    for (uint32_t i = 0; i < nfaults; i++) {
+        const orc_fault* ft = &faults[i];
+        const uint64_t d1 = opt->field_extension == 2 ? ft->delta[1] : 0;
+        if (ft->delta[0] >= ORC_P || d1 >= ORC_P || (ft->delta[0] == 0 && d1 == 0)) return ORC_PROVER_ERROR;
+        switch (ft->kind) {
+            case ORC_FAULT_OOD_NEXT: if (ft->index >= W) return ORC_PROVER_ERROR; break;
+            case ORC_FAULT_DEEP_COEF: if (ft->index > n - 2) return ORC_PROVER_ERROR; break;
+            case ORC_FAULT_LAYER: if (ft->index < 1 || ft->index >= nl) return ORC_PROVER_ERROR; break;
+            case ORC_FAULT_REMAINDER: if (ft->index >= rem_len) return ORC_PROVER_ERROR; break;
+            default: return ORC_PROVER_ERROR;
+        }
+    }
+    return prove_body(air, trace, n, opt, 0, faults, nfaults, out, out_len, dbg);
 }
 
 /* CPU baseline driver (bench.py cpu_baseline): `count` independent proofs over `threads` OpenMP
@@ -1079,7 +1132,7 @@ static void air_transition_q(const orc_air* air, const fq cur[7], const fq nxt[7
 }
 
 static int orc_prove_quad(const orc_air* air, const uint64_t* trace, uint64_t n, const orc_options* opt, int faithful,
-                          uint8_t* out, size_t* out_len, orc_debug* dbg) {
+                          const orc_fault* faults, uint32_t nfaults, uint8_t* out, size_t* out_len, orc_debug* dbg) {
     const uint64_t beta = opt->blowup, N = n * beta, nce = CE_BLOWUP * n, f = opt->fri_folding;
     const uint64_t g = orc_root(ilog2u(n));
     int status = ORC_OK;
@@ -1159,6 +1212,11 @@ static int orc_prove_quad(const orc_air* air, const uint64_t* trace, uint64_t n,
         ood[2 * c + 1] = horner_bq(coef + c * n, n, zg);
     }
     hz = horner_q(hcoef, n, z);
+    for (uint32_t c = 0; c < W; c++) {
+        uint64_t fd[2];
+        if (fault_delta(faults, nfaults, ORC_FAULT_OOD_NEXT, c, fd))
+            ood[2 * c + 1] = fq_add(ood[2 * c + 1], fq_make(fd[0], fd[1]));
+    }
     uint8_t dtmp[32];
     hash_fq(ood, 2 * W, dtmp);
     coin_reseed(&coin, dtmp);
@@ -1191,6 +1249,9 @@ static int orc_prove_quad(const orc_air* air, const uint64_t* trace, uint64_t n,
     hcoef[0] = fq_sub(hcoef[0], hz);
     syn_div_q(hcoef, n, z);
     for (uint64_t j = 0; j < n; j++) t1[j] = fq_add(t1[j], fq_mul(gam, hcoef[j]));
+    for (uint32_t i = 0; i < nfaults; i++)
+        if (faults[i].kind == ORC_FAULT_DEEP_COEF)
+            t1[faults[i].index] = fq_add(t1[faults[i].index], fq_make(faults[i].delta[0], faults[i].delta[1]));
     uint64_t deg = 0;
     for (uint64_t j = 0; j < n; j++) if (!fq_is_zero(t1[j])) deg = j;
     if (deg != n - 2) status = ORC_PROVER_ERROR;
@@ -1222,12 +1283,18 @@ static int orc_prove_quad(const orc_air* air, const uint64_t* trace, uint64_t n,
             for (uint64_t k = 0; k < f; k++) v[k] = layer[l][i + k * rows];
             layer[l + 1][i] = fri_fold_row_q(v, (uint32_t)f, xi, a);
         }
+        uint64_t fd[2];
+        if (fault_delta(faults, nfaults, ORC_FAULT_LAYER, l + 1, fd))
+            for (uint64_t i = 0; i < rows; i++) layer[l + 1][i] = fq_add(layer[l + 1][i], fq_make(fd[0], fd[1]));
         D = rows;
     }
     fq* rem = (fq*)malloc(D * sizeof(fq));
     memcpy(rem, layer[nl], D * sizeof(fq));
     interpolate_q(rem, D, ORC_GEN);
     uint64_t rem_len = D / beta;
+    for (uint32_t i = 0; i < nfaults; i++)
+        if (faults[i].kind == ORC_FAULT_REMAINDER)
+            rem[faults[i].index] = fq_add(rem[faults[i].index], fq_make(faults[i].delta[0], faults[i].delta[1]));
     hash_fq(rem, rem_len, dtmp);
     bb_put(&commitments, dtmp, 32);
     coin_reseed(&coin, dtmp);

@@ -29,6 +29,13 @@ class Debug(C.Structure):
                 ("positions", C.c_uint64 * 256)]
 
 
+class Fault(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("index", C.c_uint32), ("delta", C.c_uint64 * 2)]
+
+
+# orc_fault kinds (oracle.h)
+FAULT_OOD_NEXT, FAULT_DEEP_COEF, FAULT_LAYER, FAULT_REMAINDER = 1, 2, 3, 4
+
 REFERENCE_OPTIONS = dict(num_queries=42, blowup=8, grinding=4, field_extension=1, fri_folding=8, fri_rem_max_deg=31)
 
 _lib = None
@@ -59,6 +66,8 @@ def lib():
         L.orc_build_trace.argtypes = [C.POINTER(Air), C.c_uint64, u64p]
         L.orc_prove.argtypes = [C.POINTER(Air), u64p, C.c_uint64, C.POINTER(Options), C.c_int, u8p,
                                 C.POINTER(C.c_size_t), C.POINTER(Debug)]
+        L.orc_prove_faulty.argtypes = [C.POINTER(Air), u64p, C.c_uint64, C.POINTER(Options), C.POINTER(Fault),
+                                       C.c_uint32, u8p, C.POINTER(C.c_size_t), C.POINTER(Debug)]
         L.orc_prove_batch.argtypes = [C.POINTER(Air), C.c_uint32, C.c_uint64, C.POINTER(Options), C.c_int, C.c_int,
                                       C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_double)]
         L.orc_proof_size_bound.restype = C.c_size_t
@@ -118,6 +127,21 @@ def prove(air, n, opts, trace=None, faithful=False, debug=False):
     dbg = Debug() if debug else None
     st = lib().orc_prove(C.byref(air), trace, n, C.byref(opts), 1 if faithful else 0, out, C.byref(ln),
                          C.byref(dbg) if dbg is not None else None)
+    proof = bytes(out[:ln.value]) if st == 0 else None
+    return (st, proof, dbg) if debug else (st, proof)
+
+
+def prove_faulty(air, n, opts, faults, debug=False):
+    """orc_prove_faulty: the cheating prover. faults = [(kind, index, (d0, d1))], at most 4; the injected
+    errors are committed consistently (oracle.h). -> (status, proof) or (status, proof, Debug)"""
+    trace = build_trace(air, n)
+    cap = lib().orc_proof_size_bound(n, C.byref(opts))
+    out = (C.c_uint8 * cap)()
+    ln = C.c_size_t(cap)
+    dbg = Debug() if debug else None
+    arr = (Fault * max(1, len(faults)))(*[Fault(k, i, (C.c_uint64 * 2)(*d)) for k, i, d in faults])
+    st = lib().orc_prove_faulty(C.byref(air), trace, n, C.byref(opts), arr, len(faults), out, C.byref(ln),
+                                C.byref(dbg) if dbg is not None else None)
     proof = bytes(out[:ln.value]) if st == 0 else None
     return (st, proof, dbg) if debug else (st, proof)
 

@@ -1,6 +1,7 @@
 // Host side of the batched GPU verifier (xfg_verify_batch_gpu): transcripts and plans per proof on
 // the host pool (verifier.cpp), one staging upload, the two kernels of verify_kernels.hip on lane
 // 0's stream, verdicts in the host verifier's check order.
+#include <algorithm>
 #include <cstring>
 #include <functional>
 #include <string>
@@ -11,8 +12,11 @@
 
 using namespace xfg;
 
-extern "C" int xfg_verify_batch_gpu(xfg_ctx* c, uint32_t count, const uint8_t* const* proofs, const size_t* lens,
-                                    const xfg_air_consts* airs, const xfg_options* acceptable, int* results) {
+// the body of xfg_verify_batch_gpu and xfg_debug_verify_batch_gpu; flags_out / errs are the debug
+// entry's outputs (null: not wanted)
+static int verify_batch_gpu(xfg_ctx* c, uint32_t count, const uint8_t* const* proofs, const size_t* lens,
+                            const xfg_air_consts* airs, const xfg_options* acceptable, int* results, uint64_t* flags_out,
+                            char* errs, size_t err_stride) {
     if (!c || !proofs || !lens || !airs || !acceptable || !results) return XFG_INVALID_ARGUMENT;
     c->err.clear();
     return on_lane0(c, [&](Lane* L0) -> int {
@@ -125,6 +129,12 @@ extern "C" int xfg_verify_batch_gpu(xfg_ctx* c, uint32_t count, const uint8_t* c
         parallel([&](uint32_t i) {
             if (planned[i] >= 0) err[i] = finish_proof(st[i], flags[planned[i]]);
             results[i] = proofs[i] ? (err[i].empty() ? XFG_OK : XFG_VERIFY_FAILED) : XFG_INVALID_ARGUMENT;
+            if (flags_out) flags_out[i] = planned[i] >= 0 ? flags[planned[i]] : 0;
+            if (errs && err_stride) {
+                const size_t k = std::min(err_stride - 1, err[i].size());
+                memcpy(errs + i * err_stride, err[i].data(), k);
+                errs[i * err_stride + k] = 0;
+            }
         });
         ht.mark("finish");
         ht.dump((int)count);
@@ -132,3 +142,14 @@ extern "C" int xfg_verify_batch_gpu(xfg_ctx* c, uint32_t count, const uint8_t* c
     });
 }
 
+extern "C" int xfg_verify_batch_gpu(xfg_ctx* c, uint32_t count, const uint8_t* const* proofs, const size_t* lens,
+                                    const xfg_air_consts* airs, const xfg_options* acceptable, int* results) {
+    return verify_batch_gpu(c, count, proofs, lens, airs, acceptable, results, nullptr, nullptr, 0);
+}
+
+extern "C" int xfg_debug_verify_batch_gpu(xfg_ctx* c, uint32_t count, const uint8_t* const* proofs, const size_t* lens,
+                                          const xfg_air_consts* airs, const xfg_options* acceptable, int* results,
+                                          uint64_t* flags, char* errs, size_t err_stride) {
+    if (!flags || !errs || !err_stride) return XFG_INVALID_ARGUMENT;
+    return verify_batch_gpu(c, count, proofs, lens, airs, acceptable, results, flags, errs, err_stride);
+}

@@ -77,6 +77,10 @@ _lib.xfg_verify_batch.argtypes = [C.c_uint32, C.POINTER(_u8p), C.POINTER(C.c_siz
                                   C.POINTER(_Options), C.POINTER(C.c_int), C.c_uint32]
 _lib.xfg_verify_batch_gpu.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(_u8p), C.POINTER(C.c_size_t),
                                       C.POINTER(_AirConsts), C.POINTER(_Options), C.POINTER(C.c_int)]
+if hasattr(_lib, "xfg_debug_verify_batch_gpu"):  # absent from builds older than the verifier flag word
+    _lib.xfg_debug_verify_batch_gpu.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(_u8p), C.POINTER(C.c_size_t),
+                                                C.POINTER(_AirConsts), C.POINTER(_Options), C.POINTER(C.c_int),
+                                                _u64p, C.c_char_p, C.c_size_t]
 _lib.xfg_selftest_blake3.argtypes = [_u8p, C.c_size_t, _u8p]
 _lib.xfg_prepare.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(_Options)]
 _lib.xfg_burn_air_consts.argtypes = [C.POINTER(_BurnInputs), C.POINTER(_AirConsts)]
@@ -285,18 +289,10 @@ class XfgBurnMintVerifier:
     def batch_verify(self, proofs_and_airs, threads=0, gpu=None):
         """BatchBurnMintVerifier::verify_batch: list of (proof, air) -> list of bool. Host threads, or
         the GPU of `gpu` (an XfgBurnMintProver context) via xfg_verify_batch_gpu."""
-        import numpy as np
         k = len(proofs_and_airs)
         if k == 0:
             return []
-        datas = [(p.to_bytes() if isinstance(p, StarkProof) else bytes(p)) for p, _ in proofs_and_airs]
-        # statements as one numpy array (per-item ctypes structs dominated large batches)
-        ptrs = (_u8p * k)(*[_bytes_ptr(d) for d in datas])
-        lens = (C.c_size_t * k)(*[len(d) for d in datas])
-        air_np = np.array([list(a[0]) + [a[1], a[2]] for _, a in proofs_and_airs], dtype=np.uint64)
-        airs = air_np.ctypes.data_as(C.POINTER(_AirConsts))
-        res = (C.c_int * k)()
-        o = self.proof_options._c()
+        keep, ptrs, lens, airs, res, o = self._batch_args(proofs_and_airs)
         if gpu is not None:
             st = _lib.xfg_verify_batch_gpu(gpu._ctx, k, ptrs, lens, airs, C.byref(o), res)
             if st:
@@ -306,6 +302,34 @@ class XfgBurnMintVerifier:
         if st:
             raise XfgStarkError(st, STATUS.get(st))
         return [r == 0 for r in res]
+
+    def _batch_args(self, proofs_and_airs):
+        """the C arguments of a batch: (objects to keep alive, proofs, lens, airs, results, options)"""
+        import numpy as np
+        k = len(proofs_and_airs)
+        datas = [(p.to_bytes() if isinstance(p, StarkProof) else bytes(p)) for p, _ in proofs_and_airs]
+        # statements as one numpy array (per-item ctypes structs dominated large batches)
+        ptrs = (_u8p * k)(*[_bytes_ptr(d) for d in datas])
+        lens = (C.c_size_t * k)(*[len(d) for d in datas])
+        air_np = np.array([list(a[0]) + [a[1], a[2]] for _, a in proofs_and_airs], dtype=np.uint64)
+        airs = air_np.ctypes.data_as(C.POINTER(_AirConsts))
+        return (datas, air_np), ptrs, lens, airs, (C.c_int * k)(), self.proof_options._c()
+
+    def debug_batch_verify(self, proofs_and_airs, gpu):
+        """batch_verify(..., gpu=gpu) with what the device decided (xfg_debug_verify_batch_gpu): list of
+        (accepted, flag word the verifier kernels set, error text or None) per item"""
+        k = len(proofs_and_airs)
+        if k == 0:
+            return []
+        keep, ptrs, lens, airs, res, o = self._batch_args(proofs_and_airs)
+        flags = (C.c_uint64 * k)()
+        stride = 256
+        errs = C.create_string_buffer(k * stride)
+        st = _lib.xfg_debug_verify_batch_gpu(gpu._ctx, k, ptrs, lens, airs, C.byref(o), res, flags, errs, stride)
+        if st:
+            raise gpu._err(st)
+        texts = [errs.raw[i * stride:(i + 1) * stride].split(b"\0", 1)[0].decode() for i in range(k)]
+        return [(res[i] == 0, int(flags[i]), texts[i] or None) for i in range(k)]
 
     def verify_all(self, proofs_and_airs, threads=0):
         return all(self.batch_verify(proofs_and_airs, threads))
