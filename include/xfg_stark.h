@@ -48,7 +48,10 @@ typedef enum {
     XFG_SHORT_SECRET = 5,        /* secret shorter than 8 bytes (reference: error <4, panic 4..7) */
     XFG_PROVER_ERROR = 6,        /* Winterfell prover error / options outside the supported set (FRI
                                     folding factor not 2, 4, 8 or 16, a last FRI layer smaller than the
-                                    blowup, an NTT size without a kernel) */
+                                    blowup, an NTT size without a kernel); also a proof whose bounded
+                                    proof-of-work search on the device found no nonce up to
+                                    2^(grinding_factor + 8) ("proof-of-work search exhausted", probability
+                                    e^-256; the other proofs of the batch are unaffected) */
     XFG_DEVICE_ERROR = 7,        /* HIP runtime failure */
     XFG_BUFFER_TOO_SMALL = 8,
     XFG_INVALID_ARGUMENT = 9,
@@ -264,6 +267,14 @@ int xfg_debug_merkle_fri(xfg_ctx* ctx, uint32_t count, uint32_t ext, uint32_t lo
  * i + k rows, k < fold, rows = D / fold, D >= 2 fold (xfg_debug_merkle_fri is this entry with fold = 8) */
 int xfg_debug_merkle_fri_f(xfg_ctx* ctx, uint32_t count, uint32_t ext, uint32_t logn, uint32_t logbeta, int coset_major,
                            uint32_t fold, const uint64_t* vals, uint8_t* nodes_out);
+/* the prover's proof-of-work search alone: for each of count seeds (8 LE u32 words) the smallest nonce
+ * in [first_nonce, max_nonce] whose BLAKE3(seed || nonce_le8) has >= grind trailing zero bits in its
+ * first 8 LE bytes; 0 where there is none. chunk_log / blocks = 0 take grind_plan's values, otherwise
+ * they force the geometry (chunk_log 6..16, blocks 1..4096); max_nonce 0 = the prover's bound */
+int xfg_debug_grind(xfg_ctx* ctx, uint32_t count, const uint32_t* seeds, uint32_t grind, uint64_t first_nonce,
+                    uint64_t max_nonce, uint32_t chunk_log, uint32_t blocks, uint64_t* nonces_out);
+/* GRIND_DEVICE_MIN, and how many proofs' nonces this context has searched on the device / on the host */
+int xfg_grind_probe(const xfg_ctx* ctx, uint32_t* device_min, uint64_t* device_searches, uint64_t* host_searches);
 /* xfg_verify_batch_gpu (the same body, same rules for pending batches) with what the device decided:
  * flags[i] = the 64-bit word the two verifier kernels set for proof i (bit l < 24: layer l folding,
  * 32 + l: layer l commitment, 61 / 62: constraint / trace commitment, 63: remainder folding), 0 for a

@@ -314,6 +314,35 @@ int xfg_debug_coin_draws(xfg_ctx* c, const uint32_t seed[8], uint64_t counter, u
     });
 }
 
+int xfg_debug_grind(xfg_ctx* c, uint32_t count, const uint32_t* seeds, uint32_t grind, uint64_t first_nonce,
+                    uint64_t max_nonce, uint32_t chunk_log, uint32_t blocks, uint64_t* nonces_out) {
+    if (!c || !seeds || !nonces_out || count == 0 || grind > GRIND_MAX || first_nonce == 0 ||
+        (chunk_log != 0 && (chunk_log < GRIND_CHUNK_LOG_MIN || chunk_log > GRIND_CHUNK_LOG_MAX)) ||
+        blocks > GRIND_FORCED_BLOCKS_MAX)
+        return XFG_INVALID_ARGUMENT;
+    return on_lane0(c, [&](Lane* L) -> int {
+        const GrindPlan gp = grind_plan(grind, count, (unsigned)L->cus);
+        memcpy(grind_seeds(L, count), seeds, (size_t)count * sizeof(Digest));
+        const u64* got = grind_search(L, (int)count, grind, first_nonce, max_nonce ? max_nonce : gp.max_nonce,
+                                      chunk_log ? chunk_log : gp.chunk_log, blocks ? blocks : gp.blocks);
+        memcpy(nonces_out, got, (size_t)count * 8);
+        return XFG_OK;
+    });
+}
+
+int xfg_grind_probe(const xfg_ctx* c, uint32_t* device_min, uint64_t* device_searches, uint64_t* host_searches) {
+    if (!c) return XFG_INVALID_ARGUMENT;
+    uint64_t dev = 0, host = 0;
+    for (auto& L : c->lanes) {
+        dev += L->grind_dev;
+        host += L->grind_host;
+    }
+    if (device_min) *device_min = GRIND_DEVICE_MIN;
+    if (device_searches) *device_searches = dev;
+    if (host_searches) *host_searches = host;
+    return XFG_OK;
+}
+
 int xfg_debug_ood_deep(xfg_ctx* c, uint32_t count, uint64_t n, const uint64_t* coef, const uint64_t* hcoef,
                        const uint64_t* zpts, const uint64_t* coeffs, uint64_t* ood_out, uint64_t* deep_out) {
     if (!c || !coef || !hcoef || !zpts || !coeffs || !ood_out || !deep_out || !is_pow2(n) || n < 8 || count == 0)

@@ -179,4 +179,13 @@ struct PackSet {
 };
 void launch_pack(const PackSet& p, void* dst, hipStream_t s);
 
+// ---- proof-of-work search (grind.hip) ----
+// out[b] (may be device-mapped pinned host memory) = the smallest nonce in [first, max_nonce] for which
+// BLAKE3(seeds[b] || nonce_le8) has >= grind (<= 32) trailing zero bits in its first 8 LE bytes, 0 where
+// there is none. state: grind_state_words(B) words of device memory, set here (two memsets on s).
+// chunk_log, blocks: grind_plan (grind_plan.hpp) or forced; the block size follows from chunk_log
+constexpr size_t grind_state_words(size_t B) { return 2 * ((B + 1) & ~(size_t)1); }  // best, next_chunk: 16 B multiples
+void launch_grind(const Digest* seeds, u64* state, u64* out, unsigned B, unsigned grind, u64 first, u64 max_nonce,
+                  unsigned chunk_log, unsigned blocks, hipStream_t s);
+
 }  // namespace xfg

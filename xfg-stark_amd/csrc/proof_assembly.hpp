@@ -39,6 +39,7 @@ struct ProofJob {
     std::vector<u64> pos;
     std::vector<uint8_t> bytes;
     int status = XFG_OK;
+    bool pow_exhausted = false;  // status XFG_PROVER_ERROR because the bounded device search found no nonce
 };
 
 // ------------------------------------------------------------------ byte writer
@@ -156,15 +157,14 @@ static inline void replay_transcript(ProofJob& j, int b, int B, const ProofShape
     if (failed != (rv.ffail[b] != 0) || !same) throw std::runtime_error("device / host transcript diverged");
 }
 
-// degree check, remainder commitment, grinding, query positions, and proof b's gather lists:
-// LDE trees store heap levels >= log2(beta) (indices < 2n); lower nodes of an opened row are
-// recomputed by launch_open_rows (local heap: 2 * beta slots per row)
-static inline void plan_queries(ProofJob& j, int b, const ProofShape& sh, const Opts& o, const ReplayView& rv,
-                                LaneLayout& L) {
-    const u64 n = sh.n, beta = sh.beta, N = sh.N, rem_len = sh.rem_len;
-    const int DE = sh.DE, logn = sh.logn, logbeta = sh.logbeta;
+// plan_queries in three steps, so that the prover can put the device's proof-of-work search
+// (grind.hip, from GRIND_DEVICE_MIN on) in the place of the host's:
+// (a) plan_commit_remainder: degree check, remainder commitment, reseed -- j.coin.seed is then the seed
+//     the nonce is searched for
+static inline void plan_commit_remainder(ProofJob& j, int b, const ProofShape& sh, const ReplayView& rv, LaneLayout& L) {
+    const u64 rem_len = sh.rem_len;
+    const int DE = sh.DE;
     const unsigned nl = sh.nl;
-    const u64 stored_lim = n, LB = beta;  // stored: heap levels >= log2(beta) + 1
     L.ref.clear();
     L.fops.clear();
     L.fpos.clear();
@@ -181,10 +181,26 @@ static inline void plan_queries(ProofJob& j, int b, const ProofShape& sh, const 
     digest_bytes(rc, rb);
     j.commitments.insert(j.commitments.end(), rb, rb + 32);
     j.coin.reseed(rc);
+}
+// trailing zero bits of the first 8 LE bytes of BLAKE3(seed || nonce_le8): a nonce passes with >= grind
+static inline unsigned pow_zeros(const Digest& seed, u64 nonce) {
+    const Digest h = merge_with_int(seed, nonce);
+    return tz64((u64)h.w[0] | ((u64)h.w[1] << 32));
+}
+// the host's search: the smallest nonce >= 1 that passes, one hash at a time
+static inline u64 host_grind(const Digest& seed, u64 grind) {
     u64 nonce = 1;
-    while (tz64([&] { Digest h = merge_with_int(j.coin.seed, nonce); return (u64)h.w[0] | ((u64)h.w[1] << 32); }()) <
-           o.grind)
-        nonce++;
+    while (pow_zeros(seed, nonce) < grind) nonce++;
+    return nonce;
+}
+// (b) plan_openings: the nonce into the transcript, query positions, and proof b's gather lists:
+// LDE trees store heap levels >= log2(beta) (indices < 2n); lower nodes of an opened row are
+// recomputed by launch_open_rows (local heap: 2 * beta slots per row)
+static inline void plan_openings(ProofJob& j, int b, const ProofShape& sh, const Opts& o, u64 nonce, LaneLayout& L) {
+    const u64 n = sh.n, beta = sh.beta, N = sh.N;
+    const int DE = sh.DE, logn = sh.logn, logbeta = sh.logbeta;
+    const unsigned nl = sh.nl;
+    const u64 stored_lim = n, LB = beta;  // stored: heap levels >= log2(beta) + 1
     j.nonce = nonce;
     j.coin.reseed_int(nonce);
     std::vector<u64> pos(o.q);
@@ -250,6 +266,12 @@ static inline void plan_queries(ProofJob& j, int b, const ProofShape& sh, const 
         df.clear();
         L.fops.back().each([&](u64 x) { df.push_back((u64)b * 2 * rows + x); });
     }
+}
+// degree check, remainder commitment, grinding on the host, query positions, and proof b's gather lists
+static inline void plan_queries(ProofJob& j, int b, const ProofShape& sh, const Opts& o, const ReplayView& rv,
+                                LaneLayout& L) {
+    plan_commit_remainder(j, b, sh, rv, L);
+    plan_openings(j, b, sh, o, host_grind(j.coin.seed, o.grind), L);
 }
 
 // lays the B proofs' gather lists end to end (serial; ix's vectors are the lane's, so steady-state

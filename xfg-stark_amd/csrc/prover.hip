@@ -212,6 +212,7 @@ static void size_lane_buffers(Lane* c, size_t B, const ProofShape& sh, const Opt
     c->h_idx.ensure(vals + digs + B * 2 * q);
     c->h_gv.ensure(vals);
     c->h_gd.ensure(digs + opens);
+    size_grind(c, B);
 }
 
 // the unit's small uploads are copied by a kernel from the pinned, device-mapped host blocks: no
@@ -228,6 +229,27 @@ static void upload(void* dst, const void* host, size_t bytes, hipStream_t s) {
     launch_pack(u, dst, s);
 }
 static_assert(sizeof(AirConst) % 4 == 0 && sizeof(DevCoin) % 4 == 0, "uploads copy 32-bit words");
+
+void size_grind(Lane* c, size_t B) {
+    c->h_gseed.ensure(B);
+    c->h_gnonce.ensure(B);
+    c->gseed.ensure(B);
+    c->gstate.ensure(grind_state_words(B));
+}
+Digest* grind_seeds(Lane* c, size_t B) {
+    size_grind(c, B);
+    return c->h_gseed.p;
+}
+const u64* grind_search(Lane* c, int B, unsigned grind, u64 first, u64 max_nonce, unsigned chunk_log, unsigned blocks) {
+    size_grind(c, B);
+    const hipStream_t s = gather_stream(c);
+    void* out = nullptr;
+    HIPCHK(hipHostGetDevicePointer(&out, c->h_gnonce.p, 0));
+    upload(c->gseed.p, c->h_gseed.p, (size_t)B * sizeof(Digest), s);
+    launch_grind(c->gseed.p, c->gstate.p, (u64*)out, (unsigned)B, grind, first, max_nonce, chunk_log, blocks, s);
+    HIPCHK(hipStreamSynchronize(s));
+    return c->h_gnonce.p;
+}
 
 // AIR constants and transcript seeds of the unit's proofs, on the host and on the device.
 // The Fiat-Shamir steps between the commitments (coefficient, OOD point, DEEP and FRI alpha
@@ -503,7 +525,30 @@ static void prove_lane(Lane* c, const Tables& T, const u64* ce_div, ProofJob* jo
     // per-proof index lists, which are then laid end to end
     std::vector<LaneLayout>& lay = c->hs.lay;
     if (lay.size() < (size_t)B) lay.resize(B);
-    pool.parallel_for(B, [jobs, &sh, &o, &rv, &lay](int b) { plan_queries(jobs[b], b, sh, o, rv, lay[b]); });
+    if (o.grind < GRIND_DEVICE_MIN) {
+        pool.parallel_for(B, [jobs, &sh, &o, &rv, &lay](int b) { plan_queries(jobs[b], b, sh, o, rv, lay[b]); });
+        c->grind_host += (u64)B;
+    } else {
+        // plan_queries with the device's search in the place of the host's: remainder commitments on the
+        // pool, the unit's B seeds to the device, one launch on the gather stream, each nonce checked with
+        // one hash, then the openings on the pool
+        pool.parallel_for(B, [jobs, &sh, &rv, &lay](int b) { plan_commit_remainder(jobs[b], b, sh, rv, lay[b]); });
+        Digest* seeds = grind_seeds(c, B);
+        for (int b = 0; b < B; b++) seeds[b] = jobs[b].coin.seed;
+        const GrindPlan gp = grind_plan((unsigned)o.grind, (uint32_t)B, (unsigned)c->cus);
+        const u64* nonces = grind_search(c, B, (unsigned)o.grind, 1, gp.max_nonce, gp.chunk_log, gp.blocks);
+        ht.mark("grind");
+        for (int b = 0; b < B; b++) {
+            if (nonces[b] == 0) {  // no nonce up to max_nonce (probability e^-256): this proof fails, the others go on
+                jobs[b].status = XFG_PROVER_ERROR;
+                jobs[b].pow_exhausted = true;
+            } else if (nonces[b] > gp.max_nonce || pow_zeros(jobs[b].coin.seed, nonces[b]) < o.grind) {
+                throw std::runtime_error("device / host transcript diverged");
+            }
+        }
+        pool.parallel_for(B, [jobs, &sh, &o, nonces, &lay](int b) { plan_openings(jobs[b], b, sh, o, nonces[b], lay[b]); });
+        c->grind_dev += (u64)B;
+    }
     ht.mark("queries_plan");
     OpeningIndex& ix = c->hs.ix;
     concat_indices(lay, B, sh, ix);
@@ -545,6 +590,7 @@ static void prove_lane(Lane* c, const Tables& T, const u64* ce_div, ProofJob* jo
 // and events
 static void create_lane_stream(xfg_ctx* c, Lane* L) {
     L->lde_probe = c->lde_probe;
+    HIPCHK(hipDeviceGetAttribute(&L->cus, hipDeviceAttributeMultiprocessorCount, c->device));
     HIPCHK(hipStreamCreateWithFlags(&L->stream, hipStreamNonBlocking));
     for (auto& e : L->ev) HIPCHK(hipEventCreate(&e));
 }
@@ -774,6 +820,11 @@ bool busy(xfg_ctx* c) {
     return !c->pending.empty();
 }
 
+static const char* prover_error_text(const ProofJob& j) {
+    return j.pow_exhausted ? "Prover error: proof-of-work search exhausted"
+                           : "Prover error: proof generation failed (degenerate transcript or DEEP degree)";
+}
+
 }  // namespace xfg
 
 using namespace xfg;
@@ -911,7 +962,7 @@ int xfg_prove_trace(xfg_ctx* c, const uint64_t* trace, uint32_t width, uint64_t 
         std::unique_ptr<Batch> b = wait_batch(c, enqueue(c, std::move(bp), {Unit{nullptr, 0, 1, -1}}));
         if (b->err) std::rethrow_exception(b->err);
         if (b->st[0] == XFG_PROVER_ERROR) {
-            c->err = "Prover error: proof generation failed (degenerate transcript or DEEP degree)";
+            c->err = prover_error_text(b->jobs[0]);
         } else if (b->st[0] == XFG_BUFFER_TOO_SMALL) {
             c->err = "output buffer too small";
         }
@@ -973,8 +1024,7 @@ int xfg_batch_wait(xfg_ctx* c, uint64_t ticket) {
         for (size_t k = 0; k < b->jobs.size(); k++) {
             b->statuses[b->which[k]] = b->st[k];
             if (b->st[k] == XFG_BUFFER_TOO_SMALL) c->err = "output buffer too small";
-            if (b->st[k] == XFG_PROVER_ERROR)
-                c->err = "Prover error: proof generation failed (degenerate transcript or DEEP degree)";
+            if (b->st[k] == XFG_PROVER_ERROR) c->err = prover_error_text(b->jobs[k]);
         }
         return XFG_OK;
     });

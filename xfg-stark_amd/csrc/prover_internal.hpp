@@ -2,6 +2,7 @@
 // (prover.hip), the debug / bench entry points (debug_abi.hip) and the GPU batch verifier's host
 // side (verify_batch_gpu.hip).
 #pragma once
+#include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <deque>
@@ -13,6 +14,7 @@
 #include <vector>
 
 #include "../../include/xfg_stark.h"
+#include "grind_plan.hpp"
 #include "hip_util.hpp"
 #include "host_common.hpp"
 #include "kernels.hpp"
@@ -69,6 +71,13 @@ struct Lane {
     MappedHBuf<unsigned char> h_xfer;  // the replay's inputs, written by launch_pack
     MappedHBuf<AirConst> h_air;
     MappedHBuf<DevCoin> h_coin;
+    // the device's proof-of-work search (grind_search): seeds in, nonces out, the kernel's per-proof words
+    MappedHBuf<Digest> h_gseed;
+    MappedHBuf<u64> h_gnonce;
+    DBuf<Digest> gseed;
+    DBuf<u64> gstate;
+    int cus = 0;  // compute units of the device (grind_plan)
+    std::atomic<uint64_t> grind_dev{0}, grind_host{0};  // proofs whose nonce was searched there (xfg_grind_probe)
     // host scratch of the opening plans and the serialiser, kept across units so steady-state
     // units neither allocate nor page-fault (their cost grew with the shared hosts' load)
     struct {
@@ -185,6 +194,12 @@ void size_ood_deep(Lane* c, size_t B, const ProofShape& sh);  // hcoef, zpts, pa
 // Constant columns are detected in the trace as it lies in c->trace (whatever put it there) and
 // filled in instead of transformed; the flags stay in c->const_col
 void launch_trace_lde(Lane* c, const Tables& T, int B, const ProofShape& sh, bool probe);
+// the proof-of-work search on the device for the B seeds the caller wrote to grind_seeds(c, B): launched on
+// the lane's gather stream (idle between a unit's chain and its gathers) and waited for. Returns the B
+// nonces (pinned host memory, valid until the lane's next search), 0 where [first, max_nonce] held none
+void size_grind(Lane* c, size_t B);
+Digest* grind_seeds(Lane* c, size_t B);
+const u64* grind_search(Lane* c, int B, unsigned grind, u64 first, u64 max_nonce, unsigned chunk_log, unsigned blocks);
 
 // the kernels' subtractions (gl_sub) are exact for canonical operands only: host inputs are checked
 static inline bool all_canonical(const uint64_t* v, size_t k) {

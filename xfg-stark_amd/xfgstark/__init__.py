@@ -116,6 +116,10 @@ if hasattr(_lib, "xfg_debug_fri_fold_f"):  # absent from builds older than foldi
                                           C.c_uint32, _u64p, _u64p, _u64p]
     _lib.xfg_debug_merkle_fri_f.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                             C.c_uint32, _u64p, _u8p]
+if hasattr(_lib, "xfg_debug_grind"):  # absent from builds older than the device proof-of-work search (XFG_LIB A/B)
+    _lib.xfg_debug_grind.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint64, C.c_uint64,
+                                     C.c_uint32, C.c_uint32, _u64p]
+    _lib.xfg_grind_probe.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), _u64p, _u64p]
 
 
 class XfgStarkError(Exception):
@@ -834,6 +838,31 @@ class XfgBurnMintProver:
         if st:
             raise self._err(st)
         return ow, osq, (int(ctr[0]), int(ctr[1])), (ok[0], ok[1])
+
+    def debug_grind(self, seeds, grind, first_nonce=1, max_nonce=0, chunk_log=0, blocks=0):
+        """the prover's proof-of-work search alone (xfg_debug_grind): seeds = 32-byte strings; for each the
+        smallest nonce in [first_nonce, max_nonce] whose BLAKE3(seed || nonce_le8) has >= grind trailing
+        zero bits in its first 8 LE bytes, 0 where there is none. max_nonce 0: the prover's bound
+        2^(grind + 8); chunk_log / blocks 0: the planner's geometry, else forced (6..16, 1..4096)"""
+        import numpy as np
+        k = len(seeds)
+        if any(len(bytes(sd)) != 32 for sd in seeds):
+            raise XfgStarkError(9, "debug_grind: seeds are 32 bytes each")
+        w = np.frombuffer(b"".join(bytes(sd) for sd in seeds), dtype="<u4").copy()
+        out = np.zeros(k, dtype=np.uint64)
+        st = _lib.xfg_debug_grind(self._ctx, k, w.ctypes.data_as(C.POINTER(C.c_uint32)), grind, first_nonce, max_nonce,
+                                  chunk_log, blocks, out.ctypes.data_as(_u64p))
+        if st:
+            raise self._err(st)
+        return [int(v) for v in out]
+
+    def grind_probe(self):
+        """(GRIND_DEVICE_MIN, proofs whose nonce this context searched on the device, on the host)"""
+        dmin, dev, host = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        st = _lib.xfg_grind_probe(self._ctx, C.byref(dmin), C.byref(dev), C.byref(host))
+        if st:
+            raise self._err(st)
+        return dmin.value, dev.value, host.value
 
     def debug_merkle_lde(self, lde, entries=()):
         """Merkle commitment of LDEs as the prover runs it (xfg_debug_merkle_lde): lde [B,nc,blowup,n]
