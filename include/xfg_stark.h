@@ -12,6 +12,8 @@
  *   xfg_prove_trace      <- <XfgBurnMintAir as winterfell::Prover>::prove(trace)
  *                           src/burn_mint_air.rs:479-531 (ExecutionTrace-level entry; trace layout
  *                           of build_trace :442-476, column-major)
+ *   xfg_prove_trace_batch <- the same for many traces at once, with Trace::validate (which Prover::prove runs
+ *                           in debug builds) on request; xfg_check_traces is that check alone
  *   xfg_prove_batch      <- the serial loops of the reference callers (e.g. benchmark harness
  *                           src/benchmarks/mod.rs:301-342, BatchBurnMintVerifier's pattern
  *                           src/burn_mint_verifier.rs:326-338) -- independent proofs, one launch set
@@ -55,7 +57,8 @@ typedef enum {
     XFG_DEVICE_ERROR = 7,        /* HIP runtime failure */
     XFG_BUFFER_TOO_SMALL = 8,
     XFG_INVALID_ARGUMENT = 9,
-    XFG_VERIFY_FAILED = 10       /* proof rejected (verifier) or not a well-formed proof (parser) */
+    XFG_VERIFY_FAILED = 10,      /* proof rejected (verifier) or not a well-formed proof (parser) */
+    XFG_INVALID_TRACE = 11       /* trace does not satisfy the AIR (only reported when validation is requested) */
 } xfg_status;
 
 /* winterfell::ProofOptions (0.8) */
@@ -122,6 +125,61 @@ int xfg_prove_batch_submit(xfg_ctx* ctx, uint32_t count, const xfg_burn_inputs* 
                            uint64_t* ticket);
 /* blocks until the batch is proven and its outputs written; returns like xfg_prove_batch */
 int xfg_batch_wait(xfg_ctx* ctx, uint64_t ticket);
+
+/* ---- batches of caller-supplied execution traces, optionally validated on the device ----
+ * What Trace::validate (winter-air 0.8, run by Prover::prove in debug builds) reports first for a trace:
+ * the assertions in the order of the AIR, then the transition constraints step by step (steps
+ * 0 .. n-2: the last step has no transition), constraint by constraint. */
+typedef struct {
+    uint32_t kind;     /* 0 = trace is valid, 1 = assertion, 2 = transition constraint, 3 = a cell is not a
+                          canonical field element (>= p): the first such cell in step, then column order */
+    uint32_t index;    /* assertion number 0..7 (order of the AIR: columns 0..6 at step 0, then column 4 at
+                          step n-1) or transition constraint number 0..6; kind 3: 0 */
+    uint32_t column;   /* assertions and kind 3: the column of the cell; transitions: 0 */
+    uint64_t step;
+    uint64_t expected; /* assertions: asserted value; otherwise 0 */
+    uint64_t found;    /* assertions and kind 3: the trace cell; transitions: 0 */
+} xfg_trace_fault;
+
+#define XFG_TRACE_VALIDATE   1u  /* run the check; invalid traces get XFG_INVALID_TRACE and no proof */
+#define XFG_TRACE_ON_DEVICE  2u  /* `traces` is a device pointer on the context's device */
+
+/* the check alone on `count` (<= 65535) traces [count][7][n], column-major as for xfg_prove_trace, n a
+ * power of two >= 8; synchronous, on lane 0 (refused while batches are pending). flags: 0 or
+ * XFG_TRACE_ON_DEVICE. Returns XFG_OK when the check ran; faults[i] then says what trace i violates
+ * (kind 0: nothing). The traces are only read. */
+int xfg_check_traces(xfg_ctx* ctx, uint32_t count, const uint64_t* traces, uint64_t n, const xfg_air_consts* airs,
+                     uint32_t flags, xfg_trace_fault* faults);
+/* xfg_prove_trace for `count` independent traces [count][7][n] with their AIR constants airs[count],
+ * through the lanes like xfg_prove_batch: units of 32 proofs, each reading its own slice of `traces`.
+ * width, options and AIR constants are checked as by xfg_prove_trace; a refused call launches nothing.
+ * Host traces (no XFG_TRACE_ON_DEVICE) are checked for canonical cells before the call returns and go
+ * up through pinned staging owned by the lanes; the staging is sized by the first such batch a lane
+ * proves, or by xfg_prepare once the context has been given a host-trace batch. Device traces are copied
+ * device-to-device on the lane's stream: the caller guarantees that the data is complete (every
+ * producing stream synchronised) before the call; their cells are checked for canonicity on the device.
+ * The caller's traces are never written. A proof whose trace holds a cell >= p gets
+ * statuses[i] = XFG_INVALID_ARGUMENT, the others are unaffected.
+ * XFG_TRACE_VALIDATE: each trace is checked on the lane's stream behind its upload; a trace that
+ * violates the AIR gets statuses[i] = XFG_INVALID_TRACE, out_lens[i] = 0 and no proof (this takes
+ * precedence over the XFG_PROVER_ERROR its DEEP degree may also earn); xfg_last_error carries
+ * Trace::validate's message for the last such proof ("trace does not satisfy assertion
+ * main_trace(column, step) == expected" / "main transition constraint index did not evaluate to ZERO
+ * at step step"). The other proofs are byte-identical to proving them alone. Without the flag any
+ * canonical trace is proven, as by xfg_prove_trace.
+ * faults (may be NULL): faults[i] for every proof when the batch has been waited for (kind 0 unless
+ * statuses[i] is XFG_INVALID_TRACE, or XFG_INVALID_ARGUMENT for a cell >= p).
+ * Returns XFG_OK if the batch ran, like xfg_prove_batch. */
+int xfg_prove_trace_batch(xfg_ctx* ctx, uint32_t count, const uint64_t* traces, uint32_t width, uint64_t n,
+                          const xfg_air_consts* airs, const xfg_options* opts, uint32_t flags, uint8_t* const* outs,
+                          size_t* out_lens, int* statuses, xfg_trace_fault* faults);
+/* asynchronous form, waited for with xfg_batch_wait(ticket): traces, outs, out_lens, statuses and
+ * faults stay the caller's, valid and unchanged, until the wait returns (airs only until this call
+ * returns). statuses[i] of proofs refused here (host cell >= p) are set now. */
+int xfg_prove_trace_batch_submit(xfg_ctx* ctx, uint32_t count, const uint64_t* traces, uint32_t width, uint64_t n,
+                                 const xfg_air_consts* airs, const xfg_options* opts, uint32_t flags,
+                                 uint8_t* const* outs, size_t* out_lens, int* statuses, xfg_trace_fault* faults,
+                                 uint64_t* ticket);
 
 /* allocate every device / pinned-host workspace and load all code objects for batches of
  * `count` proofs of this shape (setup, not a prove; later calls never allocate) */

@@ -13,6 +13,7 @@
 // All arithmetic is 64-bit Goldilocks integer work: HBM/VALU bound, no MFMA.
 #include "dev_coin.hpp"
 #include "field_dft.hpp"
+#include "hip_util.hpp"
 #include <algorithm>
 #include <stdexcept>
 
@@ -21,6 +22,11 @@ namespace xfg {
 #define XFG_CHECK_LAUNCH() (void)hipGetLastError()
 
 __device__ __forceinline__ unsigned brev(unsigned x, int bits) { return __brev(x) >> (32 - bits); }
+
+__device__ __forceinline__ u64 shfl_xor_u64(u64 v, int m, int w) {
+    u32 lo = __shfl_xor((u32)v, m, w), hi = __shfl_xor((u32)(v >> 32), m, w);
+    return (u64)lo | ((u64)hi << 32);
+}
 
 // w_{2^k}^e from the master table (forward) / its inverse
 __device__ __forceinline__ u64 tw_pow(const Tables& T, int k, u64 e) {
@@ -56,6 +62,27 @@ void launch_trace_gen(const AirConst* air, u64* trace, int logn, int npoly, hipS
     XFG_CHECK_LAUNCH();
 }
 
+// XfgBurnMintAir::evaluate_transition (reference src/burn_mint_air.rs:335-378) on one row: cur = the
+// row's seven cells, nxt4 = column 4 of the next row (the only neighbour the AIR reads). Shared by
+// the constraint evaluator (rows of the LDE) and the trace check (rows of the trace itself)
+__device__ __forceinline__ void air_transition(const AirConst& A, const u64 (&cur)[7], u64 nxt4, u64 (&r)[7]) {
+    const u64 std_burn = 8000000ULL, large_burn = 8000000000ULL;
+    r[0] = gl_mul(gl_sub(cur[0], std_burn), gl_sub(cur[0], large_burn));
+    r[1] = gl_sub(cur[1], cur[0]);
+    r[2] = gl_sub(cur[2], A.pub[2] & 0xFFFFFFFFULL);
+    r[3] = gl_sub(cur[3], A.pub[3] & 0xFFFFFFFFULL);
+    const u64 d = gl_sub(nxt4, cur[4]);
+    r[4] = gl_mul(d, gl_sub(d, 1));
+    r[5] = gl_sub(cur[5], A.nullifier);
+    r[6] = gl_sub(cur[6], A.commitment);
+}
+// the values asserted at step 0 on columns 0..6 (src/burn_mint_air.rs:380-395); the eighth assertion is
+// column 4 == AIR_LAST_STATE at step n - 1
+__device__ __forceinline__ void air_step0_values(const AirConst& A, u64 (&v0)[7]) {
+    v0[0] = A.pub[0]; v0[1] = A.pub[1]; v0[2] = A.pub[2]; v0[3] = A.pub[3];
+    v0[4] = 0; v0[5] = A.nullifier; v0[6] = A.commitment;
+}
+
 struct CeArgs {
     const u64* lde;
     const AirConst* air;
@@ -89,26 +116,18 @@ __global__ __launch_bounds__(256) void constraint_eval_kernel(CeArgs a) {
     // divisor inverses loaded with the frame (not next to the multiplies that use them)
     const u64 di = par * n + m;
     const u64 dv0 = a.div[di], dv1 = a.div[nce + di], dv2 = a.div[2 * nce + di];
-    // XfgBurnMintAir::evaluate_transition (reference src/burn_mint_air.rs:335-378)
-    const u64 std_burn = 8000000ULL, large_burn = 8000000000ULL;
     u64 r[7];
-    r[0] = gl_mul(gl_sub(cur[0], std_burn), gl_sub(cur[0], large_burn));
-    r[1] = gl_sub(cur[1], cur[0]);
-    r[2] = gl_sub(cur[2], A.pub[2] & 0xFFFFFFFFULL);
-    r[3] = gl_sub(cur[3], A.pub[3] & 0xFFFFFFFFULL);
-    const u64 d = gl_sub(nxt4, cur[4]);
-    r[4] = gl_mul(d, gl_sub(d, 1));
-    r[5] = gl_sub(cur[5], A.nullifier);
-    r[6] = gl_sub(cur[6], A.commitment);
+    air_transition(A, cur, nxt4, r);
     F tr = F::zero();
 #pragma unroll
     for (int c = 0; c < 7; c++) tr = fe_add(tr, fe_mulb(F::load(co + c * D), r[c]));
     // assertions (src/burn_mint_air.rs:380-395): step 0 on columns 0..6, step n-1 on column 4
-    const u64 v0[7] = {A.pub[0], A.pub[1], A.pub[2], A.pub[3], 0, A.nullifier, A.commitment};
+    u64 v0[7];
+    air_step0_values(A, v0);
     F b0 = F::zero();
 #pragma unroll
     for (int c = 0; c < 7; c++) b0 = fe_add(b0, fe_mulb(F::load(co + (7 + c) * D), gl_sub(cur[c], v0[c])));
-    const F b1 = fe_mulb(F::load(co + 14 * D), gl_sub(cur[4], 3));
+    const F b1 = fe_mulb(F::load(co + 14 * D), gl_sub(cur[4], AIR_LAST_STATE));
     F val = fe_mulb(tr, dv0);
     val = fe_add(val, fe_mulb(b0, dv1));
     val = fe_add(val, fe_mulb(b1, dv2));
@@ -127,6 +146,76 @@ void launch_constraint_eval(const u64* lde, const AirConst* air, const u64* coef
     XFG_CHECK_LAUNCH();
 }
 
+// Trace::validate (winter-air 0.8) on the device: one thread per step reads its row (seven coalesced
+// 8-byte streams, no LDS) and, for the column-4 constraint alone, cell [4][step + 1] of the next row;
+// it checks the assertions that fall on its step and, below the last step (Winterfell's one transition
+// exemption), the seven transition expressions. What it finds first in Winterfell's reporting order
+// becomes a key (trace_key, kernels.hpp); the keys are reduced to a minimum over the wave with shuffles
+// and only a wave that found something issues an atomicMin on the proof's word, so a valid trace issues
+// none. keys[proof] was set to all ones by the launch wrapper.
+// A cell >= p is reported before anything else and replaced by its canonical value in `trace` (the
+// lane's copy, never the caller's buffer), so that the chain behind the check runs on field elements;
+// the thread of step - 1 may read that cell before or after the store, and what it then reports is
+// below the non-canonical key either way.
+// AIR = false: the canonicity test alone (device-resident traces proven without validation)
+template <bool AIR>
+__global__ __launch_bounds__(256) void trace_check_kernel(u64* trace, const AirConst* air, u64* keys, int logn) {
+    const u64 n = 1ULL << logn;
+    const u64 s = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    const int proof = blockIdx.y;
+    u64 key = TRACE_KEY_VALID;
+    if (s < n) {  // no early return: every lane of the wave takes part in the shuffles
+        u64* tr = trace + (u64)proof * 7 * n;
+        u64 cur[7];
+#pragma unroll
+        for (int c = 0; c < 7; c++) cur[c] = tr[(u64)c * n + s];
+        u64 nxt4 = 0;
+        if (AIR && s + 1 < n) nxt4 = tr[4 * n + s + 1];
+#pragma unroll
+        for (int c = 6; c >= 0; c--) {
+            if (cur[c] >= P) {
+                key = trace_key(TRACE_KEY_NONCANONICAL, s, (unsigned)c);
+                cur[c] -= P;
+                tr[(u64)c * n + s] = cur[c];
+            }
+        }
+        if (AIR && key == TRACE_KEY_VALID) {
+            const AirConst& A = air[proof];
+            if (s + 1 < n) {
+                if (nxt4 >= P) nxt4 -= P;
+                u64 r[7];
+                air_transition(A, cur, nxt4, r);
+#pragma unroll
+                for (int c = 6; c >= 0; c--)
+                    if (r[c] != 0) key = trace_key(TRACE_KEY_TRANSITION, s, (unsigned)c);
+            } else if (cur[4] != AIR_LAST_STATE) {
+                key = trace_key(TRACE_KEY_ASSERTION, s, 7);
+            }
+            if (s == 0) {  // after the rest: an assertion precedes every transition, and number 7 when n = 1
+                u64 v0[7];
+                air_step0_values(A, v0);
+#pragma unroll
+                for (int c = 6; c >= 0; c--)
+                    if (cur[c] != v0[c]) key = trace_key(TRACE_KEY_ASSERTION, 0, (unsigned)c);
+            }
+        }
+    }
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) {
+        const u64 o = shfl_xor_u64(key, m, 64);
+        key = o < key ? o : key;
+    }
+    if ((threadIdx.x & 63) == 0 && key != TRACE_KEY_VALID) atomicMin((unsigned long long*)(keys + proof), (unsigned long long)key);
+}
+void launch_trace_check(u64* trace, const AirConst* air, u64* keys, int logn, int npoly, bool with_air, hipStream_t s) {
+    const u64 n = 1ULL << logn;
+    HIPCHK(hipMemsetAsync(keys, 0xFF, (size_t)npoly * 8, s));  // TRACE_KEY_VALID
+    dim3 g((unsigned)((n + 255) / 256), npoly);
+    if (with_air) hipLaunchKernelGGL(trace_check_kernel<true>, g, dim3(256), 0, s, trace, air, keys, logn);
+    else hipLaunchKernelGGL(trace_check_kernel<false>, g, dim3(256), 0, s, trace, air, keys, logn);
+    XFG_CHECK_LAUNCH();
+}
+
 // ============================================================================ OOD
 // Blocks own CHUNK = T * OOD_R consecutive coefficients (T = min(256, n / OOD_R) threads, thread t
 // takes j = base + r T + t: coalesced). Per block the 15 partial sums
@@ -135,11 +224,6 @@ void launch_constraint_eval(const u64* lde, const AirConst* air, const u64* coef
 // them as its per-block carries (no second pass over the coefficients for the block sums).
 #define OOD_R 8
 static inline int ood_threads(u64 n) { return (int)std::min<u64>(256, n / OOD_R); }
-
-__device__ __forceinline__ u64 shfl_xor_u64(u64 v, int m, int w) {
-    u32 lo = __shfl_xor((u32)v, m, w), hi = __shfl_xor((u32)(v >> 32), m, w);
-    return (u64)lo | ((u64)hi << 32);
-}
 
 template <int D>
 __device__ __forceinline__ FE<D> fe_pow(FE<D> b, u64 e) {

@@ -127,6 +127,20 @@ void launch_merkle_fri(const u64* vals, u64 val_stride, u64 comp_stride, bool co
 
 // ---- AIR ----
 void launch_trace_gen(const AirConst* air, u64* trace, int logn, int npoly, hipStream_t s);
+// Trace::validate on the device (trace_check_kernel): keys[proof] = the smallest key of what the trace
+// [npoly][7][n] violates, TRACE_KEY_VALID (all ones) when nothing. A key is kind << 62 | step << 3 | index,
+// so that their order is the order of the report: a cell >= p first (index = column; such a cell is also
+// replaced by its canonical value, so `trace` is the lane's copy), then the assertions by number
+// (0..6 = columns 0..6 at step 0, 7 = column 4 at step n - 1; step-major order is number order), then
+// the transition constraints by step and number 0..6 (steps 0..n-2). with_air = false: the canonicity
+// test alone. Sets keys with a memset on s first; npoly <= 65535
+constexpr u64 AIR_LAST_STATE = 3;  // the value asserted on column 4 at step n - 1
+constexpr u64 TRACE_KEY_VALID = ~0ULL;
+enum : unsigned { TRACE_KEY_NONCANONICAL = 0, TRACE_KEY_ASSERTION = 1, TRACE_KEY_TRANSITION = 2 };
+__host__ __device__ constexpr u64 trace_key(unsigned kind, u64 step, unsigned index) {
+    return ((u64)kind << 62) | (step << 3) | index;
+}
+void launch_trace_check(u64* trace, const AirConst* air, u64* keys, int logn, int npoly, bool with_air, hipStream_t s);
 // composition evaluations over the CE domain 7*<w_2n> (natural order) from the trace LDE
 // div = constraint divisor table [3][2][n] from ce_divisor_table()
 // ext = extension degree D: coeffs [B][15][D], ce planes [B][D][2n]

@@ -174,8 +174,22 @@ void size_ood_deep(Lane* c, size_t B, const ProofShape& sh) {
     c->carry.ensure(B * 2 * sh.DE * ood_partial_count(sh.logn));
     c->deep.ensure(B * sh.DE * sh.n);
 }
+// where a unit's traces come from, and what is checked on the way. p: the unit's own slice [B][7][n]
+// (null: generated on the device from the AIR constants)
+struct TraceSrc {
+    enum Kind { GENERATED, HOST_DIRECT, HOST_STAGED, DEVICE };
+    Kind kind = GENERATED;
+    const u64* p = nullptr;
+    bool validate = false;        // XFG_TRACE_VALIDATE: the AIR check behind the upload
+    bool size_staging = false;    // grow the lane's pinned trace staging with its other buffers
+    const int* refused = nullptr;  // [B] non-zero: refused at submission, the slot is proven over zeros
+    u64* keys = nullptr;          // [B] out: the check kernel's words (when checks())
+    // device traces are always tested for canonical cells; host traces were on the host
+    bool checks() const { return validate || kind == DEVICE; }
+};
+
 // every device buffer of a unit of B proofs, and the pinned opening buffers
-static void size_lane_buffers(Lane* c, size_t B, const ProofShape& sh, const Opts& o) {
+static void size_lane_buffers(Lane* c, size_t B, const ProofShape& sh, const Opts& o, const TraceSrc& ts) {
     const u64 n = sh.n, N = sh.N;
     const size_t DE = sh.DE;
     const unsigned nl = sh.nl;
@@ -213,6 +227,8 @@ static void size_lane_buffers(Lane* c, size_t B, const ProofShape& sh, const Opt
     c->h_gv.ensure(vals);
     c->h_gd.ensure(digs + opens);
     size_grind(c, B);
+    if (ts.checks()) c->tkeys.ensure(B);
+    if (ts.kind == TraceSrc::HOST_STAGED || ts.size_staging) c->h_trace.ensure(B * 7 * n);
 }
 
 // the unit's small uploads are copied by a kernel from the pinned, device-mapped host blocks: no
@@ -336,7 +352,8 @@ static void enqueue_fri_layers(Lane* c, const Tables& T, int B, const ProofShape
 // could start ~0.2 ms after the previous one (rocprof, scripts/fri_timeline.sh: 1.7 ms of idle
 // stream after the last FRI fold); as one larger copy the runtime takes the SDMA engine, whose
 // dependency on the lane stream cost 17 % of the pipelined throughput (same box, lib_ab.sh)
-static ReplayView pack_replay_block(Lane* c, size_t B, const ProofShape& sh) {
+// with_keys: the trace check's word per proof rides along (units of caller-supplied traces that are checked)
+static ReplayView pack_replay_block(Lane* c, size_t B, const ProofShape& sh, bool with_keys) {
     const size_t DE = sh.DE, nl = sh.nl;
     PackSet pk;
     u64 words = 0;
@@ -357,6 +374,7 @@ static ReplayView pack_replay_block(Lane* c, size_t B, const ProofShape& sh) {
     const u64 o_rem = seg(c->rem.p, B * DE * sh.rem_len * 8);
     const u64 o_dn2 = seg(c->dn2.p, B * DE * 8);
     const u64 o_const = seg(c->const_col.p, (B * 7 + 3) & ~(size_t)3);  // whole words; B * 7 flags
+    const u64 o_keys = with_keys ? seg(c->tkeys.p, B * 8) : 0;
     unsigned char* hx = c->h_xfer.ensure(words * 4);
     void* hx_dev = nullptr;
     HIPCHK(hipHostGetDevicePointer(&hx_dev, hx, 0));
@@ -371,13 +389,14 @@ static ReplayView pack_replay_block(Lane* c, size_t B, const ProofShape& sh) {
     rv.remh = (const u64*)(hx + o_rem);
     rv.dn2h = (const u64*)(hx + o_dn2);
     c->h_const_col = hx + o_const;
+    c->h_tkeys = with_keys ? (const u64*)(hx + o_keys) : nullptr;
     return rv;
 }
 
 // the whole device chain of a unit, trace to FRI remainder and the replay block, enqueued on the
 // lane stream without a host round trip. g: the trace domain generator
 static ReplayView enqueue_commit_chain(Lane* c, const Tables& T, const u64* ce_div, ProofJob* jobs, int B,
-                                       const u64* trace_host, const ProofShape& sh, const Opts& o, u64 g,
+                                       const TraceSrc& ts, const ProofShape& sh, const Opts& o, u64 g,
                                        HostTrace& ht) {
     const u64 n = sh.n;
     const int logn = sh.logn, logbeta = sh.logbeta, DE = sh.DE;
@@ -386,8 +405,30 @@ static ReplayView enqueue_commit_chain(Lane* c, const Tables& T, const u64* ce_d
     // ---- 1. trace LDE + commitment (DefaultTraceLde::new)
     ht.mark("setup");
     stage_mark(c, 0);
-    if (trace_host) HIPCHK(hipMemcpyAsync(c->trace.p, trace_host, (size_t)B * 7 * n * 8, hipMemcpyHostToDevice, s));
-    else launch_trace_gen(c->air.p, c->trace.p, logn, B, s);
+    const size_t tbytes = (size_t)7 * n * 8;  // one proof's trace
+    switch (ts.kind) {
+        case TraceSrc::GENERATED: launch_trace_gen(c->air.p, c->trace.p, logn, B, s); break;
+        case TraceSrc::HOST_DIRECT:  // xfg_prove_trace: one trace, straight from the caller's memory
+            HIPCHK(hipMemcpyAsync(c->trace.p, ts.p, B * tbytes, hipMemcpyHostToDevice, s));
+            break;
+        case TraceSrc::HOST_STAGED: {
+            // into the lane's pinned staging (the stream has drained: the last unit's upload is over),
+            // then one asynchronous DMA; a proof refused at submission (cell >= p) is staged as zeros
+            u64* st = c->h_trace.p;
+            const u64* src = ts.p;
+            const int* refused = ts.refused;
+            host_pool().parallel_for(B, [st, src, refused, n, tbytes](int b) {
+                if (refused[b]) memset(st + (size_t)b * 7 * n, 0, tbytes);
+                else memcpy(st + (size_t)b * 7 * n, src + (size_t)b * 7 * n, tbytes);
+            });
+            HIPCHK(hipMemcpyAsync(c->trace.p, st, B * tbytes, hipMemcpyHostToDevice, s));
+            break;
+        }
+        case TraceSrc::DEVICE:
+            HIPCHK(hipMemcpyAsync(c->trace.p, ts.p, B * tbytes, hipMemcpyDeviceToDevice, s));
+            break;
+    }
+    if (ts.checks()) launch_trace_check(c->trace.p, c->air.p, c->tkeys.p, logn, B, ts.validate, s);
     launch_trace_lde(c, T, B, sh, c->lde_probe);
     stage_mark(c, 1);
     // ---- 2. trace root -> constraint composition coefficients (7 transition + 8 boundary)
@@ -429,7 +470,7 @@ static ReplayView enqueue_commit_chain(Lane* c, const Tables& T, const u64* ce_d
     stage_mark(c, 7);
     // ---- 6. FRI layers and remainder, then the replay's inputs
     enqueue_fri_layers(c, T, B, sh, (int)o.fold, cs, ht);
-    const ReplayView rv = pack_replay_block(c, B, sh);
+    const ReplayView rv = pack_replay_block(c, B, sh, ts.checks());
     stage_mark(c, 8);
     ht.mark("launch_rem");
     return rv;
@@ -501,7 +542,7 @@ static Gathered enqueue_gathers(Lane* c, const ProofShape& sh, const OpeningInde
 // the batched prover: jobs[i].air filled; trace_host optional ([B][7][n], else generated on device).
 // Device chain -> host transcript replay -> opening plans -> gathers -> serialisation; the per-proof
 // host steps (proof_assembly.hpp) are independent and spread over the host pool
-static void prove_lane(Lane* c, const Tables& T, const u64* ce_div, ProofJob* jobs, int B, const u64* trace_host,
+static void prove_lane(Lane* c, const Tables& T, const u64* ce_div, ProofJob* jobs, int B, const TraceSrc& ts,
                        u64 n, const Opts& o) {
     using clk = std::chrono::steady_clock;
     const auto t_host0 = clk::now();
@@ -511,8 +552,8 @@ static void prove_lane(Lane* c, const Tables& T, const u64* ce_div, ProofJob* jo
     const u64 g = gl_root(sh.logn);
     HostPool& pool = host_pool();
 
-    size_lane_buffers(c, B, sh, o);
-    const ReplayView rv = enqueue_commit_chain(c, T, ce_div, jobs, B, trace_host, sh, o, g, ht);
+    size_lane_buffers(c, B, sh, o, ts);
+    const ReplayView rv = enqueue_commit_chain(c, T, ce_div, jobs, B, ts, sh, o, g, ht);
     HIPCHK(hipStreamSynchronize(c->stream));
     ht.mark("sync_rem");
     // trace columns that went through the NTTs (the rest were constant: detected, filled in)
@@ -564,6 +605,16 @@ static void prove_lane(Lane* c, const Tables& T, const u64* ce_div, ProofJob* jo
         serialize_proof(jobs[b], b, B, sh, o, lay[b], ix, got.gv, got.gd);
     });
     ht.mark("serialize");
+    // caller-supplied traces: what the check found, or the refusal at submission, is the proof's status
+    // whatever the chain made of the slot (an invalid trace usually fails the DEEP degree check too)
+    for (int b = 0; b < B && ts.kind != TraceSrc::GENERATED; b++) {
+        const u64 key = c->h_tkeys ? c->h_tkeys[b] : TRACE_KEY_VALID;
+        const bool refused = ts.refused && ts.refused[b];  // its key word was written at submission
+        if (ts.keys && !refused) ts.keys[b] = key;
+        if (refused) jobs[b].status = ts.refused[b];
+        else if (key != TRACE_KEY_VALID)
+            jobs[b].status = (key >> 62) == TRACE_KEY_NONCANONICAL ? XFG_INVALID_ARGUMENT : XFG_INVALID_TRACE;
+    }
     ht.dump(B, (long)((u64)B * 7 - live_cols));
     if (c->lde_probe) {  // the stream has passed both events (root / query fetches synchronised it)
         float ms = 0;
@@ -629,7 +680,12 @@ struct Batch {
     size_t* out_lens = nullptr;    // caller capacities in, proof lengths out
     int* statuses = nullptr;       // caller statuses, written by wait
     std::vector<int> st;           // per-job copy-out status
-    const u64* trace_host = nullptr;
+    // caller-supplied traces [jobs][7][n] (job k <-> caller index k: such a batch keeps refused proofs
+    // as jobs so that every unit's slice stays at b0 * 7 * n); trace.p is the batch's base
+    TraceSrc trace;
+    std::vector<int> refused;          // per job: status set at submission (cell >= p), else 0
+    std::vector<u64> keys;             // per job: the trace check's word
+    xfg_trace_fault* faults = nullptr;  // caller's, filled by wait (may be null)
     u64 n = 0;
     Opts o{};
     Tables T{};
@@ -671,6 +727,10 @@ static void copy_unit(Batch* b, int b0, int b1) {
         ProofJob& j = b->jobs[k];
         if (j.status) {
             b->st[k] = j.status;
+            if (j.status == XFG_INVALID_TRACE) {  // no proof: whatever the slot's chain produced is dropped
+                b->out_lens[b->which[k]] = 0;
+                std::vector<uint8_t>().swap(j.bytes);
+            }
             return;
         }
         if (b->which.empty()) {  // warm-up batch (xfg_prepare): bytes discarded
@@ -736,7 +796,12 @@ static void worker_main(xfg_ctx* c, int l) {
         std::exception_ptr e;
         if (!skip) {
             try {
-                prove_lane(L, b->T, b->ce_div, b->jobs.data() + u.b0, u.b1 - u.b0, b->trace_host, b->n, b->o);
+                // the unit's own slice of the batch's traces, refusals and key words (halved units too)
+                TraceSrc ts = b->trace;
+                if (ts.p) ts.p += (size_t)u.b0 * 7 * b->n;
+                if (!b->refused.empty()) ts.refused = b->refused.data() + u.b0;
+                if (!b->keys.empty()) ts.keys = b->keys.data() + u.b0;
+                prove_lane(L, b->T, b->ce_div, b->jobs.data() + u.b0, u.b1 - u.b0, ts, b->n, b->o);
                 copy_unit(b, u.b0, u.b1);
             } catch (...) {
                 e = std::current_exception();
@@ -823,6 +888,50 @@ bool busy(xfg_ctx* c) {
 static const char* prover_error_text(const ProofJob& j) {
     return j.pow_exhausted ? "Prover error: proof-of-work search exhausted"
                            : "Prover error: proof generation failed (degenerate transcript or DEEP degree)";
+}
+
+// the trace check's word (trace_key, kernels.hpp) as the C ABI reports it; cell(column, step) fetches
+// that cell of the proof's trace as the caller holds it
+template <class Cell>
+static xfg_trace_fault decode_trace_key(u64 key, const AirConst& A, Cell cell) {
+    xfg_trace_fault f{};
+    if (key == TRACE_KEY_VALID) return f;
+    const unsigned kind = (unsigned)(key >> 62), idx = (unsigned)(key & 7);
+    f.step = (key << 2) >> 5;
+    if (kind == TRACE_KEY_TRANSITION) {
+        f.kind = 2;
+        f.index = idx;
+        return f;
+    }
+    if (kind == TRACE_KEY_ASSERTION) {
+        const u64 asserted[8] = {A.pub[0], A.pub[1], A.pub[2], A.pub[3], 0, A.nullifier, A.commitment, AIR_LAST_STATE};
+        f.kind = 1;
+        f.index = idx;
+        f.column = idx < 7 ? idx : 4;
+        f.expected = asserted[idx];
+    } else {
+        f.kind = 3;
+        f.column = idx;
+    }
+    f.found = cell(f.column, f.step);
+    return f;
+}
+// Trace::validate's panic messages (winter-air 0.8)
+static std::string trace_fault_text(const xfg_trace_fault& f) {
+    if (f.kind == 1)
+        return "trace does not satisfy assertion main_trace(" + std::to_string(f.column) + ", " +
+               std::to_string(f.step) + ") == " + std::to_string(f.expected);
+    if (f.kind == 2)
+        return "main transition constraint " + std::to_string(f.index) + " did not evaluate to ZERO at step " +
+               std::to_string(f.step);
+    return f.kind == 3 ? "trace element is not a canonical field element" : "";
+}
+// one cell of a caller's trace buffer (host memory, or device memory of the current device)
+static u64 fetch_cell(const u64* traces, bool on_device, size_t at) {
+    if (!on_device) return traces[at];
+    u64 v = 0;
+    HIPCHK(hipMemcpy(&v, traces + at, 8, hipMemcpyDeviceToHost));
+    return v;
 }
 
 }  // namespace xfg
@@ -955,7 +1064,8 @@ int xfg_prove_trace(xfg_ctx* c, const uint64_t* trace, uint32_t width, uint64_t 
         bp->which = {0};
         bp->outs = {out};
         bp->out_lens = out_len;
-        bp->trace_host = trace;
+        bp->trace.kind = TraceSrc::HOST_DIRECT;
+        bp->trace.p = trace;
         bp->n = n;
         bp->o = o;
         bind_tables(c, bp.get());
@@ -1026,6 +1136,21 @@ int xfg_batch_wait(xfg_ctx* c, uint64_t ticket) {
             if (b->st[k] == XFG_BUFFER_TOO_SMALL) c->err = "output buffer too small";
             if (b->st[k] == XFG_PROVER_ERROR) c->err = prover_error_text(b->jobs[k]);
         }
+        // caller-supplied traces: what the check found, decoded (the cell of a failed assertion is read
+        // from the caller's buffer, which stays theirs until here)
+        if (!b->keys.empty()) {
+            const bool dev = b->trace.kind == TraceSrc::DEVICE;
+            if (dev) HIPCHK(hipSetDevice(c->device));
+            for (size_t k = 0; k < b->jobs.size(); k++) {
+                const u64* tr = b->trace.p + k * 7 * b->n;
+                const u64 n = b->n;
+                const xfg_trace_fault f = decode_trace_key(b->keys[k], b->jobs[k].air, [&](uint32_t col, u64 step) {
+                    return fetch_cell(tr, dev, (size_t)col * n + step);
+                });
+                if (b->faults) b->faults[b->which[k]] = f;
+                if (f.kind) c->err = trace_fault_text(f);
+            }
+        }
         return XFG_OK;
     });
 }
@@ -1036,6 +1161,168 @@ int xfg_prove_batch(xfg_ctx* c, uint32_t count, const xfg_burn_inputs* inputs, u
     int r = xfg_prove_batch_submit(c, count, inputs, trace_length, opts, outs, out_lens, statuses, &t);
     if (r) return r;
     return xfg_batch_wait(c, t);
+}
+
+// XFG_TRACE_ON_DEVICE: `traces` must be device memory of the context's device that this process's HIP
+// runtime allocated, and the allocation must hold all `bytes` (the lanes copy that range). Returns what
+// is wrong, or null. Asks the runtime only: nothing is launched or copied
+static const char* device_traces_problem(xfg_ctx* c, const void* traces, size_t bytes) {
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, traces) != hipSuccess) {
+        (void)hipGetLastError();
+        return "traces is not a device pointer known to the library's HIP runtime";
+    }
+    if (a.type != hipMemoryTypeDevice || a.device != c->device) return "traces is not device memory of the context's device";
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(traces)) != hipSuccess) {
+        (void)hipGetLastError();
+        return "traces is not a device pointer known to the library's HIP runtime";
+    }
+    if ((const char*)traces + bytes > (const char*)base + size) return "the device allocation is smaller than [count][7][n] traces";
+    return nullptr;
+}
+
+// the key of the first cell >= p of a host trace [7][n] in the check kernel's order (step, then
+// column), TRACE_KEY_VALID when every cell is canonical
+static u64 host_noncanonical_key(const u64* tr, u64 n) {
+    u64 key = TRACE_KEY_VALID;
+    for (unsigned col = 0; col < 7; col++)
+        for (u64 s = 0; s < n; s++)
+            if (tr[col * n + s] >= P) {
+                key = std::min(key, trace_key(TRACE_KEY_NONCANONICAL, s, col));
+                break;
+            }
+    return key;
+}
+
+int xfg_prove_trace_batch_submit(xfg_ctx* c, uint32_t count, const uint64_t* traces, uint32_t width, uint64_t n,
+                                 const xfg_air_consts* airs, const xfg_options* opts, uint32_t flags,
+                                 uint8_t* const* outs, size_t* out_lens, int* statuses, xfg_trace_fault* faults,
+                                 uint64_t* ticket) {
+    if (!c) return XFG_INVALID_ARGUMENT;
+    c->err.clear();
+    if (!traces || !airs || !opts || !out_lens || !statuses || !ticket || count == 0) {
+        c->err = count == 0 ? "empty batch" : "null argument";
+        return XFG_INVALID_ARGUMENT;
+    }
+    *ticket = 0;
+    if (width != 7) {
+        c->err = "XfgBurnMintAir traces have 7 columns";
+        return XFG_INVALID_ARGUMENT;
+    }
+    if (flags & ~(XFG_TRACE_VALIDATE | XFG_TRACE_ON_DEVICE)) {
+        c->err = "unknown trace flag";
+        return XFG_INVALID_ARGUMENT;
+    }
+    Opts o = to_opts(opts);
+    if (int st = check_request(c, n, o)) return st;
+    for (uint32_t i = 0; i < count; i++)
+        if (!air_canonical(&airs[i])) {  // the constraint kernel subtracts them from trace values
+            c->err = "AIR constant is not a canonical field element";
+            return XFG_INVALID_ARGUMENT;
+        }
+    const bool dev = (flags & XFG_TRACE_ON_DEVICE) != 0;
+    return guarded(c, [&]() -> int {
+        HIPCHK(hipSetDevice(c->device));
+        if (const char* m = dev ? device_traces_problem(c, traces, (size_t)count * 7 * n * 8) : nullptr) {
+            c->err = m;
+            return XFG_INVALID_ARGUMENT;
+        }
+        std::unique_ptr<Batch> bp(new Batch());
+        bp->jobs.resize(count);
+        bp->which.resize(count);
+        bp->refused.assign(count, 0);
+        bp->keys.assign(count, TRACE_KEY_VALID);
+        for (uint32_t i = 0; i < count; i++) {
+            bp->jobs[i].air = air_of(&airs[i]);
+            bp->which[i] = i;
+            statuses[i] = XFG_OK;
+        }
+        if (!dev) {
+            // all_canonical per proof on the host pool (the submitting thread starts every batch's latency)
+            u64* keys = bp->keys.data();
+            host_pool().parallel_for((int)count, [&](int i) { keys[i] = host_noncanonical_key(traces + (size_t)i * 7 * n, n); });
+            for (uint32_t i = 0; i < count; i++)
+                if (keys[i] != TRACE_KEY_VALID) {
+                    bp->refused[i] = statuses[i] = XFG_INVALID_ARGUMENT;
+                    c->err = "trace element is not a canonical field element";
+                }
+            c->stage_traces = true;
+        }
+        bp->trace.kind = dev ? TraceSrc::DEVICE : TraceSrc::HOST_STAGED;
+        bp->trace.p = traces;
+        bp->trace.validate = (flags & XFG_TRACE_VALIDATE) != 0;
+        bp->faults = faults;
+        if (outs) bp->outs.assign(outs, outs + count);
+        bp->out_lens = out_lens;
+        bp->statuses = statuses;
+        bp->n = n;
+        bp->o = o;
+        bind_tables(c, bp.get());
+        std::vector<Unit> units = split_units(c, (int)count);
+        *ticket = enqueue(c, std::move(bp), std::move(units));
+        return XFG_OK;
+    });
+}
+
+int xfg_prove_trace_batch(xfg_ctx* c, uint32_t count, const uint64_t* traces, uint32_t width, uint64_t n,
+                          const xfg_air_consts* airs, const xfg_options* opts, uint32_t flags, uint8_t* const* outs,
+                          size_t* out_lens, int* statuses, xfg_trace_fault* faults) {
+    uint64_t t = 0;
+    int r = xfg_prove_trace_batch_submit(c, count, traces, width, n, airs, opts, flags, outs, out_lens, statuses,
+                                         faults, &t);
+    if (r) return r;
+    return xfg_batch_wait(c, t);
+}
+
+int xfg_check_traces(xfg_ctx* c, uint32_t count, const uint64_t* traces, uint64_t n, const xfg_air_consts* airs,
+                     uint32_t flags, xfg_trace_fault* faults) {
+    if (!c) return XFG_INVALID_ARGUMENT;
+    c->err.clear();
+    if (!traces || !airs || !faults || count == 0) {
+        c->err = count == 0 ? "empty batch" : "null argument";
+        return XFG_INVALID_ARGUMENT;
+    }
+    if (count > 65535 || !is_pow2(n) || n < 8 || n > (1ULL << 32) || (flags & ~XFG_TRACE_ON_DEVICE)) {
+        c->err = "xfg_check_traces: at most 65535 traces of a power-of-two length from 8 to 2^32, flags 0 or "
+                 "XFG_TRACE_ON_DEVICE";
+        return XFG_INVALID_ARGUMENT;
+    }
+    for (uint32_t i = 0; i < count; i++)
+        if (!air_canonical(&airs[i])) {
+            c->err = "AIR constant is not a canonical field element";
+            return XFG_INVALID_ARGUMENT;
+        }
+    const bool dev = (flags & XFG_TRACE_ON_DEVICE) != 0;
+    return on_lane0(c, [&](Lane* L) -> int {
+        const size_t cells = (size_t)count * 7 * n;
+        if (const char* m = dev ? device_traces_problem(c, traces, cells * 8) : nullptr) {
+            c->err = m;
+            return XFG_INVALID_ARGUMENT;
+        }
+        L->trace.ensure(cells);
+        L->air.ensure(count);
+        L->tkeys.ensure(count);
+        std::vector<AirConst> ha(count);
+        for (uint32_t i = 0; i < count; i++) ha[i] = air_of(&airs[i]);
+        HIPCHK(hipMemcpy(L->air.p, ha.data(), count * sizeof(AirConst), hipMemcpyHostToDevice));
+        // the kernel works on the lane's copy (it canonicalises what it reports as >= p)
+        HIPCHK(hipMemcpyAsync(L->trace.p, traces, cells * 8, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                              L->stream));
+        launch_trace_check(L->trace.p, L->air.p, L->tkeys.p, (int)ilog2(n), (int)count, true, L->stream);
+        std::vector<u64> keys(count);
+        HIPCHK(hipMemcpyAsync(keys.data(), L->tkeys.p, count * 8, hipMemcpyDeviceToHost, L->stream));
+        HIPCHK(hipStreamSynchronize(L->stream));
+        for (uint32_t i = 0; i < count; i++) {
+            const u64* tr = traces + (size_t)i * 7 * n;
+            faults[i] = decode_trace_key(keys[i], ha[i], [&](uint32_t col, u64 step) {
+                return fetch_cell(tr, dev, (size_t)col * n + step);
+            });
+            if (faults[i].kind) c->err = trace_fault_text(faults[i]);
+        }
+        return XFG_OK;
+    });
 }
 
 int xfg_prepare(xfg_ctx* c, uint32_t count, uint64_t trace_length, const xfg_options* opts) {
@@ -1069,6 +1356,7 @@ int xfg_prepare(xfg_ctx* c, uint32_t count, uint64_t trace_length, const xfg_opt
             std::unique_ptr<Batch> bp(new Batch());
             bp->jobs.resize((size_t)nl * U);
             for (auto& j : bp->jobs) j.air = a;
+            bp->trace.size_staging = c->stage_traces;
             bp->n = n;
             bp->o = o;
             bind_tables(c, bp.get());

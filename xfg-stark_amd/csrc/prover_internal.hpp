@@ -63,6 +63,13 @@ struct Lane {
     // flags in the replay block, for the counters
     DBuf<unsigned char> const_col;
     const unsigned char* h_const_col = nullptr;
+    // caller-supplied traces (xfg_prove_trace_batch): tkeys [B] the check kernel's word per proof
+    // (launch_trace_check), h_tkeys the unit's words in the replay block; h_trace the pinned staging host
+    // traces are uploaded from (sized with the lane's buffers, so the upload is a true asynchronous DMA
+    // that never waits on the caller's pageable memory)
+    DBuf<u64> tkeys;
+    const u64* h_tkeys = nullptr;
+    HBuf<u64> h_trace;
     std::vector<DBuf<u64>> flayer;
     std::vector<DBuf<Digest>> fnodes;
     // pinned host staging
@@ -150,6 +157,9 @@ struct xfg_ctx {
     std::string err;
     bool timing = false;
     bool lde_probe = false;  // xfg_lde_probe state, inherited by lanes created later
+    // set by the first batch of host traces (xfg_prove_trace_batch): from then on xfg_prepare sizes
+    // every lane's pinned trace staging too
+    bool stage_traces = false;
     xfg::TablesHost tables;
     std::vector<std::unique_ptr<xfg::Lane>> lanes;
     // persistent lane workers: one host thread per lane pulls proof units from a FIFO shared by

@@ -25,7 +25,8 @@ _lib = C.CDLL(LIB_PATH)
 
 STATUS = {0: "OK", 1: "INVALID_BURN_AMOUNT", 2: "MINT_MISMATCH", 3: "ZERO_TX_HASH", 4: "BAD_RECIPIENT_LEN",
           5: "SHORT_SECRET", 6: "PROVER_ERROR", 7: "DEVICE_ERROR", 8: "BUFFER_TOO_SMALL", 9: "INVALID_ARGUMENT",
-          10: "VERIFY_FAILED"}
+          10: "VERIFY_FAILED", 11: "INVALID_TRACE"}
+TRACE_VALIDATE, TRACE_ON_DEVICE = 1, 2  # XFG_TRACE_* flags of xfg_prove_trace_batch
 
 
 class _Options(C.Structure):
@@ -50,6 +51,11 @@ class _ProofInfo(C.Structure):
                 ("num_unique_queries", C.c_uint32), ("num_fri_layers", C.c_uint32), ("remainder_len", C.c_uint32),
                 ("pow_nonce", C.c_uint64), ("trace_root", C.c_uint8 * 32), ("constraint_root", C.c_uint8 * 32),
                 ("ood_trace", C.c_uint64 * 14), ("ood_composition", C.c_uint64), ("size", C.c_size_t)]
+
+
+class _TraceFault(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("index", C.c_uint32), ("column", C.c_uint32), ("step", C.c_uint64),
+                ("expected", C.c_uint64), ("found", C.c_uint64)]
 
 
 _u64p = C.POINTER(C.c_uint64)
@@ -120,6 +126,13 @@ if hasattr(_lib, "xfg_debug_grind"):  # absent from builds older than the device
     _lib.xfg_debug_grind.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint64, C.c_uint64,
                                      C.c_uint32, C.c_uint32, _u64p]
     _lib.xfg_grind_probe.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), _u64p, _u64p]
+if hasattr(_lib, "xfg_prove_trace_batch"):  # absent from builds older than the trace batches (XFG_LIB A/B)
+    _lib.xfg_check_traces.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(_AirConsts),
+                                      C.c_uint32, C.POINTER(_TraceFault)]
+    _lib.xfg_prove_trace_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint64,
+                                           C.POINTER(_AirConsts), C.POINTER(_Options), C.c_uint32, C.POINTER(_u8p),
+                                           C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(_TraceFault)]
+    _lib.xfg_prove_trace_batch_submit.argtypes = _lib.xfg_prove_trace_batch.argtypes + [C.POINTER(C.c_uint64)]
 
 
 class XfgStarkError(Exception):
@@ -129,6 +142,38 @@ class XfgStarkError(Exception):
         super().__init__(message)
         self.status = status
         self.kind = STATUS.get(status, str(status))
+
+
+class TraceFault:
+    """xfg_trace_fault: what Trace::validate reports first for a trace. kind 1 = assertion `index` (0..7)
+    on main_trace(column, step), expected / found the asserted value and the cell; 2 = transition
+    constraint `index` (0..6) at `step`; 3 = the cell (column, step) = found is not a canonical field
+    element. str() is Winterfell's message."""
+    ASSERTION, TRANSITION, NONCANONICAL = 1, 2, 3
+
+    def __init__(self, kind, index, column, step, expected, found):
+        self.kind, self.index, self.column, self.step = kind, index, column, step
+        self.expected, self.found = expected, found
+
+    @classmethod
+    def _from_c(cls, f):
+        return cls(f.kind, f.index, f.column, f.step, f.expected, f.found) if f.kind else None
+
+    def astuple(self):
+        return (self.kind, self.index, self.column, self.step, self.expected, self.found)
+
+    def __eq__(self, other):
+        return isinstance(other, TraceFault) and other.astuple() == self.astuple()
+
+    def __str__(self):
+        if self.kind == self.ASSERTION:
+            return f"trace does not satisfy assertion main_trace({self.column}, {self.step}) == {self.expected}"
+        if self.kind == self.TRANSITION:
+            return f"main transition constraint {self.index} did not evaluate to ZERO at step {self.step}"
+        return "trace element is not a canonical field element"
+
+    def __repr__(self):
+        return "TraceFault(kind={}, index={}, column={}, step={}, expected={}, found={})".format(*self.astuple())
 
 
 class FieldExtension:
@@ -402,13 +447,16 @@ class PendingBatch:
     A batch is consumed once: by result() (which can be called again and returns the same list),
     by packed_into(), or -- for a batch written into a caller's record -- by record_ready()."""
 
-    def __init__(self, prover, ticket, buf, base, cap, outs, lens, sts, record=False, owner=None):
+    def __init__(self, prover, ticket, buf, base, cap, outs, lens, sts, record=False, owner=None, faults=None):
         self._p, self._t, self._buf, self._base, self._cap = prover, ticket, buf, base, cap
         self._outs, self._lens, self._sts = outs, lens, sts
         self._record = record  # proofs live in the caller's record: no pooled buffer to release
         # the object owning the caller's record: kept alive while the workers may still write into
         # it (until the batch has been waited for, here or in __del__)
         self._owner = owner
+        # a batch of caller-supplied traces (submit_traces): the xfg_trace_fault array the wait fills;
+        # owner then holds the traces (array or device tensor), which the lanes read until the wait
+        self._faults = faults
         self._res = None
         self._consumed = None  # name of the call that consumed the batch, if not result()
 
@@ -437,7 +485,10 @@ class PendingBatch:
             res = []
             for i in range(len(self._sts)):
                 if self._sts[i]:
-                    res.append(XfgStarkError(self._sts[i], STATUS.get(self._sts[i])))
+                    fault = TraceFault._from_c(self._faults[i]) if self._faults is not None else None
+                    err = XfgStarkError(self._sts[i], str(fault) if fault else STATUS.get(self._sts[i]))
+                    err.fault = fault  # TraceFault of an INVALID_TRACE / non-canonical proof, else None
+                    res.append(err)
                 else:
                     res.append(StarkProof(C.string_at(self._base + i * self._cap, self._lens[i])))
             self._release()
@@ -523,6 +574,7 @@ class XfgBurnMintProver:
     def __init__(self, security_parameter=128, device=0, proof_options=None):
         self._security_parameter = security_parameter
         self._options = proof_options or ProofOptions.reference()
+        self._device = device
         self._ctx = _lib.xfg_ctx_create(device)
         if not self._ctx:
             raise XfgStarkError(7, f"no HIP device {device} available for libxfgstark (no CPU fallback)")
@@ -658,6 +710,75 @@ class XfgBurnMintProver:
         if st:
             raise self._err(st)
         return PendingBatch(self, ticket.value, None, base, cap, outs, lens, sts, record=True, owner=owner)
+
+    def _trace_args(self, traces, airs):
+        """the C arguments of a batch of traces: (object to keep alive, pointer, count, n, airs array, flags)"""
+        import numpy as np
+        if hasattr(traces, "data_ptr"):  # a torch.Tensor (torch itself is not imported here)
+            t = traces
+            if t.device.type != "cuda" or (t.device.index or 0) != self._device:
+                raise XfgStarkError(9, f"traces tensor is on {t.device}, the prover on device {self._device}")
+            if str(t.dtype) not in ("torch.int64", "torch.uint64") or not t.is_contiguous():
+                raise XfgStarkError(9, "traces tensor must be contiguous with dtype int64 or uint64")
+            shape, keep, flags = tuple(t.shape), t, TRACE_ON_DEVICE
+            if len(shape) == 3 and t.numel():
+                import torch
+                torch.cuda.current_stream(t.device).synchronize()  # the data is complete before the lanes copy it
+            ptr = t.data_ptr()
+        else:
+            a = np.ascontiguousarray(np.asarray(traces, dtype=np.uint64))
+            shape, keep, flags, ptr = a.shape, a, 0, a.ctypes.data
+        if len(shape) != 3:
+            raise XfgStarkError(9, "traces: [count][7][n]")
+        count, width, n = shape
+        if len(airs) != count:
+            raise XfgStarkError(9, f"{count} traces, {len(airs)} AIR constants")
+        air_np = np.array([list(a[0]) + [a[1], a[2]] for a in airs], dtype=np.uint64).reshape(count, 14)
+        return (keep, air_np), ptr or None, count, width, n, air_np.ctypes.data_as(C.POINTER(_AirConsts)), flags
+
+    def submit_traces(self, traces, airs, validate=False):
+        """asynchronous prove_traces (xfg_prove_trace_batch_submit) -> PendingBatch; the traces (array or
+        tensor) are referenced by it until it has been waited for, and must not be written before then"""
+        keep, ptr, count, width, n, air_p, flags = self._trace_args(traces, airs)
+        o = self._options._c()
+        cap = _lib.xfg_proof_size_bound(n, C.byref(o)) if count else 0
+        buf = self._take_buffer(cap * count)
+        base = C.addressof(buf)
+        outs = (_u8p * count)(*[C.cast(base + i * cap, _u8p) for i in range(count)])
+        lens = (C.c_size_t * count)(*([cap] * count))
+        sts = (C.c_int * count)()
+        faults = (_TraceFault * count)()
+        ticket = C.c_uint64(0)
+        st = _lib.xfg_prove_trace_batch_submit(self._ctx, count, ptr, width, n, air_p, C.byref(o),
+                                               flags | (TRACE_VALIDATE if validate else 0), outs, lens, sts, faults,
+                                               C.byref(ticket))
+        if st:
+            self._free.append(buf)
+            raise self._err(st)
+        return PendingBatch(self, ticket.value, buf, base, cap, outs, lens, sts, owner=keep, faults=faults)
+
+    def prove_traces(self, traces, airs, validate=False):
+        """ExecutionTrace-level proving of a batch: traces = numpy uint64 array [count][7][n] or a
+        contiguous int64 / uint64 torch.Tensor of that shape on the prover's device, airs = count x
+        (pub_inputs[12], nullifier, commitment) -> list of StarkProof | XfgStarkError (per proof).
+        validate: Trace::validate on the device first; a trace that violates the AIR gives an
+        XfgStarkError of status 11 (INVALID_TRACE) whose .fault is the TraceFault and whose text is
+        Winterfell's message, the other proofs are unaffected.
+        A tensor's data_ptr() goes to the library as it is, so torch and the library must share one HIP
+        runtime: with a torch build that bundles its own, import torch before this package (the library
+        then binds to the runtime torch loaded); a pointer the library's runtime does not know is refused"""
+        return self.submit_traces(traces, airs, validate).result()
+
+    def check_traces(self, traces, airs):
+        """Trace::validate on the device alone (xfg_check_traces): -> list of TraceFault | None"""
+        keep, ptr, count, width, n, air_p, flags = self._trace_args(traces, airs)
+        if width != 7:
+            raise XfgStarkError(9, "XfgBurnMintAir traces have 7 columns")
+        faults = (_TraceFault * max(count, 1))()
+        st = _lib.xfg_check_traces(self._ctx, count, ptr, n, air_p, flags, faults)
+        if st:
+            raise self._err(st)
+        return [TraceFault._from_c(faults[i]) for i in range(count)]
 
     def _take_buffer(self, size):
         # output buffers are recycled. A new one is an anonymous mapping, not create_string_buffer:
