@@ -48,9 +48,13 @@ typedef enum {
     XFG_ZERO_TX_HASH = 3,        /* u64 LE of tx_prefix_hash[0..8] == 0 */
     XFG_BAD_RECIPIENT_LEN = 4,   /* recipient address not 20 bytes */
     XFG_SHORT_SECRET = 5,        /* secret shorter than 8 bytes (reference: error <4, panic 4..7) */
-    XFG_PROVER_ERROR = 6,        /* Winterfell prover error / options outside the supported set (FRI
-                                    folding factor not 2, 4, 8 or 16, a last FRI layer smaller than the
-                                    blowup, an NTT size without a kernel); also a proof whose bounded
+    XFG_PROVER_ERROR = 6,        /* Winterfell prover error / options outside the supported set (blowup
+                                    factor not a power of two in [2, 128]; at blowup 32, 64 or 128 an LDE
+                                    domain trace_length * blowup above 2^24, the message naming both and
+                                    the limit; FRI folding factor not 2, 4, 8 or 16; a last FRI layer
+                                    smaller than the blowup -- folding factors 2, 4, 16 at any blowup, every
+                                    factor at blowup 32, 64, 128; an NTT size without a kernel); also a
+                                    proof whose bounded
                                     proof-of-work search on the device found no nonce up to
                                     2^(grinding_factor + 8) ("proof-of-work search exhausted", probability
                                     e^-256; the other proofs of the batch are unaffected) */
@@ -64,7 +68,7 @@ typedef enum {
 /* winterfell::ProofOptions (0.8) */
 typedef struct {
     uint32_t num_queries;
-    uint32_t blowup_factor;
+    uint32_t blowup_factor;   /* a power of two in [2, 128]; above 16: trace_length * blowup_factor <= 2^24 */
     uint32_t grinding_factor;
     uint32_t field_extension; /* 1 = FieldExtension::None */
     uint32_t fri_folding_factor; /* 2, 4, 8 or 16 */
@@ -237,7 +241,8 @@ int xfg_selftest_field(uint64_t a, uint64_t b, uint64_t* out3);
 int xfg_set_timing(xfg_ctx* ctx, int enabled);
 int xfg_stage_times(const xfg_ctx* ctx, double* ms, const char** names, int max);
 /* times `iters` launches of the trace LDE kernels (7 columns x count proofs, resident device
- * buffers, HIP events on the context stream); returns average ms per launch set in *avg_ms */
+ * buffers, HIP events on the context stream); returns average ms per launch set in *avg_ms.
+ * blowup 2..128, above 16 with n * blowup <= 2^24 (else XFG_INVALID_ARGUMENT), as xfg_debug_lde */
 int xfg_bench_lde(xfg_ctx* ctx, uint32_t count, uint64_t n, uint32_t blowup, uint32_t iters, double* avg_ms);
 /* in-pipeline trace-LDE timing: HIP events around the trace LDE launch set of every proof unit
  * (on the lane stream that launches it). enabled = 1 resets and starts; enabled = 0 stops. The
@@ -245,6 +250,9 @@ int xfg_bench_lde(xfg_ctx* ctx, uint32_t count, uint64_t n, uint32_t blowup, uin
  * which skip the transform, are not counted) are returned either way. */
 int xfg_lde_probe(xfg_ctx* ctx, int enabled, double* total_ms, uint64_t* launch_sets, uint64_t* polys);
 /* kernel-level parity hooks (host buffers in/out) */
+/* forward LDE: coef [npoly][n] -> out [npoly][blowup n] in natural order, out[p][t + blowup m] =
+ * P_p(7 w_N^(t + blowup m)), N = blowup n. blowup a power of two in 2..128; 32, 64 and 128 run as blowup / 16
+ * blowup-16 transforms of twisted coefficients and need n * blowup <= 2^24 (else XFG_INVALID_ARGUMENT) */
 int xfg_debug_lde(xfg_ctx* ctx, const uint64_t* coef, uint32_t npoly, uint64_t n, uint32_t blowup, uint64_t* out);
 int xfg_debug_interpolate(xfg_ctx* ctx, const uint64_t* evals, uint32_t npoly, uint64_t n, int offset7,
                           uint64_t* out);
@@ -279,7 +287,7 @@ int xfg_debug_ood_deep(xfg_ctx* ctx, uint32_t count, uint64_t n, const uint64_t*
                        const uint64_t* zpts, const uint64_t* coeffs, uint64_t* ood_out, uint64_t* deep_out);
 /* constraint evaluation kernel of the prover on `count` instances, through the calls prove_lane
  * makes, through the same helper (launch_trace_lde in prover.hip: column interpolation, trace LDE at
- * `blowup`; then the host-built divisor table, the kernel):
+ * `blowup` -- 2..128, above 16 with n * blowup <= 2^24; then the host-built divisor table, the kernel):
  * trace [count][7][n] canonical, airs [count], coeffs [count][15][ext] = 7 transition, 7 step-0
  * boundary and the final-step boundary coefficient, E elements (ext 1 or 2 coordinates each);
  * ce [count][ext][2n] coordinate planes in natural CE-domain order (index i <-> x = 7 w_2n^i) */
@@ -308,7 +316,8 @@ int xfg_debug_coin_draws(xfg_ctx* ctx, const uint32_t seed[8], uint64_t counter,
                          int ok[2]);
 /* Merkle commitment of `count` LDEs as the prover runs it (leaf kernel, then the tree up to the root,
  * no transcript step), every stored node copied back. lde [count][nc][blowup][n], coset-major as
- * xfg_debug_lde's device output (row m of coset t at [t][m]); nc = 1, 2 or 7 columns, blowup 2..16,
+ * xfg_debug_lde's device output (row m of coset t at [t][m]); nc = 1, 2 or 7 columns, blowup 2..16 (the
+ * prover's instantiations for blowup 32, 64 and 128 are not reachable through this hook),
  * 8 <= n <= 2^24, both powers of two, count <= 65535. nodes_out [count][2n][32 bytes]: each proof's heap (slot 1 = root,
  * slot i = H(slot 2i || slot 2i+1)); slots [1, n) are defined -- the levels below them live in
  * registers only -- and every other slot is returned as 0xFF bytes. local_out [nentries][2 blowup][32]:

@@ -113,9 +113,10 @@ static void launch_coin_draw_test(const DevCoin& c0, int k, int ext, const u64* 
 // xfg_debug_lde / xfg_debug_lde_skip: skip (host, [npoly]) or nullptr
 static int debug_lde(xfg_ctx* c, const uint64_t* coef, uint32_t npoly, uint64_t n, uint32_t blowup, const uint8_t* skip,
                      uint64_t* out) {
-    if (!c || !coef || !out || !is_pow2(n) || !is_pow2(blowup) || n < 8 || blowup < 2 || blowup > 16)
+    if (!c || !coef || !out || !is_pow2(n) || !is_pow2(blowup) || n < 8 || blowup < 2 || blowup > 128)
         return XFG_INVALID_ARGUMENT;
-    if (!ntt_supported((int)ilog2(n), (int)ilog2(blowup), false)) return XFG_INVALID_ARGUMENT;
+    // (blowup 32, 64, 128: composed LDEs, n * blowup <= 2^24)
+    if (!lde_supported((int)ilog2(n), (int)ilog2(blowup))) return XFG_INVALID_ARGUMENT;
     return on_lane0(c, [&](Lane* L) -> int {
         const int logn = (int)ilog2(n), logbeta = (int)ilog2(blowup);
         const u64 N = n * blowup;
@@ -178,9 +179,9 @@ static int debug_interpolate(xfg_ctx* c, const uint64_t* evals, uint32_t npoly, 
 extern "C" {
 
 int xfg_bench_lde(xfg_ctx* c, uint32_t count, uint64_t n, uint32_t blowup, uint32_t iters, double* avg_ms) {
-    if (!c || !avg_ms || !is_pow2(n) || !is_pow2(blowup) || n < 8 || blowup < 2 || blowup > 16 || iters == 0)
+    if (!c || !avg_ms || !is_pow2(n) || !is_pow2(blowup) || n < 8 || blowup < 2 || blowup > 128 || iters == 0)
         return XFG_INVALID_ARGUMENT;
-    if (!ntt_supported((int)ilog2(n), (int)ilog2(blowup), false)) return XFG_INVALID_ARGUMENT;
+    if (!lde_supported((int)ilog2(n), (int)ilog2(blowup))) return XFG_INVALID_ARGUMENT;
     return on_lane0(c, [&](Lane* L) -> int {
         const int logn = (int)ilog2(n), logbeta = (int)ilog2(blowup);
         const u64 N = n * blowup;
@@ -393,7 +394,7 @@ int xfg_debug_constraint_eval(xfg_ctx* c, uint32_t count, uint64_t n, uint32_t b
     if (!c) return XFG_INVALID_ARGUMENT;
     c->err.clear();
     if (!trace || !airs || !coeffs || !ce || count == 0 || !is_pow2(n) || n < 8 || !is_pow2(blowup) || blowup < 2 ||
-        blowup > 16 || (ext != 1 && ext != 2)) {
+        blowup > 128 || wide_lde_too_large(n, blowup) || (ext != 1 && ext != 2)) {
         c->err = "xfg_debug_constraint_eval: null or unsupported argument";
         return XFG_INVALID_ARGUMENT;
     }

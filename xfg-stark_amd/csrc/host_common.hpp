@@ -28,17 +28,24 @@ static inline Opts to_opts(const xfg_options* o) {
     return Opts{o->num_queries, o->blowup_factor, o->grinding_factor, o->field_extension, o->fri_folding_factor,
                 o->fri_remainder_max_degree};
 }
+// blowup 32, 64, 128 (LDEs composed of blowup-16 transforms): n * beta is limited to the largest LDE proven
+// at blowup 16, 2^20 x 16
+constexpr u64 WIDE_LDE_MAX = 1ULL << 24;
+static inline bool wide_lde_too_large(u64 n, u64 beta) { return beta > 16 && n > WIDE_LDE_MAX / beta; }
+// check_options' answer to that rule (check_request names the sizes when it is this one that failed)
+constexpr const char* WIDE_LDE_REFUSAL = "blowup factors above 16 need an LDE domain of at most 2^24 points";
 // ProofOptions::new validation (winter-air 0.8) + what this GPU path implements
 static inline const char* check_options(u64 n, const Opts& o) {
     if (!is_pow2(n) || n < 8) return "trace length must be a power of two and at least 8";
     if (n > (1ULL << 21)) return "trace length above 2^21 is not supported";
-    if (!is_pow2(o.beta) || o.beta < 2 || o.beta > 16) return "blowup factor must be a power of two in [2, 16]";
+    if (!is_pow2(o.beta) || o.beta < 2 || o.beta > 128) return "blowup factor must be a power of two in [2, 128]";
     if (o.q < 1 || o.q > 255) return "number of queries must be in [1, 255]";
     if (o.grind > 32) return "grinding factor cannot be greater than 32";
     if (o.ext != 1 && o.ext != 2) return "field extension must be None (1) or Quadratic (2)";
     if (o.fold != 2 && o.fold != 4 && o.fold != 8 && o.fold != 16) return "FRI folding factor must be 2, 4, 8 or 16";
     if (o.remdeg > 255 || !is_pow2(o.remdeg + 1)) return "FRI remainder max degree must be one less than a power of two";
     if (o.q >= n * o.beta) return "number of queries must be smaller than the LDE domain size";
+    if (wide_lde_too_large(n, o.beta)) return WIDE_LDE_REFUSAL;
     return nullptr;
 }
 static inline unsigned num_fri_layers(u64 N, const Opts& o) {
@@ -54,6 +61,12 @@ static inline unsigned num_fri_layers(u64 N, const Opts& o) {
 static inline u64 last_fri_domain(u64 N, const Opts& o) {
     for (unsigned k = num_fri_layers(N, o); k > 0; k--) N /= o.fold;
     return N;
+}
+// A last FRI layer smaller than the blowup factor leaves the remainder no coefficient: refused by the prover
+// and by both verifiers for the folding factors 2, 4 and 16 at every blowup and for every folding factor
+// at blowup 32, 64 and 128 (what factor 8 does on such a shape up to blowup 16 is as it always was)
+static inline bool last_layer_below_blowup(u64 n, const Opts& o) {
+    return (o.fold != 8 || o.beta > 16) && last_fri_domain(n * o.beta, o) < o.beta;
 }
 // Context::to_elements (TraceInfo, modulus bytes, options) -- DESIGN.md "Transcript"
 static inline void context_elements(u64 n, const Opts& o, u64* e) {

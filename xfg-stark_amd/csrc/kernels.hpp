@@ -52,7 +52,10 @@ struct Tables {
 // ---- NTT (four-step, natural order in/out) ----
 // forward LDE: coef[poly][n] -> out[poly][beta][n] (coset-major: out[p][t][m] = P(7 w_N^(t + beta m)))
 // skip [npoly] (device, or nullptr): polynomials with a non-zero byte are not transformed and their
-// planes of out are left untouched (launch_const_fill writes them)
+// planes of out are left untouched (launch_const_fill writes them).
+// beta = 2..16 is one transform; 32, 64 and 128 (N <= 2^24) run as beta / 16 blowup-16 transforms of twisted
+// coefficients whose planes land in the same layout (lde_plan, ntt_plan.hpp). scratch: npoly * beta * n words;
+// T.tw must reach N entries and T.fs hold the tables of (logn, min(logbeta, 4)) (ensure_fourstep)
 void launch_lde(const u64* coef, u64 coef_stride, u64* out, u64* scratch, int npoly, int logn, int logbeta,
                 const Tables& T, hipStream_t s, const unsigned char* skip = nullptr);
 // generator of the four-step table for (logn, logbeta) (inverse: logbeta = -1; fourstep_size entries)
@@ -110,7 +113,7 @@ struct DeepCoinStep {
 // step `cs` on the root. Which kernels run, and the level each stops at, is merkle.hip's business.
 // LDE commitment of npoly trees over lde [npoly][nc][beta][n] (coset-major): nodes [npoly][2n], of which
 // the levels from the row pairs up are stored (heap [1, n)); the subtree over the beta leaves of row m
-// tops out at heap node n + m and stays in registers. nc in {1, 2, 7}, beta in {2, 4, 8, 16}: any
+// tops out at heap node n + m and stays in registers. nc in {1, 2, 7}, beta a power of two in 2..128: any
 // other pair throws std::invalid_argument
 void launch_merkle_lde(const u64* lde, int nc, Digest* nodes, int npoly, int logn, int logbeta, hipStream_t s,
                        const CoinStep& cs = CoinStep{});

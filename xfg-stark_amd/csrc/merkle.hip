@@ -5,7 +5,7 @@
 // Heap layout per tree: nodes[1] = root, nodes[i] = H(nodes[2i] || nodes[2i+1]), leaf k at L + k
 // (MerkleTree::new / build_merkle_nodes, winter-crypto 0.8.3). For the LDE commitments only the
 // levels >= log2(beta) + 1 are stored (heap [1, n)): the 2^log2(beta) leaves of LDE row m (one per
-// coset, coset-major layout) form a register-resident subtree whose top is heap node n + m. The
+// coset, coset-major layout; beta = 2 .. 128) form a register-resident subtree whose top is heap node n + m. The
 // few leaves / low nodes a proof opens are recomputed from the LDE by open_rows_kernel. A tree of
 // L leaf slots lives in 2 L digests (node stride 2n for an LDE, 2 rows for a FRI layer).
 //
@@ -105,6 +105,25 @@ __device__ __forceinline__ Digest lde_subtree(const u64* base, u64 n, u64 m) {
     }
 }
 
+// The same subtree for 2^LOG > 16 leaves (blowup 32, 64, 128), leaves t0 .. t0 + 2^LOG - 1: the levels above
+// the 16-leaf subtrees are two-trip loops that stay rolled, one inside the other, so the code is that of one
+// unrolled 16-leaf subtree and a thread holds one pending digest per level (unrolled through all seven
+// levels the three column counts took minutes to compile). Up to 16 leaves this is lde_subtree itself.
+template <int NC, int LOGB, int LOG>
+__device__ __forceinline__ Digest lde_subtree_wide(const u64* base, u64 n, u64 m, int t0) {
+    if constexpr (LOG <= 4) {
+        return lde_subtree<NC, LOGB, LOG, 0>(base + (u64)t0 * n, n, m);
+    } else {
+        Digest l, d;
+#pragma unroll 1
+        for (int i = 0; i < 2; i++) {
+            d = lde_subtree_wide<NC, LOGB, LOG - 1>(base, n, m, t0 + (i << (LOG - 1)));
+            if (i == 0) l = d;
+        }
+        return b3_merge(l, d);
+    }
+}
+
 // one LDE row per thread, min(256, n) rows per block: the row's 2^LOGB-leaf subtree (top at heap level
 // log2(beta), not stored), then through LDS the row-pair level (heap n/2 + m/2) and one more (n/4 + m/4):
 // 256 rows -> 64 nodes per block, n/4 left for the levels above. Against two rows per thread (the
@@ -119,7 +138,7 @@ __global__ __launch_bounds__(256) void leaves_row_kernel(const u64* lde, Digest*
     const int proof = blockIdx.y;
     const u64 m = (u64)blockIdx.x * blockDim.x + threadIdx.x;  // grid covers n exactly
     const u64* base = lde + (u64)proof * NC * (1 << LOGB) * n;
-    Digest d = lde_subtree<NC, LOGB, LOGB, 0>(base, n, m);
+    Digest d = lde_subtree_wide<NC, LOGB, LOGB>(base, n, m, 0);
     block_tree_up(d, nodes_all + (u64)proof * node_stride, n, lds, blockDim.x / 4);
 }
 
@@ -139,7 +158,7 @@ __global__ __launch_bounds__(256) void leaves_row2_kernel(const u64* lde, Digest
     const int proof = blockIdx.y, t = threadIdx.x, h = t & ((1 << LOGL) - 1), rl = t >> LOGL;
     const u64 m = (u64)blockIdx.x * RB + rl;
     const u64* base = lde + (u64)proof * NC * (1 << LOGB) * n + (u64)h * (1 << (LOGB - LOGL)) * n;
-    Digest d = lde_subtree<NC, LOGB, LOGB - LOGL, 0>(base, n, m);
+    Digest d = lde_subtree_wide<NC, LOGB, LOGB - LOGL>(base, n, m, 0);
 #pragma unroll
     for (int k = 0; k < LOGL; k++) {
         Digest r;
@@ -159,12 +178,18 @@ __global__ __launch_bounds__(256) void leaves_row2_kernel(const u64* lde, Digest
 // per entry instead of the 2^(LOGB+1) - 1 one lane ran in sequence (a lone proof waits on them).
 // Every lane of a group merges at every level (no divergence around the shuffles); the lanes with
 // t % 2^k == 0 hold level k's nodes and store them to the local heap (slot 1 = top).
+// Blowup 128 has more leaves per row than a wave has lanes: there a lane takes the two leaves 2l, 2l + 1
+// and their parent (2^LPL leaves per lane, 2^LOGL = 64 lanes per entry), and the shuffles start one level up.
+template <int LOGB>
+constexpr int open_lanes_log() { return LOGB < 6 ? LOGB : 6; }
 template <int NC, int LOGB>
 __global__ __launch_bounds__(64) void open_rows_kernel(const u64* lde, const u64* entries, u64 count, Digest* out,
                                                        int logn) {
+    constexpr int LOGL = open_lanes_log<LOGB>(), LPL = LOGB - LOGL;
+    static_assert(LPL <= 1, "at most two leaves per lane");
     const u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    const u64 e = g >> LOGB;
-    const int t = (int)(g & ((1 << LOGB) - 1));
+    const u64 e = g >> LOGL;
+    const int t = (int)(g & ((1 << LOGL) - 1)) << LPL;  // the lane's (first) leaf
     if (e >= count) return;  // whole groups: count is per entry, groups never straddle a wave
     const u64 n = 1ULL << logn, ent = entries[e];
     const u64 proof = ent >> logn, m = ent & (n - 1);
@@ -175,18 +200,26 @@ __global__ __launch_bounds__(64) void open_rows_kernel(const u64* lde, const u64
     for (int c = 0; c < NC; c++) row[c] = base[((u64)c * (1 << LOGB) + t) * n + m];
     Digest d = b3_hash_elems<NC>(row);
     local[(1 << LOGB) + t] = d;
+    if constexpr (LPL == 1) {
 #pragma unroll
-    for (int k = 1; k <= LOGB; k++) {
+        for (int c = 0; c < NC; c++) row[c] = base[((u64)c * (1 << LOGB) + t + 1) * n + m];
+        const Digest d1 = b3_hash_elems<NC>(row);
+        local[(1 << LOGB) + t + 1] = d1;
+        d = b3_merge(d, d1);
+        local[((1 << LOGB) + t) >> 1] = d;
+    }
+#pragma unroll
+    for (int k = LPL + 1; k <= LOGB; k++) {
         Digest r;
 #pragma unroll
-        for (int w = 0; w < 8; w++) r.w[w] = __shfl_xor(d.w[w], 1 << (k - 1));
+        for (int w = 0; w < 8; w++) r.w[w] = __shfl_xor(d.w[w], 1 << (k - 1 - LPL));
         d = b3_merge(d, r);
         if ((t & ((1 << k) - 1)) == 0) local[((1 << LOGB) + t) >> k] = d;
     }
 }
 
 // The one (columns, log2 blowup) dispatch of the three kernel families above: f(NC, LOGB) with both as
-// integral constants, for nc in {7, 2, 1} and blowup 2..16. Any other pair has no kernel: refused,
+// integral constants, for nc in {7, 2, 1} and blowup 2..128. Any other pair has no kernel: refused,
 // never skipped (the ABI entries validate both before anything is launched).
 template <int V>
 using IntC = std::integral_constant<int, V>;
@@ -197,6 +230,9 @@ static bool with_logbeta(int logbeta, F f) {
         case 2: f(IntC<NC>{}, IntC<2>{}); return true;
         case 3: f(IntC<NC>{}, IntC<3>{}); return true;
         case 4: f(IntC<NC>{}, IntC<4>{}); return true;
+        case 5: f(IntC<NC>{}, IntC<5>{}); return true;
+        case 6: f(IntC<NC>{}, IntC<6>{}); return true;
+        case 7: f(IntC<NC>{}, IntC<7>{}); return true;
         default: return false;
     }
 }
@@ -212,7 +248,8 @@ static void with_nc_logbeta(int nc, int logbeta, F f) {
 void launch_open_rows(const u64* lde, int nc, const u64* entries, u64 count, Digest* out, int logn, int logbeta,
                       hipStream_t s) {
     if (!count) return;
-    dim3 g((unsigned)(((count << logbeta) + 63) / 64)), b(64);
+    const int logl = logbeta < 6 ? logbeta : 6;  // lanes per entry (open_lanes_log)
+    dim3 g((unsigned)(((count << logl) + 63) / 64)), b(64);
     with_nc_logbeta(nc, logbeta, [&](auto NC, auto LB) {
         hipLaunchKernelGGL((open_rows_kernel<decltype(NC)::value, decltype(LB)::value>), g, b, 0, s, lde, entries, count, out, logn);
     });

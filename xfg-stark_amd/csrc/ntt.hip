@@ -282,6 +282,8 @@ struct NttArgs {
     u64* out;
     u64 in_stride, out_stride;
     int logn, logR, logC;
+    u64 out_plane;  // forward: words between the output planes of a polynomial's consecutive cosets (n, or
+                    // g n for sub-transform u of a composed LDE, whose `out` starts at plane u: lde_plan)
     int logbeta;  // forward: 2^logbeta cosets
     int off7;     // inverse: scale coefficient k by 7^-k
     u64 scale;    // inverse: n^-1
@@ -299,6 +301,11 @@ struct NttArgs {
     // wave-uniform (poly comes from the block index); tested before a block's first barrier and after
     // the renumbering that yields poly
     __device__ bool skipped(int poly) const { return skip && skip[poly]; }
+    // forward: output plane of pt = poly * beta + t (polynomials out_stride apart, cosets out_plane apart;
+    // pt * n for a direct LDE). The inverse passes address `out` themselves
+    __device__ u64* plane_out(int pt) const {
+        return out + (u64)(pt >> logbeta) * out_stride + (u64)(pt & ((1 << logbeta) - 1)) * out_plane;
+    }
 };
 
 // Workgroups are dealt round-robin over the 8 XCDs, each with its own L2. When a pass writes less
@@ -657,7 +664,7 @@ __global__ __launch_bounds__(256, 3) void ntt_pass_b_r1024(NttArgs a) {
     for (int r = 0; r < R1; r++) yv[r] = buf_ld(ry, vy, ((u32)r << 15) * 8);  // column j0 + 32 r: 4 tiles further
     __syncthreads();
     auto ldg = [&](int, int, int o) -> u64 { return yv[o / G1]; };
-    const auto ro = buf_rsrc(a.out + (u64)pt * n + k10);
+    const auto ro = buf_rsrc(a.plane_out(pt) + k10);
     auto stg = [&](int, int seq, int base, int stride, u64* v) {  // the last butterfly level made v canonical
         store_pairs_buf<RR>(v, ro, ((u32)(seq & ~1) + ((u32)base << a.logR)) * 8, ((u32)stride << a.logR) * 8);
     };
@@ -716,7 +723,7 @@ __global__ __launch_bounds__(1 << LOGT) void ntt_pass_b(NttArgs a) {
         const u64 i = ((u64)(k10 + seq) << LOGC) + j + o;
         return tqb ? gl_mul(y[i], tqb[i]) : y[i];
     };
-    const auto rout = buf_rsrc(a.out + (u64)pt * n + k10);
+    const auto rout = buf_rsrc(a.plane_out(pt) + k10);
     auto stg = [&](int, int seq, int base, int stride, u64* v) {
 #pragma unroll
         for (int r = 0; r < RR; r++) {
@@ -780,7 +787,7 @@ __global__ __launch_bounds__(1 << LOGT) void ntt_pass_b_tq(NttArgs a) {
     }
     __syncthreads();
     auto ldg = [&](int, int, int o) -> u64 { return gl_mul(yv[o / G1], tv[o / G1]); };
-    const auto rout = buf_rsrc(a.out + (u64)pt * n + k10);
+    const auto rout = buf_rsrc(a.plane_out(pt) + k10);
     auto stg = [&](int, int seq, int base, int stride, u64* v) {  // the last butterfly level made v canonical
         // (16-byte paired stores, store_pairs_buf, measured neutral here: profiles/r05/tqp_ab.txt)
 #pragma unroll
@@ -842,7 +849,7 @@ __global__ __launch_bounds__(1 << LOGT, MINW) void ntt_pass_b_pers(NttArgs a, in
             continue;
         }
         auto ldg = [&](int, int, int o) -> u64 { return yv[o / G1]; };
-        u64* out = a.out + (u64)pt * n + k10;
+        u64* out = a.plane_out(pt) + k10;
         auto stg = [&](int, int seq, int base, int stride, u64* v) {
             u64 o[RR];
 #pragma unroll
@@ -1032,16 +1039,46 @@ void launch_const_fill(const unsigned char* flags, const u64* src, u64 src_strid
                        dim3(256), 0, s, flags, src, src_stride, coef, lde, n, lde ? logbeta : 0);
 }
 
+// ---------------------------------------------------------------- blowup 32, 64, 128: the twist
+// tw[u - 1][poly][j] = coef[poly][j] w_N^(u j) for the sub-transforms u = 1 .. g - 1 of a composed LDE
+// (lde_plan, ntt_plan.hpp): one multiply per coefficient and sub-transform, canonical in and out. u j <
+// g n = N / 16, so every power is an entry of the master table (2^LM >= N, checked by launch_lde).
+// Flagged polynomials are left alone: their sub-transforms return at once as well.
+// grid (ceil(n / 256), npoly, g - 1)
+__global__ __launch_bounds__(256) void lde_twist_kernel(const u64* coef, u64 coef_stride, u64* tw, int logn, int logN,
+                                                        const unsigned char* skip, Tables T) {
+    const u64 n = 1ULL << logn, j = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    const u64 poly = blockIdx.y, u = blockIdx.z + 1;
+    if (j >= n || (skip && skip[poly])) return;
+    tw[((u - 1) * gridDim.y + poly) * n + j] = gl_mul(coef[poly * coef_stride + j], tw_get(T, logN, u * j, false));
+}
+
+// Every forward LDE of the prover and of the debug / bench entries: the direct transform up to blowup 16,
+// g = beta / 16 of them on twisted coefficients past it (lde_plan). `scratch` holds npoly beta n words.
 void launch_lde(const u64* coef, u64 coef_stride, u64* out, u64* scratch, int npoly, int logn, int logbeta,
                 const Tables& T, hipStream_t s, const unsigned char* skip) {
-    NttArgs a{coef, scratch, out, coef_stride, 0, logn};  // in, y, out, in_stride, out_stride, logn
-    a.logbeta = logbeta;
-    a.skip = skip;
-    a.T = T;
-    const TableKind k = T.fs ? table_kind(logn, logbeta) : TableKind::none;
-    a.t4 = k == TableKind::fourstep ? T.fs->fwd[logn][logbeta] : nullptr;
-    a.pt = a.t4 ? a.t4 + fourstep_main(logn, logbeta) : (k == TableKind::pass_only ? T.fs->pass_fwd[logn][logbeta] : nullptr);
-    ntt_run(a, npoly, false, s);
+    const LdePlan lp = lde_plan(logn, logbeta, npoly);
+    if (!lp.ok) throw std::runtime_error("forward LDE of 2^" + std::to_string(logn) + " x 2^" + std::to_string(logbeta) + " has no kernel");
+    const u64 n = 1ULL << logn;
+    const int lb = lp.sub_logbeta;
+    u64* twisted = scratch + lp.twist_off;
+    if (lp.groups > 1) {
+        if (T.LM < logn + logbeta) throw std::runtime_error("forward LDE: the root-of-unity table is smaller than the LDE domain");
+        hipLaunchKernelGGL(lde_twist_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)npoly, (unsigned)(lp.groups - 1)), dim3(256),
+                           0, s, coef, coef_stride, twisted, logn, logn + logbeta, skip, T);
+    }
+    const TableKind k = T.fs ? table_kind(logn, lb) : TableKind::none;
+    for (int u = 0; u < lp.groups; u++) {
+        // in, y, out, in_stride, out_stride, logn: sub-transform u starts at plane u (lde_coset)
+        NttArgs a{u ? twisted + (u64)(u - 1) * npoly * n : coef, scratch, out + (u64)u * n, u ? n : coef_stride, n << logbeta, logn};
+        a.out_plane = lp.out_plane;
+        a.logbeta = lb;
+        a.skip = skip;
+        a.T = T;
+        a.t4 = k == TableKind::fourstep ? T.fs->fwd[logn][lb] : nullptr;
+        a.pt = a.t4 ? a.t4 + fourstep_main(logn, lb) : (k == TableKind::pass_only ? T.fs->pass_fwd[logn][lb] : nullptr);
+        ntt_run(a, npoly, false, s);
+    }
 }
 
 void launch_interpolate(const u64* evals, u64 in_stride, u64* out, u64 out_stride, u64* scratch, int npoly, int logn,

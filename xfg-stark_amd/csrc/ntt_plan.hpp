@@ -266,4 +266,44 @@ constexpr bool ntt_supported(int logn, int logbeta, bool inverse) {
     return ntt_plan(logn, logbeta, inverse, 1, t4, inverse ? t4 : k != TableKind::none, 256).ok;
 }
 
+// ---------------------------------------------------------------- blowup 32, 64, 128: composed LDEs
+// A blowup beta > 16 is g = beta / 16 blowup-16 transforms. With N = beta n and w_(16 n) = w_N^g, the
+// blowup-16 LDE of the twisted coefficients c_j w_N^(u j) evaluates P at 7 w_N^(u + g (t' + 16 m)): its coset
+// t' is the natural coset t = u + g t' of the blowup-beta LDE (lde_coset). Sub-transform u therefore writes
+// its 16 planes g n words apart starting at plane u (NttArgs::out_plane), which leaves the output in the
+// same coset-major layout [poly][t][m], t < beta, that every consumer of a direct LDE reads.
+// Scratch (words, from the start of the caller's buffer): the pass intermediate of one sub-transform
+// [npoly][16][n], shared by the g of them, then the twisted coefficients of u = 1 .. g - 1 [g - 1][npoly][n]
+// (u = 0 reads the caller's coefficients); (15 + g) npoly n words in all, within the beta npoly n every
+// caller sizes its LDE scratch to.
+constexpr int LDE_DIRECT_MAX_LOGBETA = 4, LDE_MAX_LOGBETA = 7;
+constexpr int LDE_COMPOSED_MAX_LOG = 24;  // log2 of the largest composed LDE (the largest LDE of any kind)
+struct LdePlan {
+    bool ok;              // false: nothing may be launched
+    int sub_logbeta;      // log2 blowup of each sub-transform
+    int groups;           // g sub-transforms (1: the direct LDE, nothing is twisted)
+    uint64_t out_plane;   // words between a sub-transform's consecutive output planes: g n
+    uint64_t twist_off;   // first word of the twisted coefficients in the scratch buffer
+    uint64_t scratch_words;
+};
+constexpr LdePlan lde_plan(int logn, int logbeta, int npoly) {
+    LdePlan p{};
+    if (logn < 1 || logn > 30 || logbeta < 0 || npoly < 1) return p;
+    const uint64_t n = 1ULL << logn, np = (uint64_t)npoly;
+    if (logbeta <= LDE_DIRECT_MAX_LOGBETA) return {true, logbeta, 1, n, np << (logn + logbeta), np << (logn + logbeta)};
+    if (logbeta > LDE_MAX_LOGBETA || logn + logbeta > LDE_COMPOSED_MAX_LOG) return p;
+    if (!ntt_supported(logn, LDE_DIRECT_MAX_LOGBETA, false)) return p;
+    const int g = 1 << (logbeta - LDE_DIRECT_MAX_LOGBETA);
+    const uint64_t y = np << (logn + LDE_DIRECT_MAX_LOGBETA);
+    return {true, LDE_DIRECT_MAX_LOGBETA, g, (uint64_t)g << logn, y, y + (uint64_t)(g - 1) * np * n};
+}
+// log2 blowup of the tables a forward LDE runs on (those of its sub-transforms)
+constexpr int lde_table_logbeta(int logbeta) { return logbeta > LDE_DIRECT_MAX_LOGBETA ? LDE_DIRECT_MAX_LOGBETA : logbeta; }
+// natural coset of plane t' of sub-transform u
+constexpr int lde_coset(const LdePlan& p, int u, int tsub) { return u + p.groups * tsub; }
+// whether a forward LDE of this shape can run at all (direct or composed)
+constexpr bool lde_supported(int logn, int logbeta) {
+    return logbeta <= LDE_DIRECT_MAX_LOGBETA ? ntt_supported(logn, logbeta, false) : lde_plan(logn, logbeta, 1).ok;
+}
+
 }  // namespace xfg

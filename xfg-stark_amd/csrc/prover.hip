@@ -101,6 +101,7 @@ Tables tables_of(xfg_ctx* c) {
 // Returns false when one is missing.
 static bool fourstep_ready(xfg_ctx* c, int logn, int logbeta) {
     const FourStep& f = c->tables.fs;
+    logbeta = lde_table_logbeta(logbeta);
     const TableKind k = table_kind(logn, logbeta);
     if (k == TableKind::fourstep && !f.fwd[logn][logbeta]) return false;
     if (k == TableKind::pass_only && !f.pass_fwd[logn][logbeta]) return false;
@@ -120,6 +121,8 @@ void ensure_fourstep(xfg_ctx* c, int logn, int logbeta) {
         return (const u64*)b.p;
     };
     FourStep& f = c->tables.fs;
+    // a composed LDE (blowup 32, 64, 128) runs on the tables of its blowup-16 sub-transforms
+    logbeta = lde_table_logbeta(logbeta);
     const TableKind k = table_kind(logn, logbeta);
     if (k == TableKind::fourstep && !f.fwd[logn][logbeta]) f.fwd[logn][logbeta] = build(logn, logbeta);
     if (k == TableKind::pass_only && !f.pass_fwd[logn][logbeta]) {
@@ -711,6 +714,10 @@ static int unit_size() {
     static const int v = std::max(1, env_int("XFG_UNIT", 32));
     return v;
 }
+// past blowup 16 a unit holds 16 / beta as many proofs, so that a lane's device workspace (the LDE buffers
+// and their scratch, the twisted coefficients of the composed LDE among it) grows no faster than at blowup
+// 16. Scheduling only: the unit size plays no part in the proof bytes
+static int unit_size(u64 beta) { return beta > 16 ? std::max(1, (int)(unit_size() * 16 / beta)) : unit_size(); }
 
 // smallest unit a queued unit is split into when lanes would otherwise idle (0: never split).
 // 16 (a 32-proof unit splits once): with the host tail on the pool, same box, 4 interleaved 20-step
@@ -844,11 +851,11 @@ static void bind_tables(xfg_ctx* c, Batch* b) {
     b->ce_div = ensure_ce_table(c, (int)ilog2(b->n));
 }
 
-// units of unit_size() proofs (the whole batch as one unit in timing mode, so the per-stage
+// units of unit_size(beta) proofs (the whole batch as one unit in timing mode, so the per-stage
 // times describe one launch set of the batch)
-static std::vector<Unit> split_units(xfg_ctx* c, int B) {
+static std::vector<Unit> split_units(xfg_ctx* c, int B, u64 beta) {
     std::vector<Unit> u;
-    const int U = c->timing ? std::max(1, B) : unit_size();
+    const int U = c->timing ? std::max(1, B) : unit_size(beta);
     for (int b0 = 0; b0 < B; b0 += U) u.push_back(Unit{nullptr, b0, std::min(B, b0 + U), -1});
     return u;
 }
@@ -991,6 +998,8 @@ size_t xfg_proof_size_bound(uint64_t n, const xfg_options* opts) {
     if (!opts || !is_pow2(n)) return 0;
     Opts o = to_opts(opts);
     if (o.fold < 2 || !is_pow2(o.fold) || o.beta == 0 || !is_pow2(o.beta)) return 0;
+    // no blowup above 128; past 16 the LDE domain is limited (check_options)
+    if (o.beta > 128 || wide_lde_too_large(n, o.beta)) return 0;
     return proof_size_bound(ProofShape(n, o), o);
 }
 
@@ -1011,12 +1020,16 @@ int xfg_burn_air_consts(const xfg_burn_inputs* in, xfg_air_consts* out) {
 static int check_request(xfg_ctx* c, u64 n, const Opts& o) {
     if (const char* m = check_options(n, o)) {
         c->err = std::string("Prover error: ") + m;
+        if (!strcmp(m, WIDE_LDE_REFUSAL))  // the last rule: n and beta have passed theirs
+            c->err = "Prover error: trace length " + std::to_string(n) + " at blowup factor " + std::to_string(o.beta) +
+                     " is an LDE domain of " + std::to_string(n * o.beta) + " points; blowup factors above 16 are limited to " +
+                     std::to_string(WIDE_LDE_MAX) + " (2^24)";
         return XFG_PROVER_ERROR;
     }
     const ProofShape sh(n, o);
-    // folding factors 2, 4, 16: a last layer smaller than the blowup leaves the remainder no coefficient
-    // (what factor 8 does on such a shape is as it was)
-    if (o.fold != 8 && sh.D[sh.nl] < sh.beta) {
+    // a last layer smaller than the blowup leaves the remainder no coefficient (last_layer_below_blowup:
+    // folding factors 2, 4, 16, and every factor past blowup 16)
+    if (last_layer_below_blowup(n, o)) {
         c->err = "Prover error: folding factor " + std::to_string(o.fold) + " takes the " + std::to_string(sh.N) +
                  "-point LDE domain down to a last FRI layer of " + std::to_string(sh.D[sh.nl]) +
                  ", smaller than the blowup factor " + std::to_string(sh.beta) + ": the remainder would be empty";
@@ -1025,7 +1038,7 @@ static int check_request(xfg_ctx* c, u64 n, const Opts& o) {
     const u64 rem = sh.nl > 0 ? sh.D[sh.nl] : 0;  // size the FRI remainder is interpolated at
     const char* what = nullptr;
     u64 size = 0;
-    if (!ntt_supported(sh.logn, sh.logbeta, false) || !ntt_supported(sh.logn, 0, true)) what = "", size = n;
+    if (!lde_supported(sh.logn, sh.logbeta) || !ntt_supported(sh.logn, 0, true)) what = "", size = n;
     else if (!ntt_supported(sh.logn + 1, 0, true)) what = "", size = 2 * n;
     else if (sh.nl > 0 && !ntt_supported((int)ilog2(rem), 0, true)) what = " (the FRI remainder)", size = rem;
     if (!what) return XFG_OK;
@@ -1116,7 +1129,7 @@ int xfg_prove_batch_submit(xfg_ctx* c, uint32_t count, const xfg_burn_inputs* in
         bp->n = n;
         bp->o = o;
         bind_tables(c, bp.get());
-        std::vector<Unit> units = split_units(c, (int)bp->jobs.size());
+        std::vector<Unit> units = split_units(c, (int)bp->jobs.size(), o.beta);
         *ticket = enqueue(c, std::move(bp), std::move(units));
         return XFG_OK;
     });
@@ -1260,7 +1273,7 @@ int xfg_prove_trace_batch_submit(xfg_ctx* c, uint32_t count, const uint64_t* tra
         bp->n = n;
         bp->o = o;
         bind_tables(c, bp.get());
-        std::vector<Unit> units = split_units(c, (int)count);
+        std::vector<Unit> units = split_units(c, (int)count, o.beta);
         *ticket = enqueue(c, std::move(bp), std::move(units));
         return XFG_OK;
     });
@@ -1351,7 +1364,7 @@ int xfg_prepare(xfg_ctx* c, uint32_t count, uint64_t trace_length, const xfg_opt
         if (marshal(&in, a, err)) return XFG_PROVER_ERROR;
         // every lane proves one full unit, twice (lane-pinned units)
         ensure_workers(c);
-        const int nl = (int)c->workers.size(), U = std::min<int>((int)count, unit_size());
+        const int nl = (int)c->workers.size(), U = std::min<int>((int)count, unit_size(o.beta));
         for (int pass = 0; pass < 2; pass++) {
             std::unique_ptr<Batch> bp(new Batch());
             bp->jobs.resize((size_t)nl * U);

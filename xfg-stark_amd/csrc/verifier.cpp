@@ -292,7 +292,7 @@ std::string verify_transcript(const uint8_t* bytes, size_t len, const AirConst& 
     if (check_options(n, o)) return "UnacceptableProofOptions";
     // folding factors 2, 4, 16: options whose last layer is smaller than the blowup leave the remainder no
     // coefficient (the prover refuses them too, check_request); every layer below then has >= 1 row
-    if (o.fold != 8 && last_fri_domain(n * o.beta, o) < o.beta) return "UnacceptableProofOptions";
+    if (last_layer_below_blowup(n, o)) return "UnacceptableProofOptions";
     // VerifierChannel::new: the section contents and the element sections are deserialised now
     e = parse_contents(pf);
     if (!e.empty()) return e;

@@ -184,7 +184,9 @@ class FieldExtension:
 
 class ProofOptions:
     """winterfell::ProofOptions::new(num_queries, blowup_factor, grinding_factor, field_extension,
-    fri_folding_factor, fri_remainder_max_degree) -- argument order of winter-air 0.8."""
+    fri_folding_factor, fri_remainder_max_degree) -- argument order of winter-air 0.8.
+    blowup_factor: a power of two in [2, 128]; 32, 64 and 128 need trace_length * blowup_factor <= 2^24 and a
+    last FRI layer of at least blowup_factor points (else XfgStarkError 6). fri_folding_factor: 2, 4, 8 or 16."""
 
     def __init__(self, num_queries, blowup_factor, grinding_factor, field_extension, fri_folding_factor,
                  fri_remainder_max_degree):
