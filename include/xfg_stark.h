@@ -286,7 +286,7 @@ int xfg_debug_field(xfg_ctx* ctx, uint32_t op, uint64_t count, const uint64_t* a
 int xfg_debug_ood_deep(xfg_ctx* ctx, uint32_t count, uint64_t n, const uint64_t* coef, const uint64_t* hcoef,
                        const uint64_t* zpts, const uint64_t* coeffs, uint64_t* ood_out, uint64_t* deep_out);
 /* constraint evaluation kernel of the prover on `count` instances, through the calls prove_lane
- * makes, through the same helper (launch_trace_lde in prover.hip: column interpolation, trace LDE at
+ * makes, through the same helper (launch_trace_lde in lane_unit.hip: column interpolation, trace LDE at
  * `blowup` -- 2..128, above 16 with n * blowup <= 2^24; then the host-built divisor table, the kernel):
  * trace [count][7][n] canonical, airs [count], coeffs [count][15][ext] = 7 transition, 7 step-0
  * boundary and the final-step boundary coefficient, E elements (ext 1 or 2 coordinates each);

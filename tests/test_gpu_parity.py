@@ -1050,6 +1050,59 @@ def test_one_lane_back_to_back_units_match_oracle():
         assert st == 0 and hashlib.sha256(want).hexdigest() == got[i], i
 
 
+_INTERLEAVED_CHILD = r"""
+import hashlib, json, sys
+sys.path[:0] = [sys.argv[1], sys.argv[2]]
+import numpy as np
+import synthetic, xfgstark
+traces, airs = np.load(sys.argv[3]), [tuple(a) for a in json.load(open(sys.argv[4]))]
+pr = xfgstark.XfgBurnMintProver()
+first = pr.submit_batch([synthetic.burn_inputs(1400 + i) for i in range(5)], trace_length=64)
+mid = pr.submit_traces(traces, airs, validate=True)
+last = pr.submit_batch([synthetic.burn_inputs(1410 + i) for i in range(4)], trace_length=64)
+res = {"last": last.result(), "first": first.result(), "mid": mid.result()}
+sha = lambda r: hashlib.sha256(r.to_bytes()).hexdigest()
+out = {k: [sha(r) if hasattr(r, "to_bytes") else [r.status, mid._lens[i], list(r.fault.astuple()), str(r)]
+           for i, r in enumerate(v)] for k, v in res.items()}
+out["one"] = sha(pr.prove_trace(traces[2], *airs[2]))
+print(json.dumps(out))
+"""
+
+
+def test_interleaved_batch_kinds_waited_out_of_order(tmp_path):
+    """two lanes, 2-proof units halved to 1: a generated batch of 5, a validated host-trace batch of 3 whose
+    middle trace breaks the AIR, and a generated batch of 4 are in flight together and waited for as 3rd,
+    1st, 2nd; then one xfg_prove_trace on the same context. Every valid proof equals the oracle's, the
+    invalid trace has XFG_INVALID_TRACE, length 0 and the reference check's fault, its neighbours are intact"""
+    import subprocess
+    import sys
+    import trace_check_ref as T
+    from test_trace_batch_gpu import _flat
+    n, root = 64, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    traces, airs = zip(*[T.valid_trace(n, 1420 + i) for i in range(3)])
+    traces[1][5][n - 2] = 77  # constraint 5 at the last checked step
+    fault = T.first_fault(traces[1], airs[1])
+    assert fault == (2, 5, 0, n - 2, 0, 0)
+    np.save(tmp_path / "traces.npy", np.stack(traces))
+    json.dump(airs, open(tmp_path / "airs.json", "w"))
+    env = dict(os.environ, XFG_LANES="2", XFG_UNIT="2", XFG_SPLIT_MIN="1")
+    r = subprocess.run([sys.executable, "-c", _INTERLEAVED_CHILD, os.path.join(root, "xfg-stark_amd"), root,
+                        str(tmp_path / "traces.npy"), str(tmp_path / "airs.json")],
+                       capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = json.loads(r.stdout)
+
+    def oracle_sha(air, trace=None):
+        st, want = O.prove(air, n, O.options(), **({} if trace is None else {"trace": _flat(trace)}))
+        assert st == 0
+        return hashlib.sha256(want).hexdigest()
+    assert got["first"] == [oracle_sha(oracle_air(synthetic.burn_inputs(1400 + i))) for i in range(5)]
+    assert got["last"] == [oracle_sha(oracle_air(synthetic.burn_inputs(1410 + i))) for i in range(4)]
+    assert got["mid"][0] == oracle_sha(T.oracle_air(airs[0]), traces[0])
+    assert got["mid"][2] == oracle_sha(T.oracle_air(airs[2]), traces[2]) == got["one"]
+    assert got["mid"][1] == [11, 0, list(fault), "main transition constraint 5 did not evaluate to ZERO at step 62"]
+
+
 def test_batch_record_and_consumption_rules(prover):
     """submit_batch_record writes proofs and lengths straight into a caller's fixed-size record (the
     exchange format of bench.Exchange); a batch is consumed once: result() after packed_into() or

@@ -1,5 +1,5 @@
 // HIP error handling, the XFG_TRACE switch and the owning device / pinned-host buffer types of the
-// prover's host code (prover.hip, debug_abi.hip, verify_batch_gpu.hip).
+// prover's host code (tables.hip, lane_unit.hip, prover.hip, debug_abi.hip, verify_batch_gpu.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>

@@ -1,4 +1,4 @@
-// Host-side protocol pieces shared by the prover (prover.hip, proof_assembly.hpp) and the verifier (verifier.cpp):
+// Host-side protocol pieces shared by the prover (lane_unit.hip, prover.hip, proof_assembly.hpp) and the verifier (verifier.cpp):
 // proof options, Context elements, the Fiat-Shamir coin, batch Merkle opening plans.
 // Winterfell 0.8.3 as restated in DESIGN.md "Proof format and transcript".
 #pragma once

@@ -1,5 +1,5 @@
 // Process-wide pool of host threads for the per-proof host work of a proof unit (transcript replay,
-// grinding and opening plans, serialisation: proof_assembly.hpp; copy-out). The lane workers (prover.hip) run up to
+// grinding and opening plans, serialisation: proof_assembly.hpp; copy-out). The lane workers (prover.hip, unit_queue.hpp) run up to
 // XFG_LANES units' host tails at once, each a loop over 8-64 independent proofs that used to run on
 // the lane's own thread while its stream waited; parallel_for spreads such a loop over the pool.
 #pragma once
@@ -77,13 +77,14 @@ class HostPool {
     // call has returned and rethrows the first exception one of them threw
     void parallel_for(int count, const std::function<void(int)>& fn) {
         if (count <= 0) return;
-        if (count == 1 || th_.empty()) {
-            for (int i = 0; i < count; i++) fn(i);
-            return;
-        }
         Task t;
         t.fn = &fn;
         t.count = count;
+        if (count == 1 || th_.empty()) {  // all on the caller, with the same rule for exceptions
+            work(&t);
+            if (t.err) std::rethrow_exception(t.err);
+            return;
+        }
         {
             std::lock_guard<std::mutex> g(m_);
             q_.push_back(&t);

@@ -1,6 +1,6 @@
 // The host half of one proof unit, free of any HIP runtime call (compiles host-only, like
 // verifier.cpp): the shape of a proof, the transcript replay, the query / opening plans, the lay-out
-// of the gather indices and the serialiser (StarkProof::to_bytes). prover.hip runs these between its
+// of the gather indices and the serialiser (StarkProof::to_bytes). lane_unit.hip runs these between its
 // launch sets; tests/sanitize/assemble_proof.cpp runs them on the CPU over synthetic memory.
 #pragma once
 #include <stdexcept>

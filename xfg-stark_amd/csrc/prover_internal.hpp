@@ -1,14 +1,14 @@
-// The prover context as its translation units share it: table registry, lanes, the batch queue
-// (prover.hip), the debug / bench entry points (debug_abi.hip) and the GPU batch verifier's host
-// side (verify_batch_gpu.hip).
+// The prover context as its translation units share it: the table registry (tables.hip), the lanes
+// and one work unit on a lane (lane_unit.hip), the batches and their queue (prover.hip,
+// unit_queue.hpp), the debug / bench entry points (debug_abi.hip) and the GPU batch verifier's
+// host side (verify_batch_gpu.hip).
 #pragma once
+#include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <condition_variable>
-#include <deque>
+#include <cstdlib>
 #include <map>
 #include <memory>
-#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -19,6 +19,7 @@
 #include "host_common.hpp"
 #include "kernels.hpp"
 #include "proof_assembly.hpp"
+#include "unit_queue.hpp"
 #include "verifier.hpp"
 
 namespace xfg {
@@ -106,11 +107,41 @@ struct Lane {
     }
 };
 
-struct Batch;
-struct Unit {
-    Batch* b;
-    int b0, b1;
-    int lane;  // -1: any worker
+// where a unit's traces come from, and what is checked on the way. p: the unit's own slice [B][7][n]
+// (null: generated on the device from the AIR constants)
+struct TraceSrc {
+    enum Kind { GENERATED, HOST_DIRECT, HOST_STAGED, DEVICE };
+    Kind kind = GENERATED;
+    const u64* p = nullptr;
+    bool validate = false;        // XFG_TRACE_VALIDATE: the AIR check behind the upload
+    bool size_staging = false;    // grow the lane's pinned trace staging with its other buffers
+    const int* refused = nullptr;  // [B] non-zero: refused at submission, the slot is proven over zeros
+    u64* keys = nullptr;          // [B] out: the check kernel's words (when checks())
+    // device traces are always tested for canonical cells; host traces were on the host
+    bool checks() const { return validate || kind == DEVICE; }
+};
+
+// a submitted batch: jobs [0, B) proven in units of XFG_UNIT proofs by the lane workers; proof
+// bytes are copied into the caller's buffers on the worker thread as each unit finishes
+struct Batch {
+    std::vector<ProofJob> jobs;
+    std::vector<uint32_t> which;   // jobs[k] -> caller index
+    std::vector<uint8_t*> outs;    // caller buffers (null entry or empty: size query)
+    size_t* out_lens = nullptr;    // caller capacities in, proof lengths out
+    int* statuses = nullptr;       // caller statuses, written by wait
+    std::vector<int> st;           // per-job copy-out status
+    // caller-supplied traces [jobs][7][n] (job k <-> caller index k: such a batch keeps refused proofs
+    // as jobs so that every unit's slice stays at b0 * 7 * n); trace.p is the batch's base
+    TraceSrc trace;
+    std::vector<int> refused;          // per job: status set at submission (cell >= p), else 0
+    std::vector<u64> keys;             // per job: the trace check's word
+    xfg_trace_fault* faults = nullptr;  // caller's, filled by wait (may be null)
+    u64 n = 0;
+    Opts o{};
+    Tables T{};
+    const u64* ce_div = nullptr;
+    int units_left = 0;
+    std::exception_ptr err;
 };
 
 struct HostTrace {
@@ -155,7 +186,6 @@ struct HostTrace {
 struct xfg_ctx {
     int device = 0;
     std::string err;
-    bool timing = false;
     bool lde_probe = false;  // xfg_lde_probe state, inherited by lanes created later
     // set by the first batch of host traces (xfg_prove_trace_batch): from then on xfg_prepare sizes
     // every lane's pinned trace staging too
@@ -163,16 +193,10 @@ struct xfg_ctx {
     xfg::TablesHost tables;
     std::vector<std::unique_ptr<xfg::Lane>> lanes;
     // persistent lane workers: one host thread per lane pulls proof units from a FIFO shared by
-    // every submitted batch, so the host tail of one batch overlaps the kernels of the next
-    std::mutex qm;
-    std::condition_variable qcv, dcv;
-    std::deque<xfg::Unit> q;
+    // every submitted batch, so the host tail of one batch overlaps the kernels of the next.
+    // Timing mode (xfg_set_timing) is the queue's whole-units switch
+    xfg::UnitQueue<xfg::Batch> queue;
     std::vector<std::thread> workers;
-    bool stop = false;
-    uint64_t next_ticket = 1;
-    std::map<uint64_t, std::unique_ptr<xfg::Batch>> pending;
-    int last_lane = 0;
-    int idle = 0;  // lane workers waiting for a unit
     // batched GPU verification workspace (xfg_verify_batch_gpu)
     struct {
         xfg::HBuf<uint8_t> stage;  // pinned: proof blob + task lists, one DMA
@@ -181,20 +205,24 @@ struct xfg_ctx {
         std::vector<xfg::VState> st;        // per-proof transcript states, reused between calls
         std::vector<xfg::VerifyPlan> frag;  // per-proof plan fragments, reused between calls
     } vb;
-    ~xfg_ctx();  // prover.hip (Batch is complete there)
 };
 
 namespace xfg {
 
-// ---- defined in prover.hip
+// ---- defined in tables.hip
 void ensure_tables(xfg_ctx* c, int LM);
 const u64* ensure_ce_table(xfg_ctx* c, int logn);
+// false when a four-step (or pass) table of the NTT sizes one (n, beta) proof uses is missing
+bool fourstep_ready(xfg_ctx* c, int logn, int logbeta);
 // caller guarantees no kernel in flight reads the registry (fresh context or drained)
 void ensure_fourstep(xfg_ctx* c, int logn, int logbeta);
 Tables tables_of(xfg_ctx* c);
+// ---- defined in lane_unit.hip
 Lane* lane0(xfg_ctx* c);
-// true while a submitted batch has not been waited for
-bool busy(xfg_ctx* c);
+void ensure_lanes(xfg_ctx* c, size_t k);
+// one work unit: jobs[0, B) with .air filled, proven on the lane's streams and serialised into .bytes
+void prove_lane(Lane* c, const Tables& T, const u64* ce_div, ProofJob* jobs, int B, const TraceSrc& ts, u64 n,
+                const Opts& o);
 // buffer sizing and launch sets of the proving chain that the debug entry points run too; of the
 // shape they read n, beta and DE only
 void size_trace_lde(Lane* c, size_t B, const ProofShape& sh);        // trace, coef, scratch, lde
@@ -235,18 +263,51 @@ static int guarded(xfg_ctx* c, F f) {
 }
 
 // an entry point that uses lane 0 directly: refused while batches are pending (lane 0's stream,
-// buffers and counters belong to the workers then), else f(lane 0) with the context's device current
+// buffers and counters belong to the workers then), else f(lane 0) with the context's device current.
+// The lane's timing flag follows timing mode here; the workers set it for the units they pick
 template <class F>
 static int on_lane0(xfg_ctx* c, F f) {
-    if (busy(c)) {
+    if (c->queue.busy()) {
         c->err = "batches pending: call xfg_batch_wait first";
         return XFG_INVALID_ARGUMENT;
     }
     return guarded(c, [&]() -> int {
         Lane* L = lane0(c);
+        L->timing = c->queue.whole_units();
         HIPCHK(hipSetDevice(c->device));
         return f(L);
     });
+}
+
+// lane / work-unit tuning knobs (XFG_LANES, XFG_UNIT)
+static int env_int(const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v && *v ? atoi(v) : dflt;
+}
+static int max_lanes() {
+    static const int v = std::max(1, env_int("XFG_LANES", 7));
+    return v;
+}
+// 32 proofs per unit: a 64-proof batch is two units. Same box, 3 x 20 steps at bench.py's depth 6:
+// 12,069 +- 70 burn-proofs/s against 11,890 +- 50 with 22, 11,645 with 64, 11,557 with 16. (At depth
+// 3 the unit queue ran dry and smaller units won: 22 gave 11,400 against 10,790 with 32; with the
+// transcript's host round trips still in place 20 had been best.)
+static int unit_size() {
+    static const int v = std::max(1, env_int("XFG_UNIT", 32));
+    return v;
+}
+// past blowup 16 a unit holds 16 / beta as many proofs, so that a lane's device workspace (the LDE buffers
+// and their scratch, the twisted coefficients of the composed LDE among it) grows no faster than at blowup
+// 16. Scheduling only: the unit size plays no part in the proof bytes
+static int unit_size(u64 beta) { return beta > 16 ? std::max(1, (int)(unit_size() * 16 / beta)) : unit_size(); }
+
+// smallest unit a queued unit is split into when lanes would otherwise idle (0: never split).
+// 16 (a 32-proof unit splits once): with the host tail on the pool, same box, 4 interleaved 20-step
+// bench runs each: 16 -> 12,725, 0 -> 12,675, 12 -> 12,576, 8 -> 12,575 burn-proofs/s (8 cut the
+// first batch of a window into 8 pieces for 7 lanes)
+static int split_min() {
+    static const int v = std::max(0, env_int("XFG_SPLIT_MIN", 16));
+    return v;
 }
 
 }  // namespace xfg
