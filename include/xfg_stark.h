@@ -282,9 +282,32 @@ int xfg_debug_field(xfg_ctx* ctx, uint32_t op, uint64_t count, const uint64_t* a
 /* OOD evaluation + DEEP quotient kernels of the prover on `count` instances: coef [count][7][n],
  * hcoef [count][n] (trace / composition coefficients), zpts [count][2] = (z, z g), coeffs
  * [count][8] = 7 trace DEEP coefficients + the composition one; ood_out [count][15] (T_c(z),
- * T_c(zg) interleaved, H(z)), deep_out [count][n] (DEEP composition coefficients) */
+ * T_c(zg) interleaved, H(z)), deep_out [count][n] (DEEP composition coefficients).
+ * This is xfg_debug_ood_deep_e with ext = 1 and no coin step, and refuses what that entry refuses */
 int xfg_debug_ood_deep(xfg_ctx* ctx, uint32_t count, uint64_t n, const uint64_t* coef, const uint64_t* hcoef,
                        const uint64_t* zpts, const uint64_t* coeffs, uint64_t* ood_out, uint64_t* deep_out);
+/* the same kernels in the field of extension degree ext (1 or 2), E elements as ext consecutive words:
+ * coef [count][7][n] (base field), hcoef [count][ext][n] coordinate planes, zpts [count][2][ext] = (z, z g),
+ * ood_out [count][15][ext], deep_out [count][ext][n] coordinate planes.
+ * coin_seeds == NULL: coeffs [count][8][ext] = a_0..a_6, gamma; the entry forms the DEEP parameters
+ * (1 / z, 1 / (z g), c1, c2) on the host from the frame the device returned, and the frame is reduced by
+ * the 64-thread block of a launch without transcript step. ginv and the outputs from dp_out on are unused.
+ * coin_seeds != NULL: the launches of the prover. The frame is reduced by the 128-thread block that
+ * then runs the DEEP transcript step of instance b on the coin (coin_seeds [count][8] LE u32 words,
+ * coin_counters [count]): reseed with the hashes of the frame, draw a_0..a_6 and gamma, and write the DEEP
+ * parameters with 1 / (z g) = (1 / z) ginv; the quotient kernels consume what it wrote. coeffs is unused.
+ * Out: dp_out [count][28] = a_0..a_6, gamma, z, z g, 1 / z, 1 / (z g), c1, c2 as 14 elements of 2 words
+ * (second word 0 when ext = 1); seeds_out [count][8] and counters_out [count], the coins afterwards;
+ * fail_out [count], cleared before the launches: 1 where a draw ran out of its tries or z = 0 (1 / z is
+ * then returned as 0 and that instance's deep_out is meaningless).
+ * Refused with XFG_INVALID_ARGUMENT before anything is allocated or launched: ext other than 1 or 2, n no
+ * power of two in [8, 2^21], count 0 or above 65535, a word that is not below p, and without coin step
+ * z = 0 or z g = 0. Every device output is set to 0xFF bytes before the launches */
+int xfg_debug_ood_deep_e(xfg_ctx* ctx, uint32_t count, uint64_t n, uint32_t ext, const uint64_t* coef,
+                         const uint64_t* hcoef, const uint64_t* zpts, const uint64_t* coeffs,
+                         const uint32_t* coin_seeds, const uint64_t* coin_counters, uint64_t ginv, uint64_t* ood_out,
+                         uint64_t* deep_out, uint64_t* dp_out, uint32_t* seeds_out, uint64_t* counters_out,
+                         int* fail_out);
 /* constraint evaluation kernel of the prover on `count` instances, through the calls prove_lane
  * makes, through the same helper (launch_trace_lde in lane_unit.hip: column interpolation, trace LDE at
  * `blowup` -- 2..128, above 16 with n * blowup <= 2^24; then the host-built divisor table, the kernel):

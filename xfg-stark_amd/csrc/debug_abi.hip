@@ -346,43 +346,124 @@ int xfg_grind_probe(const xfg_ctx* c, uint32_t* device_min, uint64_t* device_sea
 
 int xfg_debug_ood_deep(xfg_ctx* c, uint32_t count, uint64_t n, const uint64_t* coef, const uint64_t* hcoef,
                        const uint64_t* zpts, const uint64_t* coeffs, uint64_t* ood_out, uint64_t* deep_out) {
-    if (!c || !coef || !hcoef || !zpts || !coeffs || !ood_out || !deep_out || !is_pow2(n) || n < 8 || count == 0)
+    return xfg_debug_ood_deep_e(c, count, n, 1, coef, hcoef, zpts, coeffs, nullptr, nullptr, 0, ood_out, deep_out,
+                                nullptr, nullptr, nullptr, nullptr);
+}
+
+int xfg_debug_ood_deep_e(xfg_ctx* c, uint32_t count, uint64_t n, uint32_t ext, const uint64_t* coef,
+                         const uint64_t* hcoef, const uint64_t* zpts, const uint64_t* coeffs,
+                         const uint32_t* coin_seeds, const uint64_t* coin_counters, uint64_t ginv, uint64_t* ood_out,
+                         uint64_t* deep_out, uint64_t* dp_out, uint32_t* seeds_out, uint64_t* counters_out,
+                         int* fail_out) {
+    if (!c) return XFG_INVALID_ARGUMENT;
+    c->err.clear();
+    const bool coin = coin_seeds != nullptr;
+    // the shape first: nothing below reads an array or sizes a buffer for a shape that is refused
+    // (launch_deep: one carry thread per block of 2048 coefficients, at most 1024; one grid row per instance)
+    if ((ext != 1 && ext != 2) || !is_pow2(n) || n < 8 || n > (1ULL << 21) || count == 0 || count > 0xFFFF) {
+        c->err = "xfg_debug_ood_deep: ext is 1 or 2, n a power of two in [8, 2^21], count in [1, 65535]";
         return XFG_INVALID_ARGUMENT;
+    }
+    if (!coef || !hcoef || !zpts || !ood_out || !deep_out ||
+        (coin ? !coin_counters || !dp_out || !seeds_out || !counters_out || !fail_out : !coeffs)) {
+        c->err = "xfg_debug_ood_deep: null argument";
+        return XFG_INVALID_ARGUMENT;
+    }
+    const size_t B = count, D = ext;
+    if (!all_canonical(coef, B * 7 * n) || !all_canonical(hcoef, B * D * n) || !all_canonical(zpts, B * 2 * D) ||
+        (coin ? ginv >= P : !all_canonical(coeffs, B * 8 * D))) {
+        c->err = "xfg_debug_ood_deep: a word is not a canonical field element";
+        return XFG_INVALID_ARGUMENT;
+    }
+    auto e_at = [D](const u64* v) { return E2{v[0], D == 2 ? v[1] : 0}; };
+    if (!coin)  // the quotients by (x - z) and (x - z g) take 1 / z and 1 / (z g)
+        for (size_t k = 0; k < B * 2; k++)
+            if (e2_eq(e_at(zpts + k * D), E2{0, 0})) {
+                c->err = "xfg_debug_ood_deep: z and z g must not be zero";
+                return XFG_INVALID_ARGUMENT;
+            }
     return on_lane0(c, [&](Lane* L) -> int {
-        const ProofShape sh(n, Opts{0, 2, 0, 1, 8, 31});  // base field; the blowup plays no part
+        const ProofShape sh(n, Opts{0, 2, 0, ext, 8, 31});  // the blowup plays no part
         const int logn = sh.logn;
-        const size_t B = count;
         L->coef.ensure(B * 7 * n);
         size_ood_deep(L, B, sh);
         hipStream_t s = L->stream;
         HIPCHK(hipMemcpyAsync(L->coef.p, coef, B * 7 * n * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(L->hcoef.p, hcoef, B * n * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(L->zpts.p, zpts, B * 2 * 8, hipMemcpyHostToDevice, s));
-        launch_ood(L->coef.p, L->hcoef.p, L->zpts.p, L->partial.p, L->ood.p, logn, (int)B, 1, s);
-        HIPCHK(hipMemcpyAsync(ood_out, L->ood.p, B * 15 * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(L->hcoef.p, hcoef, B * D * n * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(L->zpts.p, zpts, B * 2 * D * 8, hipMemcpyHostToDevice, s));
+        // as the Merkle entries: what a kernel fails to store must show, whatever an earlier call left
+        const size_t nblk = ood_partial_count(logn);
+        HIPCHK(hipMemsetAsync(L->partial.p, 0xFF, B * nblk * 15 * D * 8, s));
+        HIPCHK(hipMemsetAsync(L->carry.p, 0xFF, B * nblk * 2 * D * 8, s));
+        HIPCHK(hipMemsetAsync(L->ood.p, 0xFF, B * 15 * D * 8, s));
+        HIPCHK(hipMemsetAsync(L->dp.p, 0xFF, B * sizeof(DeepParams), s));
+        HIPCHK(hipMemsetAsync(L->deep.p, 0xFF, B * D * n * 8, s));
+        if (coin) {  // as prove_lane: the frame's block draws the coefficients and writes the DeepParams
+            L->dcoin.ensure(B);
+            L->dfail.ensure(B);
+            std::vector<DevCoin> hc(B);
+            for (size_t b = 0; b < B; b++) {
+                memcpy(hc[b].seed.w, coin_seeds + 8 * b, 32);
+                hc[b].counter = coin_counters[b];
+                hc[b].pad = 0;
+            }
+            HIPCHK(hipMemcpyAsync(L->dcoin.p, hc.data(), B * sizeof(DevCoin), hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemsetAsync(L->dfail.p, 0, B * sizeof(int), s));
+            DeepCoinStep dc;
+            dc.coins = L->dcoin.p;
+            dc.fail = L->dfail.p;
+            dc.zpts = L->zpts.p;
+            dc.dp = L->dp.p;
+            dc.ginv = ginv;
+            launch_ood(L->coef.p, L->hcoef.p, L->zpts.p, L->partial.p, L->ood.p, logn, (int)B, (int)ext, s, dc);
+            launch_deep(L->coef.p, L->hcoef.p, L->dp.p, L->partial.p, L->carry.p, L->deep.p, logn, (int)B, (int)ext, s);
+            std::vector<DeepParams> dps(B);
+            HIPCHK(hipMemcpyAsync(ood_out, L->ood.p, B * 15 * D * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(deep_out, L->deep.p, B * D * n * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(dps.data(), L->dp.p, B * sizeof(DeepParams), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(hc.data(), L->dcoin.p, B * sizeof(DevCoin), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(fail_out, L->dfail.p, B * sizeof(int), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            for (size_t b = 0; b < B; b++) {
+                static_assert(sizeof(DeepParams) == 30 * 8, "dp_out: the 28 words before DeepParams::pad");
+                memcpy(dp_out + 28 * b, &dps[b], 28 * 8);
+                memcpy(seeds_out + 8 * b, hc[b].seed.w, 32);
+                counters_out[b] = hc[b].counter;
+            }
+            return XFG_OK;
+        }
+        launch_ood(L->coef.p, L->hcoef.p, L->zpts.p, L->partial.p, L->ood.p, logn, (int)B, (int)ext, s);
+        HIPCHK(hipMemcpyAsync(ood_out, L->ood.p, B * 15 * D * 8, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         std::vector<DeepParams> dps(B);
         for (size_t b = 0; b < B; b++) {  // what the device transcript step derives: c1, c2 from the OOD values
             DeepParams& dp = dps[b];
             memset(&dp, 0, sizeof dp);
-            for (int k = 0; k < 7; k++) dp.a[k][0] = coeffs[b * 8 + k];
-            dp.gamma[0] = coeffs[b * 8 + 7];
-            dp.z[0] = zpts[2 * b];
-            dp.zg[0] = zpts[2 * b + 1];
-            dp.zinv[0] = gl_inv(dp.z[0]);
-            dp.zginv[0] = gl_inv(dp.zg[0]);
-            const u64* o = ood_out + b * 15;
-            u64 c1 = gl_mul(dp.gamma[0], o[14]), c2 = 0;
+            auto put = [D](u64* d, E2 v) {
+                d[0] = v.a;
+                if (D == 2) d[1] = v.b;
+            };
+            const u64* cf = coeffs + b * 8 * D;
+            const u64* o = ood_out + b * 15 * D;
+            const E2 z = e_at(zpts + b * 2 * D), zg = e_at(zpts + b * 2 * D + D), gamma = e_at(cf + 7 * D);
+            E2 c1 = e2_mul(gamma, e_at(o + 14 * D)), c2{0, 0};
             for (int k = 0; k < 7; k++) {
-                c1 = gl_add(c1, gl_mul(dp.a[k][0], o[2 * k]));
-                c2 = gl_add(c2, gl_mul(dp.a[k][0], o[2 * k + 1]));
+                const E2 a = e_at(cf + k * D);
+                put(dp.a[k], a);
+                c1 = e2_add(c1, e2_mul(a, e_at(o + 2 * k * D)));
+                c2 = e2_add(c2, e2_mul(a, e_at(o + (2 * k + 1) * D)));
             }
-            dp.c1[0] = c1;
-            dp.c2[0] = c2;
+            put(dp.gamma, gamma);
+            put(dp.z, z);
+            put(dp.zg, zg);
+            put(dp.zinv, e2_inv(z));
+            put(dp.zginv, e2_inv(zg));
+            put(dp.c1, c1);
+            put(dp.c2, c2);
         }
         HIPCHK(hipMemcpyAsync(L->dp.p, dps.data(), B * sizeof(DeepParams), hipMemcpyHostToDevice, s));
-        launch_deep(L->coef.p, L->hcoef.p, L->dp.p, L->partial.p, L->carry.p, L->deep.p, logn, (int)B, 1, s);
-        HIPCHK(hipMemcpyAsync(deep_out, L->deep.p, B * n * 8, hipMemcpyDeviceToHost, s));
+        launch_deep(L->coef.p, L->hcoef.p, L->dp.p, L->partial.p, L->carry.p, L->deep.p, logn, (int)B, (int)ext, s);
+        HIPCHK(hipMemcpyAsync(deep_out, L->deep.p, B * D * n * 8, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return XFG_OK;
     });

@@ -97,6 +97,10 @@ _lib.xfg_lde_probe.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POI
                                C.POINTER(C.c_uint64)]
 _lib.xfg_debug_lde.argtypes = [C.c_void_p, _u64p, C.c_uint32, C.c_uint64, C.c_uint32, _u64p]
 _lib.xfg_debug_ood_deep.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p]
+if hasattr(_lib, "xfg_debug_ood_deep_e"):  # absent from builds older than the OOD / DEEP hook in E (XFG_LIB A/B)
+    _lib.xfg_debug_ood_deep_e.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, _u64p, _u64p, _u64p, _u64p,
+                                          C.POINTER(C.c_uint32), _u64p, C.c_uint64, _u64p, _u64p, _u64p,
+                                          C.POINTER(C.c_uint32), _u64p, C.POINTER(C.c_int)]
 _lib.xfg_debug_interpolate.argtypes = [C.c_void_p, _u64p, C.c_uint32, C.c_uint64, C.c_int, _u64p]
 if hasattr(_lib, "xfg_debug_const_columns"):  # absent from builds older than the constant-column skip (XFG_LIB A/B)
     _lib.xfg_debug_const_columns.argtypes = [C.c_void_p, _u64p, C.c_uint32, C.c_uint32, C.c_uint64, _u8p]
@@ -889,6 +893,49 @@ class XfgBurnMintProver:
         if st:
             raise self._err(st)
         return ood, deep
+
+    def debug_ood_deep_e(self, coef, hcoef, zpts, coeffs=None, coins=None, ginv=0):
+        """OOD + DEEP kernels in the field of degree ext (xfg_debug_ood_deep_e): coef [B,7,n], hcoef [B,ext,n],
+        zpts [B,2,ext]. Without `coins`: coeffs [B,8,ext] -> (ood [B,15,ext], deep [B,ext,n]). With coins = B x
+        (32-byte seed, counter) and ginv = 1 / g, the prover's launches with the DEEP transcript step ->
+        (ood, deep, dp [B,14,2] = a_0..a_6, gamma, z, zg, 1/z, 1/zg, c1, c2, coins afterwards, fail [B]).
+        Shapes are passed on as they are: the library refuses what it does not support"""
+        import numpy as np
+        c = np.ascontiguousarray(coef, dtype=np.uint64)
+        hc = np.ascontiguousarray(hcoef, dtype=np.uint64)
+        zp = np.ascontiguousarray(zpts, dtype=np.uint64)
+        B, _, n = c.shape
+        ext = hc.shape[1]
+        if c.shape[1] != 7 or hc.shape != (B, ext, n) or zp.shape != (B, 2, ext):
+            raise XfgStarkError(9, "debug_ood_deep_e: coef [B,7,n], hcoef [B,ext,n], zpts [B,2,ext]")
+        ood = np.zeros((B, 15, ext), dtype=np.uint64)
+        deep = np.zeros((B, ext, n), dtype=np.uint64)
+        p = lambda a: a.ctypes.data_as(_u64p)
+        if coins is None:
+            co = np.ascontiguousarray(coeffs, dtype=np.uint64)
+            if co.shape != (B, 8, ext):
+                raise XfgStarkError(9, "debug_ood_deep_e: coeffs [B,8,ext]")
+            st = _lib.xfg_debug_ood_deep_e(self._ctx, B, n, ext, p(c), p(hc), p(zp), p(co), None, None, 0, p(ood),
+                                           p(deep), None, None, None, None)
+            if st:
+                raise self._err(st)
+            return ood, deep
+        if len(coins) != B or any(len(bytes(sd)) != 32 for sd, _ in coins):
+            raise XfgStarkError(9, "debug_ood_deep_e: coins are B x (32-byte seed, counter)")
+        u32p = C.POINTER(C.c_uint32)
+        seeds = np.frombuffer(b"".join(bytes(sd) for sd, _ in coins), dtype="<u4").copy()
+        ctrs = np.array([ctr for _, ctr in coins], dtype=np.uint64)
+        dp = np.zeros((B, 14, 2), dtype=np.uint64)
+        seeds_out = np.zeros(B * 8, dtype="<u4")
+        ctrs_out = np.zeros(B, dtype=np.uint64)
+        fail = (C.c_int * max(B, 1))()
+        st = _lib.xfg_debug_ood_deep_e(self._ctx, B, n, ext, p(c), p(hc), p(zp), None, seeds.ctypes.data_as(u32p),
+                                       p(ctrs), ginv, p(ood), p(deep), p(dp), seeds_out.ctypes.data_as(u32p),
+                                       p(ctrs_out), fail)
+        if st:
+            raise self._err(st)
+        after = [(seeds_out[8 * b:8 * b + 8].tobytes(), int(ctrs_out[b])) for b in range(B)]
+        return ood, deep, dp, after, [fail[b] for b in range(B)]
 
     def debug_constraint_eval(self, trace, airs, coeffs, blowup):
         """constraint evaluation kernel behind interpolation + LDE + the divisor table, as the prover
