@@ -16,6 +16,7 @@ import pytest
 
 import ntt_shapes
 import oracle_lib as O
+import proof_mutants as PM
 import synthetic
 
 pytestmark = pytest.mark.gpu
@@ -867,58 +868,6 @@ def test_gpu_batch_verify_matches_host_verifier(prover, ext, n, blowup):
     assert not any(xfgstark.XfgBurnMintVerifier(proof_options=other).batch_verify(items[:3], gpu=prover))
 
 
-def _node_vectors(raw):
-    """BatchMerkleProof node vectors of a paths section: u8 vector count, per vector u8 count + digests"""
-    m, p, vecs = raw[0], 1, []
-    for _ in range(m):
-        c = raw[p]
-        vecs.append([raw[p + 1 + 32 * i:p + 33 + 32 * i] for i in range(c)])
-        p += 1 + 32 * c
-    assert p == len(raw)
-    return vecs
-
-
-def _with_node_vectors(proof, at, vecs):
-    import struct
-    body = bytes([len(vecs)]) + b"".join(bytes([len(v)]) + b"".join(v) for v in vecs)
-    start, ln = at
-    return proof[:start - 4] + struct.pack("<I", len(body)) + body + proof[start + ln:]
-
-
-def _node_vector_mutants(proof):
-    """(mutant, accepted) pairs: openings whose node vectors still parse but do not fit the opening,
-    for the trace, constraint and first FRI layer paths -- a digest moved to the next vector (both
-    directions), one node dropped, two vectors swapped (all rejected) -- and one node appended to a
-    vector, which winter-crypto 0.8's get_root never reads (accepted, as by the oracle's restatement)"""
-    from test_verifier import _sections
-    sec = _sections(proof)
-    out = []
-    for name in ("trace_paths", "constraint_paths", "fri_paths0"):
-        at = sec[name]
-        vecs = _node_vectors(proof[at[0]:at[0] + at[1]])
-        i = next(k for k in range(len(vecs) - 1) if len(vecs[k]) and len(vecs[k + 1]))
-        v = [list(x) for x in vecs]
-        v[i + 1].insert(0, v[i].pop())  # last digest of vector i moved to the front of vector i + 1
-        out.append((_with_node_vectors(proof, at, v), False))
-        v = [list(x) for x in vecs]
-        v[i].append(v[i + 1].pop(0))  # first digest of vector i + 1 moved to the end of vector i
-        out.append((_with_node_vectors(proof, at, v), False))
-        v = [list(x) for x in vecs]
-        v[i].append(v[i][-1])  # one node appended: never read by the walk
-        out.append((_with_node_vectors(proof, at, v), True))
-        v = [list(x) for x in vecs]
-        v[i].insert(0, v[i][-1])  # one node prepended: shifts every node the walk reads
-        out.append((_with_node_vectors(proof, at, v), False))
-        v = [list(x) for x in vecs]
-        v[i].pop()  # one node dropped
-        out.append((_with_node_vectors(proof, at, v), False))
-        if vecs[i] != vecs[i + 1]:
-            v = [list(x) for x in vecs]
-            v[i], v[i + 1] = v[i + 1], v[i]  # two vectors swapped
-            out.append((_with_node_vectors(proof, at, v), False))
-    return out
-
-
 @pytest.mark.parametrize("ext", [1, 2])
 def test_gpu_batch_verify_node_vector_mutants(prover, ext):
     """vtree_kernel's device walk of the batch openings (node-vector consumption, npairs == nvec,
@@ -940,7 +889,7 @@ def test_gpu_batch_verify_node_vector_mutants(prover, ext):
     for p, a in zip(proofs, airs):
         items.append((p, a))
         want.append(True)
-        for m, ok in _node_vector_mutants(p):
+        for m, ok in PM.node_vector_mutants(p):
             items.append((m, a))
             want.append(ok)
     v = xfgstark.XfgBurnMintVerifier(proof_options=o)
@@ -954,6 +903,28 @@ def test_gpu_batch_verify_node_vector_mutants(prover, ext):
         oa.pub = (O.C.c_uint64 * 12)(*a[0])
         oa.nullifier, oa.commitment = a[1], a[2]
         assert (O.verify(oa, p, oo) == 0) == ok
+
+
+def test_gpu_batch_verifier_reports_structural_errors_first(prover):
+    """the nine doubly broken proofs of proof_mutants.CHECK_ORDER (a FRI section of the wrong size, alone
+    or with a flipped byte in a section opened before it) in one xfg_debug_verify_batch_gpu call, an honest
+    proof before each: the GPU verifier does not send a proof with a broken FRI structure to the device, so
+    it answers with the structural error whatever else is wrong, flag word 0 (recorded from the build before
+    the host verifier became an executor of the plan), while xfg_verify reports the same proofs at the
+    structural error's place in its walk (test_verifier_plan_cpu.py); the honest proofs are accepted"""
+    import xfgstark
+    import fold_cases as FC
+    v = xfgstark.XfgBurnMintVerifier()
+    items, want_gpu, want_host = [], [], []
+    for n, short, cut, flip, host_err in PM.CHECK_ORDER:
+        kw, air, proof = FC.oracle_proof((n, 8, 31, 42, 8, 1))
+        xair = xfgstark.air_consts(**kw)
+        items += [(proof, xair), (PM.doubly_broken(proof, short, cut, flip), xair)]
+        want_gpu += [(True, 0, None), (False, 0, PM.REMAINDER_FOLDING if short == "remainder" else PM.LAYER_SIZE)]
+        want_host += [(True, None), (False, host_err)]
+    assert v.debug_batch_verify(items, prover) == want_gpu
+    assert [v.verify_with_details(*it)[:2] for it in items] == want_host
+    assert v.batch_verify(items, gpu=prover) == [ok for ok, err in want_host]
 
 
 def test_rejects_options_the_reference_rejects(prover):

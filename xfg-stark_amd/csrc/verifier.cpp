@@ -10,7 +10,6 @@
 
 #include <string>
 #include <thread>
-#include <unordered_map>
 #include <vector>
 
 #include "verifier.hpp"
@@ -144,100 +143,65 @@ std::string parse_contents(ParsedProof& pf) {
 }
 
 // ------------------------------------------------------------------ batch Merkle root
-// BatchMerkleProof::get_root: node vector i must hold at least the siblings the opening plan of
-// `idx` takes from it, in that order; every node on the way to the root is then recomputed, level by
-// level. Nodes past the ones the walk takes are ignored: winter-crypto 0.8's get_root consumes the
-// vectors through per-position pointers and never checks that every node was used (the oracle's
-// batch_root restates the same walk, oracle/orc_stark.c), so an opening with a trailing extra node
-// still verifies there, and here. PARITY UNPINNED against upstream: winter-crypto 0.8.x
-// (`BatchMerkleProof::get_root`, src/merkle/proofs.rs of that crate) is not vendored in the reference
-// and no reference fixture covers an over-long node vector, so this acceptance rests on the
-// restatement of its published walk (the per-position `proof_pointers` advance, no final check that
-// each vector was consumed); test_gpu_batch_verify_node_vector_mutants pins GPU = host = oracle only.
-bool merkle_symbolic(const std::vector<u64>& idx, const Paths& paths, u64 L, MerkleSym& out) {
-    thread_local BatchOpening plan;
-    plan_batch_opening(idx, L, plan);
-    // reset in place: callers reuse `out`, so steady-state planning does not allocate
-    out.nslots = out.root = 0;
-    out.leaf_slot.clear();
-    out.given.clear();
-    for (auto& v : out.levels) v.clear();
-    if (plan.size() != paths.ptr.size()) return false;
-    const unsigned depth = ilog2(L);
-    // nodes available per level (0 = leaves) as (heap index, slot), sorted before use; per-thread
-    // scratch so batch planning does not allocate per tree
-    thread_local std::vector<std::vector<std::pair<u64, uint32_t>>> lv;
-    if (lv.size() < depth + 1) lv.resize(depth + 1);
-    for (unsigned l = 0; l <= depth; l++) lv[l].clear();
-    uint32_t s = 0;
-    out.leaf_slot.resize(idx.size());
-    for (size_t i = 0; i < idx.size(); i++) {
-        out.leaf_slot[i] = s;
-        lv[0].push_back({L + idx[i], s++});
-    }
-    for (size_t i = 0; i < plan.size(); i++) {
-        if (paths.cnt[i] < plan.len[i]) return false;
-        for (unsigned k = 0; k < plan.len[i]; k++) {
-            const u64 h = plan.row(i)[k];
-            lv[depth - (63 - __builtin_clzll(h))].push_back({h, s});
-            out.given.push_back({s++, paths.ptr[i] + 32 * k});
+// One planned opening on the host, BatchMerkleProof::get_root: vtree_kernel's walk (verify_kernels.hip)
+// done serially. The opened rows come sorted by leaf index; leaf pair j takes a missing leaf from node
+// vector j; then, level by level, the entry at position j of the current list merges with its right
+// neighbour when that is its sibling, else with the next unread node of vector j. The opening is valid
+// when there is a vector per leaf pair, no vector runs out, and the root equals the commitment. Nodes
+// past the ones the walk takes are ignored: winter-crypto 0.8's get_root consumes the vectors through
+// per-position pointers and never checks that every node was used (the oracle's batch_root restates
+// the same walk, oracle/orc_stark.c), so an opening with a trailing extra node still verifies there,
+// and here. PARITY UNPINNED against upstream: winter-crypto 0.8.x (`BatchMerkleProof::get_root`,
+// src/merkle/proofs.rs of that crate) is not vendored in the reference and no reference fixture covers
+// an over-long node vector, so this acceptance rests on the restatement of its published walk (the
+// per-position `proof_pointers` advance, no final check that each vector was consumed); the node-vector
+// mutants of tests/proof_mutants.py pin GPU = host = oracle only.
+static bool tree_ok(const uint8_t* blob, const VTree& T, const VTreeLeaf* lf, const VVec* vec) {
+    Digest dg[256];  // T.nidx <= 255: the number of unique queries is a u8
+    u64 hx[256];     // heap index of dg[j] (root = 1)
+    uint32_t used[256] = {};
+    bool fits = true;
+    auto take = [&](size_t j) {
+        if (j >= T.nvec || used[j] >= vec[j].cnt) {
+            fits = false;
+            return Digest{};
         }
-    }
-    thread_local std::vector<u64> level, up;
-    level.resize(idx.size());
-    for (size_t i = 0; i < idx.size(); i++) level[i] = L + idx[i];
-    std::sort(level.begin(), level.end());
-    level.erase(std::unique(level.begin(), level.end()), level.end());
-    if (out.levels.size() < depth) out.levels.resize(depth);
-    out.nlev = depth;
-    for (unsigned l = 0; l < depth; l++) {
-        auto& cur = lv[l];
-        std::sort(cur.begin(), cur.end());
-        for (size_t i = 1; i < cur.size(); i++)
-            if (cur[i].first == cur[i - 1].first) return false;
-        auto find = [&](u64 h, uint32_t& sl) {
-            auto it = std::lower_bound(cur.begin(), cur.end(), std::make_pair(h, (uint32_t)0));
-            if (it == cur.end() || it->first != h) return false;
-            sl = it->second;
-            return true;
-        };
-        std::vector<uint32_t>& trip = out.levels[l];
-        trip.reserve(3 * level.size());
-        up.clear();
-        for (u64 x : level) {
-            const u64 p = x >> 1;
-            if (!up.empty() && up.back() == p) continue;
-            uint32_t a, b;
-            if (!find(2 * p, a) || !find(2 * p + 1, b)) return false;
-            trip.insert(trip.end(), {s, a, b});
-            lv[l + 1].push_back({p, s++});
-            up.push_back(p);
+        return ld_digest(blob + vec[j].off + 32 * (u64)used[j]++);
+    };
+    const u64 L = 1ULL << T.depth;
+    size_t nn = 0;
+    for (size_t i = 0; i < T.nidx; nn++) {
+        const u64 idx = lf[i].index;
+        Digest a = hash_row(blob + lf[i++].row_off, T.words), b;
+        if (i < T.nidx && lf[i].index == (idx ^ 1)) {  // sorted: only the right leaf can follow
+            b = hash_row(blob + lf[i++].row_off, T.words);
+        } else {
+            b = take(nn);
+            if (idx & 1) std::swap(a, b);
         }
-        level.swap(up);
+        dg[nn] = b3_merge(a, b);
+        hx[nn] = (L + idx) >> 1;
     }
-    if (level.size() != 1 || level[0] != 1) return false;
-    out.root = lv[depth].back().second;  // the last node added at the top level is the root
-    for (auto& e : lv[depth])
-        if (e.first == 1) out.root = e.second;
-    out.nslots = s;
-    return true;
-}
-static bool batch_root(const std::vector<u64>& idx, const std::vector<Digest>& leaf, const Paths& paths, u64 L,
-                       Digest& root) {
-    MerkleSym sym;
-    if (!merkle_symbolic(idx, paths, L, sym)) return false;
-    std::vector<Digest> val(sym.nslots);
-    for (size_t i = 0; i < idx.size(); i++) val[sym.leaf_slot[i]] = leaf[i];
-    for (auto& g : sym.given) memcpy(val[g.first].w, g.second, 32);
-    for (unsigned l = 0; l < sym.nlev; l++) {
-        const auto& lvl = sym.levels[l];
-        for (size_t t = 0; t < lvl.size(); t += 3) val[lvl[t]] = b3_merge(val[lvl[t + 1]], val[lvl[t + 2]]);
+    if (nn != T.nvec) fits = false;
+    for (unsigned lvl = 1; lvl < T.depth; lvl++) {
+        size_t m = 0;
+        for (size_t i = 0; i < nn; i++, m++) {  // m <= i: in-place compaction is safe
+            const u64 h = hx[i];
+            Digest x = dg[i], y;
+            if (!(h & 1) && i + 1 < nn && hx[i + 1] == h + 1) {
+                y = dg[++i];
+            } else {
+                y = take(i);
+                if (h & 1) std::swap(x, y);
+            }
+            dg[m] = b3_merge(x, y);
+            hx[m] = h >> 1;
+        }
+        nn = m;
     }
-    root = val[sym.root];
-    return true;
+    const Digest root = ld_digest(blob + T.root_off);
+    return fits && nn == 1 && hx[0] == 1 && !memcmp(dg[0].w, root.w, 32);
 }
-static bool same(const Digest& a, const Digest& b) { return !memcmp(a.w, b.w, 32); }
-static Digest leaf_hash(const uint8_t* bytes, size_t len) { return blake3_bytes(bytes, len); }
 
 // ------------------------------------------------------------------ burn AIR at a point
 // evaluate_transition (src/burn_mint_air.rs:335-378, corrected AIR A.2) and the 8 assertions
@@ -255,27 +219,6 @@ static void air_transition(const AirConst& a, const E2 cur[7], const E2 nxt[7], 
     r[6] = e2_sub(cur[6], e2(a.commitment));
 }
 
-// FRI apply_drp on one row (folding factor F = 2^logf <= 16, domain offset 7): interpolate the F
-// values on the coset x * <w_F> (the size-F inverse DFT scaled by 1 / F, per coordinate: base-field
-// weights) and evaluate at alpha
-static E2 fold_row(const E2* v, unsigned logf, u64 x, E2 alpha) {
-    const int F = 1 << logf;
-    const u64 winv = gl_inv(gl_root(logf)), invf = gl_inv((u64)F);
-    E2 c[16];
-    for (int k = 0; k < F; k++) {
-        E2 s{0, 0};
-        u64 wk = gl_pow(winv, (u64)k), p = 1;
-        for (int j = 0; j < F; j++) {
-            s = e2_add(s, e2_mulb(v[j], p));
-            p = gl_mul(p, wk);
-        }
-        c[k] = e2_mulb(s, invf);
-    }
-    const E2 t = e2_mulb(alpha, gl_inv(x));
-    E2 r{0, 0};
-    for (int k = F - 1; k >= 0; k--) r = e2_add(e2_mul(r, t), c[k]);
-    return r;
-}
 // E element i of a span of DE-coordinate elements
 static E2 elem_e(const Span& s, size_t i, int de) { return de == 2 ? E2{s.elem(2 * i), s.elem(2 * i + 1)} : e2(s.elem(i)); }
 
@@ -303,6 +246,9 @@ std::string verify_transcript(const uint8_t* bytes, size_t len, const AirConst& 
     const int de = (int)o.ext;  // E = base field (1) or its quadratic extension (2)
     const u64 beta = o.beta, N = n * beta;
     const unsigned nl = num_fri_layers(N, o);
+    // the plan's records hold VMAXL layers. Never more here: check_options leaves n <= 2^21 and a layer
+    // divides by at least 2 down to (remdeg + 1) * beta >= beta, so nl <= 21 for both verifiers
+    if (nl > (unsigned)VMAXL) return "ProofDeserializationError(\"too many FRI layers\")";
     if (pf.com.size() != 3 + nl || pf.fri_vals.size() != nl || pf.partitions != 0 || pf.num_unique == 0 ||
         pf.ood.n != 14 * 8 * (size_t)de)
         return "ProofDeserializationError(\"inconsistent proof structure\")";
@@ -369,7 +315,7 @@ std::string verify_transcript(const uint8_t* bytes, size_t len, const AirConst& 
     for (auto& x : dc)
         if (!draw(coin, x)) return "RandomCoinError";
     if (!draw(coin, gam)) return "RandomCoinError";
-    std::vector<E2> falpha(nl);
+    E2 falpha[VMAXL];
     for (unsigned l = 0; l <= nl; l++) {
         coin.reseed(pf.com[2 + l]);
         E2 a;
@@ -392,154 +338,58 @@ std::string verify_transcript(const uint8_t* bytes, size_t len, const AirConst& 
     if (pos.size() != nu) return "ProofDeserializationError(\"number of unique queries\")";
 
     st.de = de;
-    st.n = n;
     st.N = N;
     st.beta = beta;
     st.nl = nl;
     st.pos = std::move(pos);
-    st.z = z;
-    st.zg = zg;
-    st.hz = hz;
-    for (int k = 0; k < 14; k++) st.ood[k] = ood[k];
-    for (int k = 0; k < 7; k++) st.dc[k] = dc[k];
-    st.gam = gam;
-    st.falpha = std::move(falpha);
+    VFieldProof& F = st.f;
+    F = VFieldProof{};
+    F.z = z;
+    F.zg = zg;
+    F.hz = hz;
+    F.gam = gam;
+    for (int k = 0; k < 7; k++) F.dc[k] = dc[k];
+    for (int k = 0; k < 14; k++) F.ood[k] = ood[k];
+    for (unsigned l = 0; l < nl; l++) F.falpha[l] = falpha[l];
+    F.de = (uint32_t)de;
+    F.logN = ilog2(N);
     return "";
 }
 
-std::string verify_queries_host(const VState& st) {
-    const ParsedProof& pf = st.pf;
-    const int de = st.de;
-    const u64 N = st.N, beta = st.beta, nu = pf.num_unique, depthN = ilog2(N);
-    const unsigned nl = st.nl;
-    const u64 fold = pf.o.fold;  // 2, 4, 8 or 16 (check_options)
-    const unsigned logf = ilog2(fold);
-    const size_t rowb = (size_t)fold * 8 * de;  // bytes of an opened FRI row
-    const std::vector<u64>& pos = st.pos;
-    const E2 z = st.z, zg = st.zg, hz = st.hz, gam = st.gam;
-    const E2* ood = st.ood;
-    const E2* dc = st.dc;
-    const std::vector<E2>& falpha = st.falpha;
-    // ---- trace / constraint openings
-    std::vector<Digest> leaves(nu);
-    Digest root;
-    for (u64 i = 0; i < nu; i++) leaves[i] = leaf_hash(pf.trace_rows.p + i * 56, 56);
-    if (!batch_root(pos, leaves, pf.trace_paths, N, root) || !same(root, pf.com[0]))
-        return "TraceQueryDoesNotMatchCommitment";
-    for (u64 i = 0; i < nu; i++) leaves[i] = leaf_hash(pf.constraint_rows.p + i * 8 * de, 8 * de);
-    if (!batch_root(pos, leaves, pf.constraint_paths, N, root) || !same(root, pf.com[1]))
-        return "ConstraintQueryDoesNotMatchCommitment";
-
-    // ---- DEEP composition at the query points
-    std::vector<E2> ev(nu);
-    const u64 wN = gl_root((unsigned)depthN);
-    for (u64 i = 0; i < nu; i++) {
-        const E2 x = e2(gl_mul(GEN, gl_pow(wN, pos[i])));
-        E2 s1{0, 0}, s2{0, 0};
-        for (int c = 0; c < 7; c++) {
-            const E2 tx = e2(pf.trace_rows.elem(i * 7 + c));
-            s1 = e2_add(s1, e2_mul(dc[c], e2_sub(tx, ood[2 * c])));
-            s2 = e2_add(s2, e2_mul(dc[c], e2_sub(tx, ood[2 * c + 1])));
-        }
-        const E2 izx = e2_inv(e2_sub(x, z)), izgx = e2_inv(e2_sub(x, zg));
-        E2 d = e2_add(e2_mul(s1, izx), e2_mul(s2, izgx));
-        d = e2_add(d, e2_mul(e2_mul(gam, e2_sub(elem_e(pf.constraint_rows, i, de), hz)), izx));
-        ev[i] = d;
-    }
-
-    // ---- FRI: each layer's openings, folding consistency, remainder
-    std::vector<u64> cur = pos;
-    u64 D = N;
-    for (unsigned l = 0; l < nl; l++) {
-        const u64 rows = D / fold;
-        std::vector<u64> fp = fold_positions(cur, rows);
-        const Span& vals = pf.fri_vals[l];
-        if (vals.n != fp.size() * rowb) return "FriVerificationFailed(InvalidLayerCommitment)";
-        std::vector<Digest> lv(fp.size());
-        for (size_t i = 0; i < fp.size(); i++) lv[i] = leaf_hash(vals.p + i * rowb, rowb);
-        if (!batch_root(fp, lv, pf.fri_paths[l], rows, root) || !same(root, pf.com[2 + l]))
-            return "FriVerificationFailed(LayerCommitmentMismatch)";
-        for (size_t i = 0; i < cur.size(); i++) {
-            const u64 ri = cur[i] & (rows - 1), k = cur[i] / rows;
-            const size_t at = std::find(fp.begin(), fp.end(), ri) - fp.begin();
-            if (!e2_eq(elem_e(vals, at * fold + k, de), ev[i])) return "FriVerificationFailed(InvalidLayerFolding)";
-        }
-        const u64 wD = gl_root(ilog2(D));
-        std::vector<E2> nev(fp.size());
-        for (size_t i = 0; i < fp.size(); i++) {
-            E2 v[16];
-            for (u64 k = 0; k < fold; k++) v[k] = elem_e(vals, i * fold + k, de);
-            nev[i] = fold_row(v, logf, gl_mul(GEN, gl_pow(wD, fp[i])), falpha[l]);
-        }
-        cur.swap(fp);
-        ev.swap(nev);
-        D = rows;
-    }
-    const u64 rl = pf.fri_rem.n / (8 * de);
-    if (rl == 0 || rl != D / beta) return "FriVerificationFailed(InvalidRemainderFolding)";
-    std::vector<u64> raw(rl * de);
-    memcpy(raw.data(), pf.fri_rem.p, rl * 8 * de);
-    if (!same(hash_elements(raw.data(), rl * de), pf.com[2 + nl]))
-        return "FriVerificationFailed(RemainderCommitmentMismatch)";
-    const u64 wD = gl_root(ilog2(D));
-    for (size_t i = 0; i < cur.size(); i++) {
-        const E2 x = e2(gl_mul(GEN, gl_pow(wD, cur[i])));
-        E2 r{0, 0};
-        for (u64 k = rl; k-- > 0;) r = e2_add(e2_mul(r, x), elem_e(pf.fri_rem, k, de));
-        if (!e2_eq(r, ev[i])) return "FriVerificationFailed(InvalidRemainderFolding)";
-    }
-    return "";
-}
-
-static std::string verify_proof(const uint8_t* bytes, size_t len, const AirConst& air, const Opts& acceptable) {
-    VState st;
-    std::string e = verify_transcript(bytes, len, air, acceptable, st);
-    return e.empty() ? verify_queries_host(st) : e;
-}
-
-// ------------------------------------------------------------------ batched GPU verification plan
-bool plan_proof(const VState& st, size_t blob_off, VerifyPlan& plan, std::string& err) {
+// ------------------------------------------------------------------ the query checks: plan, executors, verdict
+void plan_proof(const VState& st, size_t blob_off, VerifyPlan& plan) {
     const ParsedProof& pf = st.pf;
     const int de = st.de;
     const u64 N = st.N, nu = pf.num_unique;
-    const unsigned nl = st.nl;
-    const u64 fold = pf.o.fold;
+    const u64 fold = pf.o.fold;  // 2, 4, 8 or 16 (check_options)
     const unsigned logf = ilog2(fold);
     const size_t rowb = (size_t)fold * 8 * de;  // bytes of an opened FRI row
     plan.trees.clear();
     plan.tleaves.clear();
     plan.vecs.clear();
     plan.fqueries.clear();
-    if (nl > (unsigned)VMAXL) {
-        err = "ProofDeserializationError(\"too many FRI layers\")";
-        return false;
-    }
+    plan.broken = -1;
     auto off = [&](const uint8_t* p) { return (u64)blob_off + (u64)(p - pf.base); };
-    // FRI position lists (first-occurrence order, the order of the opened rows) and the structural
-    // checks the host verifier makes before it opens anything
+    // FRI position lists (first-occurrence order, the order of the opened rows), as far as the value
+    // sections have a row per position; then the remainder's length
     thread_local std::vector<std::vector<u64>> fps;
-    fps.resize(nl);
+    if (fps.size() < st.nl) fps.resize(st.nl);
+    unsigned nl = 0;  // the layers planned
     {
         const std::vector<u64>* cur = &st.pos;
         u64 D = N;
-        for (unsigned l = 0; l < nl; l++) {
+        for (; nl < st.nl; nl++) {
             const u64 rows = D / fold;
-            fps[l] = fold_positions(*cur, rows);
-            if (pf.fri_vals[l].n != fps[l].size() * rowb) {
-                err = "FriVerificationFailed(InvalidLayerCommitment)";
-                return false;
-            }
-            cur = &fps[l];
+            fps[nl] = fold_positions(*cur, rows);
+            if (pf.fri_vals[nl].n != fps[nl].size() * rowb) break;
+            cur = &fps[nl];
             D = rows;
         }
         const u64 rl = pf.fri_rem.n / (8 * de);
-        if (rl == 0 || rl != D / st.beta) {
-            err = "FriVerificationFailed(InvalidRemainderFolding)";
-            return false;
-        }
+        if (nl < st.nl || rl == 0 || rl != D / st.beta) plan.broken = (int)nl;
     }
     // one VTree per batch opening: the opened rows sorted by leaf index, the node vectors as the
-    // proof holds them; the device checks that they fit the opening (BatchMerkleProof::get_root)
+    // proof holds them; the executor checks that they fit the opening (BatchMerkleProof::get_root)
     auto add_tree = [&](const u64* idx, size_t cnt, const Paths& paths, unsigned depth, const uint8_t* row0,
                         size_t stride, uint32_t words, unsigned com, u64 bit) {
         VTree t{};
@@ -558,7 +408,7 @@ bool plan_proof(const VState& st, size_t blob_off, VerifyPlan& plan, std::string
         for (size_t v = 0; v < paths.ptr.size(); v++) plan.vecs.push_back(VVec{off(paths.ptr[v]), paths.cnt[v], 0});
         plan.trees.push_back(t);
     };
-    const unsigned depthN = ilog2(N);
+    const unsigned depthN = st.f.logN;
     add_tree(st.pos.data(), nu, pf.trace_paths, depthN, pf.trace_rows.p, 56, 7, 0, VF_TRACE);
     add_tree(st.pos.data(), nu, pf.constraint_paths, depthN, pf.constraint_rows.p, 8 * de, (uint32_t)de, 1,
              VF_CONSTRAINT);
@@ -567,19 +417,10 @@ bool plan_proof(const VState& st, size_t blob_off, VerifyPlan& plan, std::string
                  (uint32_t)(fold * de), 2 + l, 1ULL << (VF_LAYER_COMMIT + l));
     // field checks
     VFieldProof& F = plan.fproof;
-    F = VFieldProof{};
-    F.z = st.z;
-    F.zg = st.zg;
-    F.hz = st.hz;
-    F.gam = st.gam;
-    for (int k = 0; k < 7; k++) F.dc[k] = st.dc[k];
-    for (int k = 0; k < 14; k++) F.ood[k] = st.ood[k];
-    for (unsigned l = 0; l < nl; l++) F.falpha[l] = st.falpha[l];
-    F.rem_off = off(pf.fri_rem.p);
-    F.rem_len = (uint32_t)(pf.fri_rem.n / (8 * de));
+    F = st.f;
     F.nl = nl;
-    F.de = (uint32_t)de;
-    F.logN = depthN;
+    F.rem_off = off(pf.fri_rem.p);
+    F.rem_len = plan.broken < 0 ? (uint32_t)(pf.fri_rem.n / (8 * de)) : 0;
     for (u64 i = 0; i < nu; i++) {
         VFieldQuery Q{};
         Q.pos = st.pos[i];
@@ -595,24 +436,44 @@ bool plan_proof(const VState& st, size_t blob_off, VerifyPlan& plan, std::string
         }
         plan.fqueries.push_back(Q);
     }
-    return true;
 }
 
-std::string finish_proof(const VState& st, u64 flags) {
+std::string finish_proof(const VState& st, int broken, u64 flags) {
     const ParsedProof& pf = st.pf;
     if (flags & VF_TRACE) return "TraceQueryDoesNotMatchCommitment";
     if (flags & VF_CONSTRAINT) return "ConstraintQueryDoesNotMatchCommitment";
     for (unsigned l = 0; l < st.nl; l++) {
+        if ((int)l == broken) return "FriVerificationFailed(InvalidLayerCommitment)";
         if (flags & (1ULL << (VF_LAYER_COMMIT + l))) return "FriVerificationFailed(LayerCommitmentMismatch)";
         if (flags & (1ULL << l)) return "FriVerificationFailed(InvalidLayerFolding)";
     }
-    const u64 rl = pf.fri_rem.n / (8 * st.de);
-    std::vector<u64> raw(rl * st.de);
-    memcpy(raw.data(), pf.fri_rem.p, rl * 8 * st.de);
-    if (!same(hash_elements(raw.data(), rl * st.de), pf.com[2 + st.nl]))
-        return "FriVerificationFailed(RemainderCommitmentMismatch)";
+    if (broken >= 0) return "FriVerificationFailed(InvalidRemainderFolding)";
+    // the remainder's commitment is the hash of its elements, which are the section's bytes
+    const Digest rem = blake3_bytes(pf.fri_rem.p, pf.fri_rem.n);
+    if (memcmp(rem.w, pf.com[2 + st.nl].w, 32)) return "FriVerificationFailed(RemainderCommitmentMismatch)";
     if (flags & VF_REMAINDER) return "FriVerificationFailed(InvalidRemainderFolding)";
     return "";
+}
+
+// The host executes the plan serially over the proof's own bytes. It runs everything that was planned
+// and lets finish_proof pick the first failure, so a rejected proof costs at most what an accepted one
+// costs; the checks behind a failed one are pure functions of the proof bytes and cannot fault.
+std::string verify_queries_host(const VState& st) {
+    thread_local VerifyPlan plan;  // reset in place: a batch does not allocate per proof
+    plan_proof(st, 0, plan);
+    const uint8_t* blob = st.pf.base;
+    u64 flags = 0;
+    for (const VTree& T : plan.trees)
+        if (!tree_ok(blob, T, plan.tleaves.data() + T.leaf0, plan.vecs.data() + T.vec0)) flags |= T.bit;
+    const unsigned logf = ilog2(st.pf.o.fold);
+    for (const VFieldQuery& Q : plan.fqueries) flags |= query_bits(blob, plan.fproof, Q, logf);
+    return finish_proof(st, plan.broken, flags);
+}
+
+static std::string verify_proof(const uint8_t* bytes, size_t len, const AirConst& air, const Opts& acceptable) {
+    VState st;
+    std::string e = verify_transcript(bytes, len, air, acceptable, st);
+    return e.empty() ? verify_queries_host(st) : e;
 }
 
 AirConst air_of(const xfg_air_consts* a) {

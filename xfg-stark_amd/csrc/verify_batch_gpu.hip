@@ -1,6 +1,7 @@
 // Host side of the batched GPU verifier (xfg_verify_batch_gpu): transcripts and plans per proof on
 // the host pool (verifier.cpp), one staging upload, the two kernels of verify_kernels.hip on lane
-// 0's stream, verdicts in the host verifier's check order.
+// 0's stream, verdicts by finish_proof: the host verifier's check order, except that a broken FRI
+// structure is reported before anything the device would have checked (verifier.hpp plan_proof).
 #include <algorithm>
 #include <cstring>
 #include <functional>
@@ -49,14 +50,13 @@ static int verify_batch_gpu(xfg_ctx* c, uint32_t count, const uint8_t* const* pr
         });
         ht.mark("transcripts");
         // 2. plan: per-proof fragments (openings, queries) built in parallel; blob offsets by prefix
-        //    sum of the accepted proofs' lengths
+        //    sum of the accepted proofs' lengths. A proof whose FRI structure is broken is not sent to
+        //    the device: its flag word stays 0 and finish_proof reports the break
         std::vector<size_t> boff(count + 1, 0);
         for (uint32_t i = 0; i < count; i++) boff[i + 1] = boff[i] + (err[i].empty() ? lens[i] : 0);
         std::vector<VerifyPlan>& frag = V.frag;
         parallel([&](uint32_t i) {
-            if (!err[i].empty()) return;
-            std::string e;
-            if (!plan_proof(st[i], boff[i], frag[i], e)) err[i] = e;
+            if (err[i].empty()) plan_proof(st[i], boff[i], frag[i]);
         });
         ht.mark("plan_fragments");
         // 3. concatenate into one pinned staging region (parallel fill) and one DMA
@@ -66,8 +66,8 @@ static int verify_batch_gpu(xfg_ctx* c, uint32_t count, const uint8_t* const* pr
         std::vector<Off> fo(count + 1);
         std::vector<int> planned(count, -1);
         for (uint32_t i = 0; i < count; i++) {
-            const bool ok = err[i].empty();
             const VerifyPlan& f = frag[i];
+            const bool ok = err[i].empty() && f.broken < 0;
             Off& a = fo[i];
             Off& b = fo[i + 1];
             b.t = a.t + (ok ? f.trees.size() : 0);
@@ -125,9 +125,10 @@ static int verify_batch_gpu(xfg_ctx* c, uint32_t count, const uint8_t* const* pr
             HIPCHK(hipStreamSynchronize(s));
             ht.mark("device");
         }
-        // 4. verdicts in the host verifier's check order
+        // 4. verdicts (finish_proof)
         parallel([&](uint32_t i) {
-            if (planned[i] >= 0) err[i] = finish_proof(st[i], flags[planned[i]]);
+            if (err[i].empty())
+                err[i] = finish_proof(st[i], frag[i].broken, planned[i] >= 0 ? flags[planned[i]] : 0);
             results[i] = proofs[i] ? (err[i].empty() ? XFG_OK : XFG_VERIFY_FAILED) : XFG_INVALID_ARGUMENT;
             if (flags_out) flags_out[i] = planned[i] >= 0 ? flags[planned[i]] : 0;
             if (errs && err_stride) {

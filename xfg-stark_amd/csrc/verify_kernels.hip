@@ -9,42 +9,6 @@
 
 namespace xfg {
 
-// proof bytes are not 8-aligned inside the blob: assemble words from bytes
-__device__ __forceinline__ u64 ld_u64(const uint8_t* p) {
-    u64 v = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) v |= (u64)p[i] << (8 * i);
-    return v;
-}
-__device__ __forceinline__ E2 ld_e(const uint8_t* p, int de) { return de == 2 ? E2{ld_u64(p), ld_u64(p + 8)} : E2{ld_u64(p), 0}; }
-
-template <int K>
-__device__ __forceinline__ Digest hash_words(const uint8_t* p) {
-    u64 v[K];
-#pragma unroll
-    for (int k = 0; k < K; k++) v[k] = ld_u64(p + 8 * k);
-    return b3_hash_elems<K>(v);
-}
-__device__ Digest hash_row(const uint8_t* p, uint32_t words) {
-    switch (words) {  // trace row 7, constraint value 1 / 2, FRI row 2, 4, 8, 16 or 32 (fold x extension degree)
-        case 1: return hash_words<1>(p);
-        case 2: return hash_words<2>(p);
-        case 4: return hash_words<4>(p);
-        case 7: return hash_words<7>(p);
-        case 8: return hash_words<8>(p);
-        case 16: return hash_words<16>(p);
-        default: return hash_words<32>(p);
-    }
-}
-__device__ __forceinline__ Digest ld_digest(const uint8_t* p) {
-    Digest d;
-#pragma unroll
-    for (int w = 0; w < 8; w++)
-        d.w[w] = (uint32_t)p[4 * w] | ((uint32_t)p[4 * w + 1] << 8) | ((uint32_t)p[4 * w + 2] << 16) |
-                 ((uint32_t)p[4 * w + 3] << 24);
-    return d;
-}
-
 // exclusive prefix count of `f` over the workgroup's 256 threads (4 waves), and the total
 __device__ __forceinline__ int block_scan(bool f, int* wsum, int& total) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -70,7 +34,8 @@ __device__ __forceinline__ int block_scan(bool f, int* wsum, int& total) {
 // its right neighbour when that is its sibling, else takes its sibling from vector j; the survivors
 // are compacted (block scan) and climb one level. The opening is valid when every vector holds the
 // nodes the walk takes (nodes past them are ignored, as winter-crypto 0.8's get_root ignores them:
-// verifier.cpp merkle_symbolic) and the root equals the commitment; else flags[proof] |= bit.
+// verifier.cpp tree_ok, the same walk done serially by the host) and the root equals the commitment;
+// else flags[proof] |= bit.
 __global__ __launch_bounds__(256) void vtree_kernel(const uint8_t* blob, const VTree* trees, const VTreeLeaf* tleaves,
                                                     const VVec* vecs, u64* flags) {
     __shared__ Digest leaf[512];
@@ -168,71 +133,15 @@ __global__ __launch_bounds__(256) void vtree_kernel(const uint8_t* blob, const V
     }
 }
 
-// apply_drp of one row of F = 2^LOGF values: iDFT_F on the coset x<w_F> (per coordinate), evaluate at alpha
-template <int LOGF>
-__device__ E2 vfold(const E2* v, u64 x, E2 alpha) {
-    constexpr int F = 1 << LOGF;
-    const u64 winv = gl_inv(gl_root(LOGF)), invf = gl_inv((u64)F);
-    E2 c[F];
-    for (int k = 0; k < F; k++) {
-        E2 s{0, 0};
-        u64 wk = gl_pow(winv, (u64)k), p = 1;
-        for (int j = 0; j < F; j++) {
-            s = e2_add(s, e2_mulb(v[j], p));
-            p = gl_mul(p, wk);
-        }
-        c[k] = e2_mulb(s, invf);
-    }
-    const E2 t = e2_mulb(alpha, gl_inv(x));
-    E2 r{0, 0};
-    for (int k = F - 1; k >= 0; k--) r = e2_add(e2_mul(r, t), c[k]);
-    return r;
-}
-
-// one thread per (proof, query): DEEP value at the query point, then every FRI layer's opened value
-// against the running fold, then the remainder polynomial; failures set bits of flags[proof]
-// (bit l: layer l folding, VF_REMAINDER: remainder). F = 2^LOGF: the folding factor of every proof of the
-// batch (the acceptable options')
+// one thread per (proof, query): query_bits (verify_checks.hpp), its failures set in flags[proof].
+// F = 2^LOGF: the folding factor of every proof of the batch (the acceptable options')
 template <int LOGF>
 __global__ __launch_bounds__(64) void vfield_kernel(const uint8_t* blob, const VFieldProof* fp, const VFieldQuery* fq,
                                                     u64 nq, u64* flags) {
     const u64 qi = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (qi >= nq) return;
     const VFieldQuery& Q = fq[qi];
-    const VFieldProof& P = fp[Q.proof];
-    const int de = (int)P.de;
-    const u64 N = 1ULL << P.logN;
-    E2 x = e2(gl_mul(GEN, gl_pow(gl_root(P.logN), Q.pos)));
-    E2 s1{0, 0}, s2{0, 0};
-    for (int c = 0; c < 7; c++) {
-        const E2 tx = e2(ld_u64(blob + Q.trace_off + 8 * c));
-        s1 = e2_add(s1, e2_mul(P.dc[c], e2_sub(tx, P.ood[2 * c])));
-        s2 = e2_add(s2, e2_mul(P.dc[c], e2_sub(tx, P.ood[2 * c + 1])));
-    }
-    const E2 izx = e2_inv(e2_sub(x, P.z)), izgx = e2_inv(e2_sub(x, P.zg));
-    E2 ev = e2_add(e2_mul(s1, izx), e2_mul(s2, izgx));
-    ev = e2_add(ev, e2_mul(e2_mul(P.gam, e2_sub(ld_e(blob + Q.cons_off, de), P.hz)), izx));
-    u64 D = N, p = Q.pos;
-    u64 bad = 0;
-    constexpr int F = 1 << LOGF;
-    for (uint32_t l = 0; l < P.nl; l++) {
-        const u64 rows = D / F, i = p & (rows - 1), k = p / rows;
-        const uint8_t* row = blob + Q.row_off[l];
-        E2 v[F];
-        for (int j = 0; j < F; j++) v[j] = ld_e(row + 8 * de * j, de);
-        if (!e2_eq(v[k], ev)) bad |= 1ULL << l;
-        int logD = 0;
-        while ((1ULL << logD) < D) logD++;
-        ev = vfold<LOGF>(v, gl_mul(GEN, gl_pow(gl_root(logD), i)), P.falpha[l]);
-        p = i;
-        D = rows;
-    }
-    int logD = 0;
-    while ((1ULL << logD) < D) logD++;
-    const E2 xr = e2(gl_mul(GEN, gl_pow(gl_root(logD), p)));
-    E2 r{0, 0};
-    for (uint32_t k = P.rem_len; k-- > 0;) r = e2_add(e2_mul(r, xr), ld_e(blob + P.rem_off + 8 * de * k, de));
-    if (!e2_eq(r, ev)) bad |= VF_REMAINDER;
+    const u64 bad = query_bits<LOGF>(blob, fp[Q.proof], Q);
     if (bad) atomicOr((unsigned long long*)&flags[Q.proof], (unsigned long long)bad);
 }
 
