@@ -348,6 +348,19 @@ int xfg_debug_coin_draws(xfg_ctx* ctx, const uint32_t seed[8], uint64_t counter,
  * the row's node n + row of the full tree, leaf of coset t at blowup + t; slot 0 is 0xFF bytes) */
 int xfg_debug_merkle_lde(xfg_ctx* ctx, uint32_t count, uint32_t nc, uint64_t n, uint32_t blowup, const uint64_t* lde,
                          const uint64_t* entries, uint64_t nentries, uint8_t* nodes_out, uint8_t* local_out);
+/* xfg_debug_merkle_lde for an LDE with constant columns, as the prover commits to its trace LDE:
+ * flags [count][nc] (non-zero: the column holds vals [count][nc]'s value at every point) go to the leaf
+ * and opening kernels, which take a flagged column from them and do not read its plane. The flagged
+ * planes of the uploaded lde are set to 0xFF bytes on the device before the launches, so a kernel that
+ * still reads one hashes a word that is no field element. nc must be 7; blowup 2..128.
+ * flags = vals = NULL: the dense kernels on the lde as uploaded (xfg_debug_merkle_lde with blowup up to 128) */
+int xfg_debug_merkle_lde_const(xfg_ctx* ctx, uint32_t count, uint32_t nc, uint64_t n, uint32_t blowup,
+                               const uint64_t* lde, const uint8_t* flags, const uint64_t* vals,
+                               const uint64_t* entries, uint64_t nentries, uint8_t* nodes_out, uint8_t* local_out);
+/* on != 0: from now on every unit sets its whole trace LDE buffer to 0xFF bytes before the transforms.
+ * The planes of constant columns are never written, and without this one that a previous unit left
+ * there can hold the right value by accident. Refused while batches are pending */
+int xfg_debug_poison_lde(xfg_ctx* ctx, int on);
 /* Merkle commitment of `count` FRI layers (leaf i = the 8 E values at natural indices i + k rows,
  * k < 8, rows = D / 8), vals, the layout arguments and their checks as for xfg_debug_fri_fold; count <= 65535.
  * nodes_out [count][2 rows][32 bytes]: the whole heap, slots [1, 2 rows); slot 0 is 0xFF bytes */

@@ -505,7 +505,8 @@ int xfg_debug_constraint_eval(xfg_ctx* c, uint32_t count, uint64_t n, uint32_t b
         HIPCHK(hipMemcpy(L->air.p, ha.data(), B * sizeof(AirConst), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(L->coeffs.p, coeffs, B * 15 * ext * 8, hipMemcpyHostToDevice));
         launch_trace_lde(L, T, (int)B, sh, false);
-        launch_constraint_eval(L->lde.p, L->air.p, L->coeffs.p, ce_div, L->ce.p, sh.logn, sh.logbeta, (int)B, sh.DE, s);
+        launch_constraint_eval(L->lde.p, L->air.p, L->coeffs.p, ce_div, L->ce.p, sh.logn, sh.logbeta, (int)B, sh.DE, s,
+                               trace_const(L, sh));
         HIPCHK(hipMemcpyAsync(ce, L->ce.p, B * ext * 2 * n * 8, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return XFG_OK;
@@ -558,15 +559,17 @@ int xfg_debug_fri_fold_f(xfg_ctx* c, uint32_t count, uint32_t ext, uint32_t logn
     });
 }
 
-// The two Merkle entries set the heaps to 0xFF bytes before the launches: a node a kernel fails to
+// The Merkle entries set the heaps to 0xFF bytes before the launches: a node a kernel fails to
 // store must show, whatever an earlier call left in the lane's buffers.
-int xfg_debug_merkle_lde(xfg_ctx* c, uint32_t count, uint32_t nc, uint64_t n, uint32_t blowup, const uint64_t* lde,
-                         const uint64_t* entries, uint64_t nentries, uint8_t* nodes_out, uint8_t* local_out) {
+// xfg_debug_merkle_lde (flags = vals = nullptr, blowup up to 16) and xfg_debug_merkle_lde_const
+static int debug_merkle_lde(xfg_ctx* c, uint32_t count, uint32_t nc, uint64_t n, uint32_t blowup, uint32_t max_blowup,
+                            const uint64_t* lde, const uint8_t* flags, const uint64_t* vals, const uint64_t* entries,
+                            uint64_t nentries, uint8_t* nodes_out, uint8_t* local_out) {
     if (!c) return XFG_INVALID_ARGUMENT;
     c->err.clear();
     if (!lde || !nodes_out || (nentries && (!entries || !local_out)) || count == 0 || count > 0xFFFF ||
-        (nc != 1 && nc != 2 && nc != 7) || !is_pow2(blowup) || blowup < 2 || blowup > 16 || !is_pow2(n) || n < 8 ||
-        n > (1ULL << 24)) {
+        (nc != 1 && nc != 2 && nc != 7) || !is_pow2(blowup) || blowup < 2 || blowup > max_blowup || !is_pow2(n) ||
+        n < 8 || n > (1ULL << 24) || (flags && (!vals || nc != 7))) {
         c->err = "xfg_debug_merkle_lde: null or unsupported argument";
         return XFG_INVALID_ARGUMENT;
     }
@@ -583,17 +586,49 @@ int xfg_debug_merkle_lde(xfg_ctx* c, uint32_t count, uint32_t nc, uint64_t n, ui
         hipStream_t s = L->stream;
         HIPCHK(hipMemcpyAsync(L->lde.p, lde, nlde * 8, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemsetAsync(L->tnodes.p, 0xFF, B * 2 * n * sizeof(Digest), s));
-        launch_merkle_lde(L->lde.p, (int)nc, L->tnodes.p, (int)B, logn, logbeta, s);
+        ColConst cc;
+        if (flags) {  // the flagged planes hold no field element: a kernel that reads one hashes 0xFF bytes
+            const size_t cols = B * nc, N = (size_t)blowup * n;
+            L->const_col.ensure((cols + 3) & ~(size_t)3);
+            L->coef.ensure(cols);
+            HIPCHK(hipMemcpyAsync(L->const_col.p, flags, cols, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(L->coef.p, vals, cols * 8, hipMemcpyHostToDevice, s));
+            for (size_t k = 0; k < cols; k++)
+                if (flags[k]) HIPCHK(hipMemsetAsync(L->lde.p + k * N, 0xFF, N * 8, s));
+            cc.flags = L->const_col.p;
+            cc.vals = L->coef.p;
+            cc.val_stride = 1;
+        }
+        launch_merkle_lde(L->lde.p, (int)nc, L->tnodes.p, (int)B, logn, logbeta, s, CoinStep{}, cc);
         HIPCHK(hipMemcpyAsync(nodes_out, L->tnodes.p, B * 2 * n * sizeof(Digest), hipMemcpyDeviceToHost, s));
         if (nentries) {
             L->scratch.ensure(nentries);
             L->hnodes.ensure(nloc);
             HIPCHK(hipMemcpyAsync(L->scratch.p, entries, nentries * 8, hipMemcpyHostToDevice, s));
             HIPCHK(hipMemsetAsync(L->hnodes.p, 0xFF, nloc * sizeof(Digest), s));
-            launch_open_rows(L->lde.p, (int)nc, L->scratch.p, nentries, L->hnodes.p, logn, logbeta, s);
+            launch_open_rows(L->lde.p, (int)nc, L->scratch.p, nentries, L->hnodes.p, logn, logbeta, s, cc);
             HIPCHK(hipMemcpyAsync(local_out, L->hnodes.p, nloc * sizeof(Digest), hipMemcpyDeviceToHost, s));
         }
         HIPCHK(hipStreamSynchronize(s));
+        return XFG_OK;
+    });
+}
+
+int xfg_debug_merkle_lde(xfg_ctx* c, uint32_t count, uint32_t nc, uint64_t n, uint32_t blowup, const uint64_t* lde,
+                         const uint64_t* entries, uint64_t nentries, uint8_t* nodes_out, uint8_t* local_out) {
+    return debug_merkle_lde(c, count, nc, n, blowup, 16, lde, nullptr, nullptr, entries, nentries, nodes_out, local_out);
+}
+int xfg_debug_merkle_lde_const(xfg_ctx* c, uint32_t count, uint32_t nc, uint64_t n, uint32_t blowup,
+                               const uint64_t* lde, const uint8_t* flags, const uint64_t* vals, const uint64_t* entries,
+                               uint64_t nentries, uint8_t* nodes_out, uint8_t* local_out) {
+    return debug_merkle_lde(c, count, nc, n, blowup, 128, lde, flags, vals, entries, nentries, nodes_out, local_out);
+}
+
+int xfg_debug_poison_lde(xfg_ctx* c, int on) {
+    if (!c) return XFG_INVALID_ARGUMENT;
+    return on_lane0(c, [&](Lane*) -> int {
+        c->poison_lde = on != 0;
+        for (auto& L : c->lanes) L->poison_lde = on != 0;
         return XFG_OK;
     });
 }

@@ -90,6 +90,7 @@ struct CeArgs {
     const u64* div;  // [3][2][n]: (x - g^(n-1))/(x^n - 1), 1/(x - 1), 1/(x - g^(n-1)) by (parity, m)
     u64* ce;
     int logn, logbeta;
+    ColConst cc;  // CC instantiations: the trace's constant columns, whose LDE planes hold nothing
 };
 // One thread per constraint-evaluation point i = 2m + par of the CE domain 7*<w_2n>
 // (ce_to_lde_blowup = beta/2: CE point i is LDE row i*beta/2, i.e. coset t = par*beta/2, row m).
@@ -97,7 +98,9 @@ struct CeArgs {
 // The divisor inverses are data independent and come from a per-(n, beta) table.
 // D = extension degree of the composition coefficients (1: FieldExtension::None, 2: Quadratic);
 // the evaluations are written as D coordinate planes ce[proof][c][nce].
-template <int D>
+// CC: the frame's cells of a flagged column (the next row's column 4 among them) are the column's value,
+// read once per block (the block's proof is blockIdx.y) in place of their loads; the AIR stays generic.
+template <int D, bool CC>
 __global__ __launch_bounds__(256) void constraint_eval_kernel(CeArgs a) {
     using F = FE<D>;
     const u64 n = 1ULL << a.logn, nce = 2 * n;
@@ -109,10 +112,21 @@ __global__ __launch_bounds__(256) void constraint_eval_kernel(CeArgs a) {
     const u64 beta = 1ULL << a.logbeta;
     const u64* lde = a.lde + (u64)proof * 7 * beta * n;
     const u64 t = par * (beta / 2), mn = (m + 1) & (n - 1);
-    u64 cur[7];
+    u64 cur[7], nxt4;
+    if constexpr (CC) {
+        const RowConst rc = row_const_uniform(a.cc, (u64)proof);
 #pragma unroll
-    for (int c = 0; c < 7; c++) cur[c] = lde[(((u64)c << a.logbeta) + t) * n + m];
-    const u64 nxt4 = lde[((4ULL << a.logbeta) + t) * n + mn];
+        for (int c = 0; c < 7; c++) {
+            if ((rc.mask >> c) & 1) cur[c] = rc.v[c];
+            else cur[c] = lde[(((u64)c << a.logbeta) + t) * n + m];
+        }
+        if ((rc.mask >> 4) & 1) nxt4 = rc.v[4];
+        else nxt4 = lde[((4ULL << a.logbeta) + t) * n + mn];
+    } else {
+#pragma unroll
+        for (int c = 0; c < 7; c++) cur[c] = lde[(((u64)c << a.logbeta) + t) * n + m];
+        nxt4 = lde[((4ULL << a.logbeta) + t) * n + mn];
+    }
     // divisor inverses loaded with the frame (not next to the multiplies that use them)
     const u64 di = par * n + m;
     const u64 dv0 = a.div[di], dv1 = a.div[nce + di], dv2 = a.div[2 * nce + di];
@@ -135,14 +149,20 @@ __global__ __launch_bounds__(256) void constraint_eval_kernel(CeArgs a) {
     for (int c = 0; c < D; c++) a.ce[((u64)proof * D + c) * nce + i] = val.c(c);
 }
 void launch_constraint_eval(const u64* lde, const AirConst* air, const u64* coeffs, const u64* div, u64* ce, int logn,
-                            int logbeta, int npoly, int ext, hipStream_t s) {
+                            int logbeta, int npoly, int ext, hipStream_t s, const ColConst& cc) {
     CeArgs a;
     a.lde = lde; a.air = air; a.coeffs = coeffs; a.div = div; a.ce = ce; a.logn = logn; a.logbeta = logbeta;
+    a.cc = cc;
     u64 nce = 2ULL << logn;
     int threads = nce < 256 ? (int)nce : 256;
     dim3 g((unsigned)(nce / threads), npoly);
-    if (ext == 2) hipLaunchKernelGGL(constraint_eval_kernel<2>, g, dim3(threads), 0, s, a);
-    else hipLaunchKernelGGL(constraint_eval_kernel<1>, g, dim3(threads), 0, s, a);
+    if (cc.flags) {
+        if (ext == 2) hipLaunchKernelGGL((constraint_eval_kernel<2, true>), g, dim3(threads), 0, s, a);
+        else hipLaunchKernelGGL((constraint_eval_kernel<1, true>), g, dim3(threads), 0, s, a);
+    } else {
+        if (ext == 2) hipLaunchKernelGGL((constraint_eval_kernel<2, false>), g, dim3(threads), 0, s, a);
+        else hipLaunchKernelGGL((constraint_eval_kernel<1, false>), g, dim3(threads), 0, s, a);
+    }
     XFG_CHECK_LAUNCH();
 }
 
@@ -676,7 +696,9 @@ void launch_fri_fold(const u64* vals, u64 val_stride, u64 comp_stride, bool cose
 
 // ============================================================================ gathers
 // all of a unit's opening gathers in one launch: thread i of the grid serves element i - first[k] of
-// segment k (the segments are laid end to end in index order; at most GatherSet::MAX of them)
+// segment k (the segments are laid end to end in index order; at most GatherSet::MAX of them).
+// An element of segment cc_seg whose plane is a flagged column is the column's value: that plane of
+// the trace LDE is not written
 __global__ void gather_set_kernel(GatherSet g, const u64* idx) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= g.first[g.nseg]) return;
@@ -687,7 +709,11 @@ __global__ void gather_set_kernel(GatherSet g, const u64* idx) {
         const Digest* s = (const Digest*)g.src[k];
         ((Digest*)g.dst[k])[i - g.first[k]] = s[src];
     } else {
-        ((u64*)g.dst[k])[i - g.first[k]] = ((const u64*)g.src[k])[src];
+        u64 v;
+        const u64 plane = src >> g.cc_shift;
+        if (k == g.cc_seg && g.cc.flags[plane]) v = g.cc.vals[plane * g.cc.val_stride];
+        else v = ((const u64*)g.src[k])[src];
+        ((u64*)g.dst[k])[i - g.first[k]] = v;
     }
 }
 void launch_gather_set(const GatherSet& g, const u64* idx, hipStream_t s) {

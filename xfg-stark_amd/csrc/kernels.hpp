@@ -52,7 +52,8 @@ struct Tables {
 // ---- NTT (four-step, natural order in/out) ----
 // forward LDE: coef[poly][n] -> out[poly][beta][n] (coset-major: out[p][t][m] = P(7 w_N^(t + beta m)))
 // skip [npoly] (device, or nullptr): polynomials with a non-zero byte are not transformed and their
-// planes of out are left untouched (launch_const_fill writes them).
+// planes of out are left untouched (the consumers of a trace LDE take such a column from a ColConst;
+// launch_const_fill can write the planes).
 // beta = 2..16 is one transform; 32, 64 and 128 (N <= 2^24) run as beta / 16 blowup-16 transforms of twisted
 // coefficients whose planes land in the same layout (lde_plan, ntt_plan.hpp). scratch: npoly * beta * n words;
 // T.tw must reach N entries and T.fs hold the tables of (logn, min(logbeta, 4)) (ensure_fourstep)
@@ -70,9 +71,65 @@ void launch_interpolate(const u64* evals, u64 in_stride, u64* out, u64 out_strid
 constexpr int CONST_DETECT_SPAN = 1024, CONST_FILL_SPAN = 4096;
 void launch_const_detect(const u64* cols, int ncols, int logn, unsigned char* flags, hipStream_t s);
 // what the NTTs would have produced for the flagged columns, v = src[col * src_stride]:
-// coef[col] = (v, 0, ..., 0) and lde[col][t][m] = v (coset-major planes); coef or lde may be nullptr
+// coef[col] = (v, 0, ..., 0) and lde[col][t][m] = v (coset-major planes); coef or lde may be nullptr.
+// The prover fills the coefficients only (launch_trace_lde); the planes are written for xfg_debug_lde_skip alone
 void launch_const_fill(const unsigned char* flags, const u64* src, u64 src_stride, u64* coef, u64* lde, int ncols,
                        int logn, int logbeta, hipStream_t s);
+
+// The constant columns as the consumers of a trace LDE [B][7][beta][n] take them: the LDE plane of a
+// flagged column is never written (launch_trace_lde) and its every element is the column's value.
+//   flags  [B * 7] the detection's bytes (device, 4-byte aligned, the allocation padded to whole 32-bit
+//          words); nullptr: dense, every plane is read
+//   vals   the value of column c of proof b lies at vals[(b * 7 + c) * val_stride] (coefficient 0 in coef)
+struct ColConst {
+    const unsigned char* flags = nullptr;
+    const u64* vals = nullptr;
+    u64 val_stride = 0;
+};
+// one proof's flagged columns in registers: bit c of mask, and v[c] where it is set
+struct RowConst {
+    unsigned mask;
+    u64 v[7];
+};
+// for a proof that is the same in every lane (a block per proof): the seven flags come out of two or
+// three aligned 32-bit loads and the values of 64-bit ones at wave-uniform addresses (scalar loads),
+// and mask and values are made wave-uniform for the branches that leave the flagged loads out
+__device__ __forceinline__ RowConst row_const_uniform(const ColConst& cc, u64 proof) {
+    const u64 o = proof * 7;
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(cc.flags) + (o >> 2);
+    const unsigned r = (unsigned)(o & 3);
+    u64 bytes = ((u64)w[0] | ((u64)w[1] << 32)) >> (8 * r);  // flags o .. o + 7 - r
+    if (r >= 2) bytes |= (u64)w[2] << (64 - 8 * r);           // o + 8 - r .. (inside the padded allocation)
+    RowConst rc;
+    rc.mask = 0;
+#pragma unroll
+    for (int c = 0; c < 7; c++) rc.mask |= ((bytes >> (8 * c)) & 0xFF ? 1u : 0u) << c;
+    rc.mask = __builtin_amdgcn_readfirstlane(rc.mask);
+#pragma unroll
+    for (int c = 0; c < 7; c++) {
+        rc.v[c] = 0;
+        if ((rc.mask >> c) & 1) {
+            const u64 v = cc.vals[(o + c) * cc.val_stride];
+            const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+            const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+            rc.v[c] = (u64)lo | ((u64)hi << 32);
+        }
+    }
+    return rc;
+}
+// for a proof that differs from lane to lane (the openings): plain loads. The seven words at vals are
+// loaded whatever the flags say (an unflagged column's is its coefficient 0, never used), so that they
+// are in flight beside the flags and not behind them: a lone proof waits on this chain
+__device__ __forceinline__ RowConst row_const_lane(const ColConst& cc, u64 proof) {
+    RowConst rc;
+    rc.mask = 0;
+#pragma unroll
+    for (int c = 0; c < 7; c++) {
+        rc.v[c] = cc.vals[(proof * 7 + c) * cc.val_stride];
+        rc.mask |= (cc.flags[proof * 7 + c] ? 1u : 0u) << c;
+    }
+    return rc;
+}
 
 // ---- device-side Fiat-Shamir (winter-crypto DefaultRandomCoin<Blake3_256>, as host_common.hpp Coin).
 // Each transcript step runs in the kernel that produces its input, one proof per block; the host
@@ -114,13 +171,13 @@ struct DeepCoinStep {
 // LDE commitment of npoly trees over lde [npoly][nc][beta][n] (coset-major): nodes [npoly][2n], of which
 // the levels from the row pairs up are stored (heap [1, n)); the subtree over the beta leaves of row m
 // tops out at heap node n + m and stays in registers. nc in {1, 2, 7}, beta a power of two in 2..128: any
-// other pair throws std::invalid_argument
+// other pair throws std::invalid_argument. cc (nc = 7 only; a trace LDE): the planes of its flagged columns are not read
 void launch_merkle_lde(const u64* lde, int nc, Digest* nodes, int npoly, int logn, int logbeta, hipStream_t s,
-                       const CoinStep& cs = CoinStep{});
+                       const CoinStep& cs = CoinStep{}, const ColConst& cc = ColConst{});
 // recompute the local subtree heap (2 * beta digests, slot 1 = top, leaf t at beta + t) of LDE
 // rows entries[e] = proof << logn | m, for Merkle openings
 void launch_open_rows(const u64* lde, int nc, const u64* entries, u64 count, Digest* out, int logn, int logbeta,
-                      hipStream_t s);
+                      hipStream_t s, const ColConst& cc = ColConst{});
 // FRI layer commitment: leaf i = values at natural indices i + k*rows, k < fold (coset-major source when
 // coset_major, else natural); nodes [npoly][2 rows], every level stored (leaves at nodes[rows + i]).
 // fold in {2, 4, 8, 16}, ext in {1, 2}: anything else throws std::invalid_argument
@@ -146,9 +203,9 @@ __host__ __device__ constexpr u64 trace_key(unsigned kind, u64 step, unsigned in
 void launch_trace_check(u64* trace, const AirConst* air, u64* keys, int logn, int npoly, bool with_air, hipStream_t s);
 // composition evaluations over the CE domain 7*<w_2n> (natural order) from the trace LDE
 // div = constraint divisor table [3][2][n] from ce_divisor_table()
-// ext = extension degree D: coeffs [B][15][D], ce planes [B][D][2n]
+// ext = extension degree D: coeffs [B][15][D], ce planes [B][D][2n]; cc: as for launch_merkle_lde
 void launch_constraint_eval(const u64* lde, const AirConst* air, const u64* coeffs, const u64* div, u64* ce, int logn,
-                            int logbeta, int npoly, int ext, hipStream_t s);
+                            int logbeta, int npoly, int ext, hipStream_t s, const ColConst& cc = ColConst{});
 
 // ---- OOD / DEEP ----
 // partial: [B][ood_partial_count(logn)][15] per-block sums, kept for launch_deep
@@ -175,7 +232,9 @@ void launch_fri_fold(const u64* vals, u64 val_stride, u64 comp_stride, bool cose
 
 // ---- openings ----
 // several gathers in one launch: segment k copies src[k][idx[first[k] + j]] to dst[k][j],
-// j < first[k + 1] - first[k], as u64 or as Digest (digest[k])
+// j < first[k + 1] - first[k], as u64 or as Digest (digest[k]).
+// Segment cc_seg (-1: none) reads a trace LDE whose flagged planes hold nothing: an index whose plane
+// idx >> cc_shift (cc_shift = logn + logbeta, the plane = proof * 7 + column) is flagged yields cc's value
 struct GatherSet {
     static constexpr int MAX = 24;
     int nseg = 0;
@@ -183,6 +242,8 @@ struct GatherSet {
     void* dst[MAX];
     int digest[MAX];
     u64 first[MAX + 1] = {0};
+    int cc_seg = -1, cc_shift = 0;
+    ColConst cc;
 };
 void launch_gather_set(const GatherSet& g, const u64* idx, hipStream_t s);
 

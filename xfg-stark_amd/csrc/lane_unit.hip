@@ -157,9 +157,19 @@ static void upload_unit_inputs(Lane* c, ProofJob* jobs, int B, const ProofShape&
     HIPCHK(hipMemsetAsync(c->dfail.p, 0, B * sizeof(int), s));
 }
 
+ColConst trace_const(const Lane* c, const ProofShape& sh) {
+    ColConst cc;
+    cc.flags = c->const_col.p;
+    cc.vals = c->coef.p;  // coefficient 0 of a constant column is its value (launch_const_fill)
+    cc.val_stride = sh.n;
+    return cc;
+}
+
 void launch_trace_lde(Lane* c, const Tables& T, int B, const ProofShape& sh, bool probe) {
     hipStream_t s = c->stream;
     const unsigned char* skip = c->const_col.p;
+    // xfg_debug_poison_lde: nothing an earlier unit left in the buffer can pass for a plane of this one
+    if (c->poison_lde) HIPCHK(hipMemsetAsync(c->lde.p, 0xFF, (size_t)B * 7 * sh.N * 8, s));
     launch_const_detect(c->trace.p, B * 7, sh.logn, c->const_col.p, s);
     launch_interpolate(c->trace.p, sh.n, c->coef.p, sh.n, c->scratch.p, B * 7, sh.logn, false, sh.n, T, s, skip);
     if (probe) {
@@ -171,9 +181,10 @@ void launch_trace_lde(Lane* c, const Tables& T, int B, const ProofShape& sh, boo
     }
     launch_lde(c->coef.p, sh.n, c->lde.p, c->scratch.p, B * 7, sh.logn, sh.logbeta, T, s, skip);
     if (probe) HIPCHK(hipEventRecord(c->lde_ev[1], s));
-    // the constant columns' coefficients and LDE planes (outside the probe's window: it times the
-    // transforms of the polynomials it counts)
-    launch_const_fill(skip, c->trace.p, sh.n, c->coef.p, c->lde.p, B * 7, sh.logn, sh.logbeta, s);
+    // the constant columns' coefficients (outside the probe's window: it times the transforms of the
+    // polynomials it counts). Their LDE planes are never written: every reader of c->lde takes such a
+    // column's value from trace_const
+    launch_const_fill(skip, c->trace.p, sh.n, c->coef.p, nullptr, B * 7, sh.logn, sh.logbeta, s);
 }
 
 // FRI layers (FriProver::build_layers), folding factor `fold`: commit -> reseed -> draw alpha -> fold,
@@ -302,10 +313,11 @@ static ReplayView enqueue_commit_chain(Lane* c, const Tables& T, const u64* ce_d
     cs.kind = CoinStep::COEFFS;
     cs.out = c->coeffs.p;
     cs.root_out = c->droots.p;
-    launch_merkle_lde(c->lde.p, 7, c->tnodes.p, B, logn, logbeta, s, cs);
+    const ColConst cc = trace_const(c, sh);
+    launch_merkle_lde(c->lde.p, 7, c->tnodes.p, B, logn, logbeta, s, cs, cc);
     stage_mark(c, 2);
     // ---- 3. constraint evaluation + composition polynomial + commitment
-    launch_constraint_eval(c->lde.p, c->air.p, c->coeffs.p, ce_div, c->ce.p, logn, logbeta, B, DE, s);
+    launch_constraint_eval(c->lde.p, c->air.p, c->coeffs.p, ce_div, c->ce.p, logn, logbeta, B, DE, s, cc);
     stage_mark(c, 3);
     launch_interpolate(c->ce.p, 2 * n, c->hcoef.p, n, c->scratch.p, B * DE, logn + 1, true, n, T, s);
     launch_lde(c->hcoef.p, n, c->hlde.p, c->scratch.p, B * DE, logn, logbeta, T, s);
@@ -383,6 +395,11 @@ static Gathered enqueue_gathers(Lane* c, const ProofShape& sh, const OpeningInde
         gs.nseg++;
     };
     const u64* vsrc[2] = {c->lde.p, c->hlde.p};
+    // segment 0, the opened trace values: an index into c->lde, whose constant columns' planes are not written
+    const ColConst cc = trace_const(c, sh);
+    gs.cc_seg = 0;
+    gs.cc_shift = sh.logn + sh.logbeta;
+    gs.cc = cc;
     for (size_t k = 0; k < ix.vseg.size(); k++) {
         const u64* src = k < 2 ? vsrc[k] : (k == 2 ? c->f0.p : c->flayer[k - 2].p);
         add(src, gval + vo, false, ix.vseg[k].second);
@@ -395,7 +412,7 @@ static Gathered enqueue_gathers(Lane* c, const ProofShape& sh, const OpeningInde
     }
     launch_gather_set(gs, gidx + gbase, sq);
     const u64* ent = gidx + nvals + ndig;
-    launch_open_rows(c->lde.p, 7, ent, nent, gdig + ndig, sh.logn, sh.logbeta, sq);
+    launch_open_rows(c->lde.p, 7, ent, nent, gdig + ndig, sh.logn, sh.logbeta, sq, cc);
     launch_open_rows(c->hlde.p, sh.DE, ent, nent, gdig + ndig + nopen, sh.logn, sh.logbeta, sq);
     ht.mark("q_launch");
     stage_mark(c, 9, sq);
@@ -504,6 +521,7 @@ void prove_lane(Lane* c, const Tables& T, const u64* ce_div, ProofJob* jobs, int
 // and events
 static void create_lane_stream(xfg_ctx* c, Lane* L) {
     L->lde_probe = c->lde_probe;
+    L->poison_lde = c->poison_lde;
     HIPCHK(hipDeviceGetAttribute(&L->cus, hipDeviceAttributeMultiprocessorCount, c->device));
     HIPCHK(hipStreamCreateWithFlags(&L->stream, hipStreamNonBlocking));
     for (auto& e : L->ev) HIPCHK(hipEventCreate(&e));

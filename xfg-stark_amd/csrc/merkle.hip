@@ -89,18 +89,38 @@ __device__ __forceinline__ void quad_level(const Digest* src, bool act, int i, i
 }
 
 // ============================================================================ LDE leaves
+// One leaf's elements: row[c] = column c of the LDE at coset t, row m. CC (a trace LDE with constant
+// columns, NC = 7; kernels.hpp ColConst): a column flagged in rc comes from rc and its load is not
+// issued. CC = false is the dense read and takes no RowConst (NoConst)
+struct NoConst {};
+template <bool CC>
+using RowConstOf = std::conditional_t<CC, RowConst, NoConst>;
+template <int NC, int LOGB, bool CC>
+__device__ __forceinline__ void lde_row(const u64* base, u64 n, u64 m, int t, const RowConstOf<CC>& rc, u64 (&row)[NC]) {
+    static_assert(!CC || NC == 7, "constant columns are those of the trace");
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        if constexpr (CC) {
+            if ((rc.mask >> c) & 1) {
+                row[c] = rc.v[c];
+                continue;
+            }
+        }
+        row[c] = base[((u64)c * (1 << LOGB) + t) * n + m];
+    }
+}
+
 // subtree over the leaves t = T0 .. T0 + 2^LOG - 1 of LDE row m; compile-time recursion keeps
 // every intermediate digest in registers.
-template <int NC, int LOGB, int LOG, int T0>
-__device__ __forceinline__ Digest lde_subtree(const u64* base, u64 n, u64 m) {
+template <int NC, int LOGB, int LOG, int T0, bool CC>
+__device__ __forceinline__ Digest lde_subtree(const u64* base, u64 n, u64 m, const RowConstOf<CC>& rc) {
     if constexpr (LOG == 0) {
         u64 row[NC];
-#pragma unroll
-        for (int c = 0; c < NC; c++) row[c] = base[((u64)c * (1 << LOGB) + T0) * n + m];
+        lde_row<NC, LOGB, CC>(base, n, m, T0, rc, row);
         return b3_hash_elems<NC>(row);
     } else {
-        Digest l = lde_subtree<NC, LOGB, LOG - 1, T0>(base, n, m);
-        Digest r = lde_subtree<NC, LOGB, LOG - 1, T0 + (1 << (LOG - 1))>(base, n, m);
+        Digest l = lde_subtree<NC, LOGB, LOG - 1, T0, CC>(base, n, m, rc);
+        Digest r = lde_subtree<NC, LOGB, LOG - 1, T0 + (1 << (LOG - 1)), CC>(base, n, m, rc);
         return b3_merge(l, r);
     }
 }
@@ -109,19 +129,26 @@ __device__ __forceinline__ Digest lde_subtree(const u64* base, u64 n, u64 m) {
 // the 16-leaf subtrees are two-trip loops that stay rolled, one inside the other, so the code is that of one
 // unrolled 16-leaf subtree and a thread holds one pending digest per level (unrolled through all seven
 // levels the three column counts took minutes to compile). Up to 16 leaves this is lde_subtree itself.
-template <int NC, int LOGB, int LOG>
-__device__ __forceinline__ Digest lde_subtree_wide(const u64* base, u64 n, u64 m, int t0) {
+template <int NC, int LOGB, int LOG, bool CC>
+__device__ __forceinline__ Digest lde_subtree_wide(const u64* base, u64 n, u64 m, int t0, const RowConstOf<CC>& rc) {
     if constexpr (LOG <= 4) {
-        return lde_subtree<NC, LOGB, LOG, 0>(base + (u64)t0 * n, n, m);
+        return lde_subtree<NC, LOGB, LOG, 0, CC>(base + (u64)t0 * n, n, m, rc);
     } else {
         Digest l, d;
 #pragma unroll 1
         for (int i = 0; i < 2; i++) {
-            d = lde_subtree_wide<NC, LOGB, LOG - 1>(base, n, m, t0 + (i << (LOG - 1)));
+            d = lde_subtree_wide<NC, LOGB, LOG - 1, CC>(base, n, m, t0 + (i << (LOG - 1)), rc);
             if (i == 0) l = d;
         }
         return b3_merge(l, d);
     }
+}
+
+// the constant columns of a block's proof (a block per proof: flags and values are read once, wave-uniform)
+template <bool CC>
+__device__ __forceinline__ RowConstOf<CC> block_row_const(const ColConst& cc, int proof) {
+    if constexpr (CC) return row_const_uniform(cc, (u64)proof);
+    else return NoConst{};
 }
 
 // one LDE row per thread, min(256, n) rows per block: the row's 2^LOGB-leaf subtree (top at heap level
@@ -130,15 +157,17 @@ __device__ __forceinline__ Digest lde_subtree_wide(const u64* base, u64 n, u64 m
 // kernel this one replaced) a thread holds one row and one pending digest per subtree level -- 49-56
 // instead of 83-105 VGPRs, 8 instead of 4-5 waves per SIMD -- for the same compressions: the trace
 // leaves 3.3 % faster, the composition leaves unchanged (profiles/r05/leaves_row.txt).
-template <int NC, int LOGB>
-__global__ __launch_bounds__(256) void leaves_row_kernel(const u64* lde, Digest* nodes_all, u64 node_stride,
-                                                         int logn) {
+// CC: the constant columns of the block's proof stand in for their planes; cc is unused without it
+template <int NC, int LOGB, bool CC>
+__global__ __launch_bounds__(256) void leaves_row_kernel(const u64* lde, Digest* nodes_all,
+                                                         u64 node_stride, int logn, ColConst cc) {
     __shared__ Digest lds[256];
     const u64 n = 1ULL << logn;
     const int proof = blockIdx.y;
     const u64 m = (u64)blockIdx.x * blockDim.x + threadIdx.x;  // grid covers n exactly
     const u64* base = lde + (u64)proof * NC * (1 << LOGB) * n;
-    Digest d = lde_subtree_wide<NC, LOGB, LOGB>(base, n, m, 0);
+    const RowConstOf<CC> rc = block_row_const<CC>(cc, proof);
+    Digest d = lde_subtree_wide<NC, LOGB, LOGB, CC>(base, n, m, 0, rc);
     block_tree_up(d, nodes_all + (u64)proof * node_stride, n, lds, blockDim.x / 4);
 }
 
@@ -149,16 +178,17 @@ __global__ __launch_bounds__(256) void leaves_row_kernel(const u64* lde, Digest*
 // 2^LOGL times the waves, and a chain of beta / 2^LOGL + log2 beta + 2 compressions instead of 2 beta + 1.
 template <int LOGB>
 constexpr int leaf_lanes_log() { return LOGB < LEAF_LANES_LOG ? LOGB : LEAF_LANES_LOG; }
-template <int NC, int LOGB>
-__global__ __launch_bounds__(256) void leaves_row2_kernel(const u64* lde, Digest* nodes_all, u64 node_stride,
-                                                          int logn) {
+template <int NC, int LOGB, bool CC>
+__global__ __launch_bounds__(256) void leaves_row2_kernel(const u64* lde, Digest* nodes_all,
+                                                          u64 node_stride, int logn, ColConst cc) {
     constexpr int LOGL = leaf_lanes_log<LOGB>(), RB = 256 >> LOGL;  // lanes per row (log2), rows per block
     __shared__ Digest lds[RB];
     const u64 n = 1ULL << logn;
     const int proof = blockIdx.y, t = threadIdx.x, h = t & ((1 << LOGL) - 1), rl = t >> LOGL;
     const u64 m = (u64)blockIdx.x * RB + rl;
     const u64* base = lde + (u64)proof * NC * (1 << LOGB) * n + (u64)h * (1 << (LOGB - LOGL)) * n;
-    Digest d = lde_subtree_wide<NC, LOGB, LOGB - LOGL>(base, n, m, 0);
+    const RowConstOf<CC> rc = block_row_const<CC>(cc, proof);
+    Digest d = lde_subtree_wide<NC, LOGB, LOGB - LOGL, CC>(base, n, m, 0, rc);
 #pragma unroll
     for (int k = 0; k < LOGL; k++) {
         Digest r;
@@ -180,11 +210,13 @@ __global__ __launch_bounds__(256) void leaves_row2_kernel(const u64* lde, Digest
 // t % 2^k == 0 hold level k's nodes and store them to the local heap (slot 1 = top).
 // Blowup 128 has more leaves per row than a wave has lanes: there a lane takes the two leaves 2l, 2l + 1
 // and their parent (2^LPL leaves per lane, 2^LOGL = 64 lanes per entry), and the shuffles start one level up.
+// CC: the constant columns of the entry's proof (which differs from lane group to lane group) stand in
+// for their planes
 template <int LOGB>
 constexpr int open_lanes_log() { return LOGB < 6 ? LOGB : 6; }
-template <int NC, int LOGB>
+template <int NC, int LOGB, bool CC>
 __global__ __launch_bounds__(64) void open_rows_kernel(const u64* lde, const u64* entries, u64 count, Digest* out,
-                                                       int logn) {
+                                                       int logn, ColConst cc) {
     constexpr int LOGL = open_lanes_log<LOGB>(), LPL = LOGB - LOGL;
     static_assert(LPL <= 1, "at most two leaves per lane");
     const u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -195,14 +227,14 @@ __global__ __launch_bounds__(64) void open_rows_kernel(const u64* lde, const u64
     const u64 proof = ent >> logn, m = ent & (n - 1);
     const u64* base = lde + proof * NC * (1 << LOGB) * n;
     Digest* local = out + e * (2 << LOGB);
+    RowConstOf<CC> rc;
+    if constexpr (CC) rc = row_const_lane(cc, proof);
     u64 row[NC];
-#pragma unroll
-    for (int c = 0; c < NC; c++) row[c] = base[((u64)c * (1 << LOGB) + t) * n + m];
+    lde_row<NC, LOGB, CC>(base, n, m, t, rc, row);
     Digest d = b3_hash_elems<NC>(row);
     local[(1 << LOGB) + t] = d;
     if constexpr (LPL == 1) {
-#pragma unroll
-        for (int c = 0; c < NC; c++) row[c] = base[((u64)c * (1 << LOGB) + t + 1) * n + m];
+        lde_row<NC, LOGB, CC>(base, n, m, t + 1, rc, row);
         const Digest d1 = b3_hash_elems<NC>(row);
         local[(1 << LOGB) + t + 1] = d1;
         d = b3_merge(d, d1);
@@ -245,14 +277,30 @@ static void with_nc_logbeta(int nc, int logbeta, F f) {
     if (!found) throw std::invalid_argument("Merkle kernels: no instantiation for this column count and blowup");
 }
 
+// with constant columns: the CC instantiations, which exist for the seven trace columns alone
+static void require_trace_width(int nc, const ColConst& cc) {
+    if (cc.flags && nc != 7) throw std::invalid_argument("Merkle kernels: constant columns are those of a 7-column trace LDE");
+}
+template <class F>
+static void with_const_logbeta(int logbeta, F f) {
+    if (!with_logbeta<7>(logbeta, f))
+        throw std::invalid_argument("Merkle kernels: no instantiation for this column count and blowup");
+}
+
 void launch_open_rows(const u64* lde, int nc, const u64* entries, u64 count, Digest* out, int logn, int logbeta,
-                      hipStream_t s) {
+                      hipStream_t s, const ColConst& cc) {
     if (!count) return;
+    require_trace_width(nc, cc);
     const int logl = logbeta < 6 ? logbeta : 6;  // lanes per entry (open_lanes_log)
     dim3 g((unsigned)(((count << logl) + 63) / 64)), b(64);
-    with_nc_logbeta(nc, logbeta, [&](auto NC, auto LB) {
-        hipLaunchKernelGGL((open_rows_kernel<decltype(NC)::value, decltype(LB)::value>), g, b, 0, s, lde, entries, count, out, logn);
-    });
+    if (cc.flags)
+        with_const_logbeta(logbeta, [&](auto NC, auto LB) {
+            hipLaunchKernelGGL((open_rows_kernel<decltype(NC)::value, decltype(LB)::value, true>), g, b, 0, s, lde, entries, count, out, logn, cc);
+        });
+    else
+        with_nc_logbeta(nc, logbeta, [&](auto NC, auto LB) {
+            hipLaunchKernelGGL((open_rows_kernel<decltype(NC)::value, decltype(LB)::value, false>), g, b, 0, s, lde, entries, count, out, logn, cc);
+        });
     XFG_CHECK_LAUNCH();
 }
 
@@ -345,20 +393,31 @@ static void finish_tree(Digest* nodes, u64 node_stride, u64 count, int npoly, hi
 }
 
 void launch_merkle_lde(const u64* lde, int nc, Digest* nodes, int npoly, int logn, int logbeta, hipStream_t s,
-                       const CoinStep& cs) {
+                       const CoinStep& cs, const ColConst& cc) {
     const u64 n = 1ULL << logn, node_stride = 2 * n;
+    require_trace_width(nc, cc);
     if (n >= ROW2_MIN_N && (u64)npoly * (n / 256) < ROW2_MAX_BLOCKS) {  // under one wave per SIMD
         const int logl = logbeta < LEAF_LANES_LOG ? logbeta : LEAF_LANES_LOG;
         dim3 g((unsigned)(n >> (8 - logl)), npoly), b(256);
-        with_nc_logbeta(nc, logbeta, [&](auto NC, auto LB) {
-            hipLaunchKernelGGL((leaves_row2_kernel<decltype(NC)::value, decltype(LB)::value>), g, b, 0, s, lde, nodes, node_stride, logn);
-        });
+        if (cc.flags)
+            with_const_logbeta(logbeta, [&](auto NC, auto LB) {
+                hipLaunchKernelGGL((leaves_row2_kernel<decltype(NC)::value, decltype(LB)::value, true>), g, b, 0, s, lde, nodes, node_stride, logn, cc);
+            });
+        else
+            with_nc_logbeta(nc, logbeta, [&](auto NC, auto LB) {
+                hipLaunchKernelGGL((leaves_row2_kernel<decltype(NC)::value, decltype(LB)::value, false>), g, b, 0, s, lde, nodes, node_stride, logn, cc);
+            });
     } else {
         const unsigned T = (unsigned)std::min<u64>(256, n);
         dim3 g((unsigned)(n / T), npoly), b(T);
-        with_nc_logbeta(nc, logbeta, [&](auto NC, auto LB) {
-            hipLaunchKernelGGL((leaves_row_kernel<decltype(NC)::value, decltype(LB)::value>), g, b, 0, s, lde, nodes, node_stride, logn);
-        });
+        if (cc.flags)
+            with_const_logbeta(logbeta, [&](auto NC, auto LB) {
+                hipLaunchKernelGGL((leaves_row_kernel<decltype(NC)::value, decltype(LB)::value, true>), g, b, 0, s, lde, nodes, node_stride, logn, cc);
+            });
+        else
+            with_nc_logbeta(nc, logbeta, [&](auto NC, auto LB) {
+                hipLaunchKernelGGL((leaves_row_kernel<decltype(NC)::value, decltype(LB)::value, false>), g, b, 0, s, lde, nodes, node_stride, logn, cc);
+            });
     }
     XFG_CHECK_LAUNCH();
     finish_tree(nodes, node_stride, n / 4, npoly, s, cs);  // both leaf kernels: the row level and two more

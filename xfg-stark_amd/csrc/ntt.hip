@@ -980,7 +980,9 @@ static void ntt_run(NttArgs& a, int npoly, bool inv, hipStream_t s) {
 // ---------------------------------------------------------------- constant columns
 // A column that holds one value v in every row interpolates to the constant v, and its LDE is v at
 // every point: such columns take no NTT. const_detect_kernel finds them in whatever trace arrives,
-// the NTT kernels return at once for them (NttArgs::skip), const_fill_kernel writes their outputs.
+// the NTT kernels return at once for them (NttArgs::skip), const_fill_kernel writes their coefficients.
+// Their LDE planes stay unwritten in the prover: the readers of the trace LDE take the value from a
+// ColConst (kernels.hpp); const_fill_kernel's lde branch serves xfg_debug_lde_skip alone.
 __global__ void const_flags_init_kernel(unsigned char* flags, int count) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < count) flags[i] = 1;

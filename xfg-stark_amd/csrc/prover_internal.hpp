@@ -52,6 +52,7 @@ struct Lane {
     hipEvent_t lde_ev[2] = {};
     double lde_ms = 0;
     u64 lde_sets = 0, lde_polys = 0;
+    bool poison_lde = false;  // xfg_debug_poison_lde: launch_trace_lde sets c->lde to 0xFF bytes first
     DBuf<AirConst> air;
     DBuf<u64> coeffs, trace, coef, scratch, lde, ce, hcoef, hlde, zpts, partial, ood, carry, deep, f0, alpha7,
         rem, dn2, falpha;
@@ -187,6 +188,7 @@ struct xfg_ctx {
     int device = 0;
     std::string err;
     bool lde_probe = false;  // xfg_lde_probe state, inherited by lanes created later
+    bool poison_lde = false;  // xfg_debug_poison_lde state, inherited likewise
     // set by the first batch of host traces (xfg_prove_trace_batch): from then on xfg_prepare sizes
     // every lane's pinned trace staging too
     bool stage_traces = false;
@@ -229,9 +231,11 @@ void size_trace_lde(Lane* c, size_t B, const ProofShape& sh);        // trace, c
 void size_constraint_eval(Lane* c, size_t B, const ProofShape& sh);  // air, coeffs, ce
 void size_ood_deep(Lane* c, size_t B, const ProofShape& sh);  // hcoef, zpts, partial, ood, dp, carry, deep
 // trace -> coefficients -> LDE (DefaultTraceLde::new); probe: the xfg_lde_probe events around the LDE.
-// Constant columns are detected in the trace as it lies in c->trace (whatever put it there) and
-// filled in instead of transformed; the flags stay in c->const_col
+// Constant columns are detected in the trace as it lies in c->trace (whatever put it there) and not
+// transformed: the flags stay in c->const_col, their coefficients are filled in, and their planes of
+// c->lde are left unwritten. Whatever reads c->lde afterwards takes trace_const along
 void launch_trace_lde(Lane* c, const Tables& T, int B, const ProofShape& sh, bool probe);
+ColConst trace_const(const Lane* c, const ProofShape& sh);
 // the proof-of-work search on the device for the B seeds the caller wrote to grind_seeds(c, B): launched on
 // the lane's gather stream (idle between a unit's chain and its gathers) and waited for. Returns the B
 // nonces (pinned host memory, valid until the lane's next search), 0 where [first, max_nonce] held none

@@ -121,6 +121,10 @@ if hasattr(_lib, "xfg_debug_merkle_lde"):  # absent from builds older than the w
                                           C.c_uint64, _u8p, _u8p]
     _lib.xfg_debug_merkle_fri.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _u64p,
                                           _u8p]
+if hasattr(_lib, "xfg_debug_merkle_lde_const"):  # absent from builds that fill the constant columns' planes (XFG_LIB A/B)
+    _lib.xfg_debug_merkle_lde_const.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, _u64p, _u8p,
+                                                _u64p, _u64p, C.c_uint64, _u8p, _u8p]
+    _lib.xfg_debug_poison_lde.argtypes = [C.c_void_p, C.c_int]
 if hasattr(_lib, "xfg_debug_fri_fold_f"):  # absent from builds older than folding factors 2, 4 and 16
     _lib.xfg_debug_fri_fold_f.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                           C.c_uint32, _u64p, _u64p, _u64p]
@@ -1049,6 +1053,38 @@ class XfgBurnMintProver:
         if st:
             raise self._err(st)
         return nodes, local
+
+    def debug_merkle_lde_const(self, lde, flags=None, vals=None, entries=()):
+        """debug_merkle_lde for an LDE [B,7,blowup,n] with constant columns (xfg_debug_merkle_lde_const):
+        flags [B,7] and vals [B,7] go to the kernels, and the flagged planes are set to 0xFF bytes on the
+        device before the launches. flags = vals = None: the dense kernels, blowup up to 128"""
+        import numpy as np
+        v = np.ascontiguousarray(lde, dtype=np.uint64)
+        ent = np.ascontiguousarray(entries, dtype=np.uint64)
+        B, nc, blowup, n = v.shape
+        if (flags is None) != (vals is None):
+            raise XfgStarkError(9, "debug_merkle_lde_const: flags and vals go together")
+        fp = vp = None
+        if flags is not None:
+            f = np.ascontiguousarray(flags, dtype=np.uint8)
+            cv = np.ascontiguousarray(vals, dtype=np.uint64)
+            if f.shape != (B, nc) or cv.shape != (B, nc):
+                raise XfgStarkError(9, "debug_merkle_lde_const: flags [B,nc], vals [B,nc]")
+            fp, vp = f.ctypes.data_as(_u8p), cv.ctypes.data_as(_u64p)
+        nodes = np.zeros((B, 2 * n, 8), dtype="<u4")
+        local = np.zeros((ent.size, 2 * blowup, 8), dtype="<u4")
+        st = _lib.xfg_debug_merkle_lde_const(self._ctx, B, nc, n, blowup, v.ctypes.data_as(_u64p), fp, vp,
+                                             ent.ctypes.data_as(_u64p), ent.size, nodes.ctypes.data_as(_u8p),
+                                             local.ctypes.data_as(_u8p))
+        if st:
+            raise self._err(st)
+        return nodes, local
+
+    def debug_poison_lde(self, on):
+        """while on, every unit sets its trace LDE buffer to 0xFF bytes before the transforms (xfg_debug_poison_lde)"""
+        st = _lib.xfg_debug_poison_lde(self._ctx, 1 if on else 0)
+        if st:
+            raise self._err(st)
 
     def debug_merkle_fri(self, vals, logn, logbeta, coset_major, fold=8):
         """Merkle commitment of FRI layers (xfg_debug_merkle_fri_f): vals and fold as for debug_fri_fold. Returns the heaps [B,2 rows,8] u32 words, rows = 2^(logn + logbeta) / fold
