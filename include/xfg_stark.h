@@ -260,6 +260,13 @@ int xfg_debug_interpolate(xfg_ctx* ctx, const uint64_t* evals, uint32_t npoly, u
  * 1 where the column holds one value in every row, else 0 */
 int xfg_debug_const_columns(xfg_ctx* ctx, const uint64_t* trace, uint32_t count, uint32_t width, uint64_t n,
                             uint8_t* flags_out);
+/* the detection as the prover runs it on a unit of `count` traces, trace [count][7][n] ->
+ * classes_out [count][7]: 0 a live column (it is transformed), 1 a constant one, 2 one that equals the same
+ * column of trace 0 element for element (its planes are those of trace 0's column). A constant column
+ * is 1 whatever it equals, trace 0's columns are never 2, and with count = 1 nothing is.
+ * vals_out [count][7] (or NULL): element 0 of every column, the value of a constant one */
+int xfg_debug_col_classes(xfg_ctx* ctx, const uint64_t* trace, uint32_t count, uint64_t n, uint8_t* classes_out,
+                          uint64_t* vals_out);
 /* xfg_debug_lde / xfg_debug_interpolate with a caller-supplied flag vector skip [npoly]: polynomials
  * with a non-zero flag take no transform and are filled in as constants (coefficient / evaluation 0 of
  * the input is the value), as the prover does for the columns it detects. The caller vouches that a
@@ -308,6 +315,17 @@ int xfg_debug_ood_deep_e(xfg_ctx* ctx, uint32_t count, uint64_t n, uint32_t ext,
                          const uint32_t* coin_seeds, const uint64_t* coin_counters, uint64_t ginv, uint64_t* ood_out,
                          uint64_t* deep_out, uint64_t* dp_out, uint32_t* seeds_out, uint64_t* counters_out,
                          int* fail_out);
+/* xfg_debug_ood_deep_e on trace coefficients behind a column descriptor, as the prover runs the two
+ * kernels: flags [count][7] with 1 for a constant column (its polynomial is the constant vals [count][7])
+ * and 2 for a column whose coefficients are those of instance 0's same column (never for instance 0
+ * itself); such a column's plane of the uploaded coef is set to 0xFF bytes on the device before the
+ * launches, so a kernel that still reads it shows. The caller vouches for what the flags say.
+ * flags = vals = NULL: xfg_debug_ood_deep_e itself, the dense kernels */
+int xfg_debug_ood_deep_const(xfg_ctx* ctx, uint32_t count, uint64_t n, uint32_t ext, const uint64_t* coef,
+                             const uint8_t* flags, const uint64_t* vals, const uint64_t* hcoef, const uint64_t* zpts,
+                             const uint64_t* coeffs, const uint32_t* coin_seeds, const uint64_t* coin_counters,
+                             uint64_t ginv, uint64_t* ood_out, uint64_t* deep_out, uint64_t* dp_out,
+                             uint32_t* seeds_out, uint64_t* counters_out, int* fail_out);
 /* constraint evaluation kernel of the prover on `count` instances, through the calls prove_lane
  * makes, through the same helper (launch_trace_lde in lane_unit.hip: column interpolation, trace LDE at
  * `blowup` -- 2..128, above 16 with n * blowup <= 2^24; then the host-built divisor table, the kernel):
@@ -357,9 +375,10 @@ int xfg_debug_merkle_lde(xfg_ctx* ctx, uint32_t count, uint32_t nc, uint64_t n, 
 int xfg_debug_merkle_lde_const(xfg_ctx* ctx, uint32_t count, uint32_t nc, uint64_t n, uint32_t blowup,
                                const uint64_t* lde, const uint8_t* flags, const uint64_t* vals,
                                const uint64_t* entries, uint64_t nentries, uint8_t* nodes_out, uint8_t* local_out);
-/* on != 0: from now on every unit sets its whole trace LDE buffer to 0xFF bytes before the transforms.
- * The planes of constant columns are never written, and without this one that a previous unit left
- * there can hold the right value by accident. Refused while batches are pending */
+/* on != 0: from now on every unit sets its whole trace LDE buffer and its trace coefficient buffer to 0xFF
+ * bytes before the transforms. The planes of constant columns, and of columns shared with the unit's first
+ * proof, are never written, and without this one that a previous unit left there can hold the right value
+ * by accident. Refused while batches are pending */
 int xfg_debug_poison_lde(xfg_ctx* ctx, int on);
 /* Merkle commitment of `count` FRI layers (leaf i = the 8 E values at natural indices i + k rows,
  * k < 8, rows = D / 8), vals, the layout arguments and their checks as for xfg_debug_fri_fold; count <= 65535.

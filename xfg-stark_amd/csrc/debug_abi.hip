@@ -270,6 +270,27 @@ int xfg_debug_const_columns(xfg_ctx* c, const uint64_t* trace, uint32_t count, u
     });
 }
 
+int xfg_debug_col_classes(xfg_ctx* c, const uint64_t* trace, uint32_t count, uint64_t n, uint8_t* classes_out,
+                          uint64_t* vals_out) {
+    if (!c || !trace || !classes_out || count == 0 || !is_pow2(n) || n < 8 || (uint64_t)count * 7 > 0xFFFF)
+        return XFG_INVALID_ARGUMENT;
+    return on_lane0(c, [&](Lane* L) -> int {
+        const size_t cols = (size_t)count * 7;
+        L->trace.ensure(cols * n);
+        L->const_col.ensure(const_flag_bytes(cols));
+        L->const_val.ensure(cols);
+        HIPCHK(hipMemcpy(L->trace.p, trace, cols * n * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemsetAsync(L->const_val.p, 0xFF, cols * 8, L->stream));
+        // the unit's detection as launch_trace_lde runs it
+        launch_const_detect(L->trace.p, (int)cols, (int)ilog2(n), L->const_col.p, L->stream, 7, L->const_val.p);
+        HIPCHK(hipMemcpyAsync(classes_out, L->const_col.p, cols, hipMemcpyDeviceToHost, L->stream));
+        if (vals_out) HIPCHK(hipMemcpyAsync(vals_out, L->const_val.p, cols * 8, hipMemcpyDeviceToHost, L->stream));
+        HIPCHK(hipStreamSynchronize(L->stream));
+        for (size_t k = 0; k < cols; k++) classes_out[k] = (uint8_t)col_class(classes_out[k]);
+        return XFG_OK;
+    });
+}
+
 int xfg_debug_field(xfg_ctx* c, uint32_t op, uint64_t count, const uint64_t* a, const uint64_t* b, uint64_t* out) {
     if (!c || !a || !b || !out || op > 12 || count == 0 || (op >= 9 && count % 2)) return XFG_INVALID_ARGUMENT;
     return on_lane0(c, [&](Lane* L) -> int {
@@ -355,9 +376,26 @@ int xfg_debug_ood_deep_e(xfg_ctx* c, uint32_t count, uint64_t n, uint32_t ext, c
                          const uint32_t* coin_seeds, const uint64_t* coin_counters, uint64_t ginv, uint64_t* ood_out,
                          uint64_t* deep_out, uint64_t* dp_out, uint32_t* seeds_out, uint64_t* counters_out,
                          int* fail_out) {
+    return xfg_debug_ood_deep_const(c, count, n, ext, coef, nullptr, nullptr, hcoef, zpts, coeffs, coin_seeds,
+                                    coin_counters, ginv, ood_out, deep_out, dp_out, seeds_out, counters_out, fail_out);
+}
+
+int xfg_debug_ood_deep_const(xfg_ctx* c, uint32_t count, uint64_t n, uint32_t ext, const uint64_t* coef,
+                             const uint8_t* flags, const uint64_t* vals, const uint64_t* hcoef, const uint64_t* zpts,
+                             const uint64_t* coeffs, const uint32_t* coin_seeds, const uint64_t* coin_counters,
+                             uint64_t ginv, uint64_t* ood_out, uint64_t* deep_out, uint64_t* dp_out, uint32_t* seeds_out,
+                             uint64_t* counters_out, int* fail_out) {
     if (!c) return XFG_INVALID_ARGUMENT;
     c->err.clear();
     const bool coin = coin_seeds != nullptr;
+    if (flags) {
+        bool ok = vals != nullptr && count <= 0xFFFF;
+        for (size_t k = 0; ok && k < (size_t)count * 7; k++) ok = flags[k] <= 2 && !(k < 7 && flags[k] == 2);
+        if (!ok) {
+            c->err = "xfg_debug_ood_deep_const: flags are 0, 1 or 2 (never 2 for instance 0) and come with vals";
+            return XFG_INVALID_ARGUMENT;
+        }
+    }
     // the shape first: nothing below reads an array or sizes a buffer for a shape that is refused
     // (launch_deep: one carry thread per block of 2048 coefficients, at most 1024; one grid row per instance)
     if ((ext != 1 && ext != 2) || !is_pow2(n) || n < 8 || n > (1ULL << 21) || count == 0 || count > 0xFFFF) {
@@ -391,6 +429,19 @@ int xfg_debug_ood_deep_e(xfg_ctx* c, uint32_t count, uint64_t n, uint32_t ext, c
         HIPCHK(hipMemcpyAsync(L->coef.p, coef, B * 7 * n * 8, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(L->hcoef.p, hcoef, B * D * n * 8, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(L->zpts.p, zpts, B * 2 * D * 8, hipMemcpyHostToDevice, s));
+        ColConst cc;
+        if (flags) {  // the flagged planes hold no field element: a kernel that reads one shows it
+            const size_t cols = B * 7;
+            L->const_col.ensure((cols + 3) & ~(size_t)3);
+            L->const_val.ensure(cols);
+            HIPCHK(hipMemcpyAsync(L->const_col.p, flags, cols, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(L->const_val.p, vals, cols * 8, hipMemcpyHostToDevice, s));
+            for (size_t k = 0; k < cols; k++)
+                if (flags[k]) HIPCHK(hipMemsetAsync(L->coef.p + k * n, 0xFF, n * 8, s));
+            cc.flags = L->const_col.p;
+            cc.vals = L->const_val.p;
+            cc.val_stride = 1;
+        }
         // as the Merkle entries: what a kernel fails to store must show, whatever an earlier call left
         const size_t nblk = ood_partial_count(logn);
         HIPCHK(hipMemsetAsync(L->partial.p, 0xFF, B * nblk * 15 * D * 8, s));
@@ -415,8 +466,8 @@ int xfg_debug_ood_deep_e(xfg_ctx* c, uint32_t count, uint64_t n, uint32_t ext, c
             dc.zpts = L->zpts.p;
             dc.dp = L->dp.p;
             dc.ginv = ginv;
-            launch_ood(L->coef.p, L->hcoef.p, L->zpts.p, L->partial.p, L->ood.p, logn, (int)B, (int)ext, s, dc);
-            launch_deep(L->coef.p, L->hcoef.p, L->dp.p, L->partial.p, L->carry.p, L->deep.p, logn, (int)B, (int)ext, s);
+            launch_ood(L->coef.p, L->hcoef.p, L->zpts.p, L->partial.p, L->ood.p, logn, (int)B, (int)ext, s, dc, cc);
+            launch_deep(L->coef.p, L->hcoef.p, L->dp.p, L->partial.p, L->carry.p, L->deep.p, logn, (int)B, (int)ext, s, cc);
             std::vector<DeepParams> dps(B);
             HIPCHK(hipMemcpyAsync(ood_out, L->ood.p, B * 15 * D * 8, hipMemcpyDeviceToHost, s));
             HIPCHK(hipMemcpyAsync(deep_out, L->deep.p, B * D * n * 8, hipMemcpyDeviceToHost, s));
@@ -432,7 +483,7 @@ int xfg_debug_ood_deep_e(xfg_ctx* c, uint32_t count, uint64_t n, uint32_t ext, c
             }
             return XFG_OK;
         }
-        launch_ood(L->coef.p, L->hcoef.p, L->zpts.p, L->partial.p, L->ood.p, logn, (int)B, (int)ext, s);
+        launch_ood(L->coef.p, L->hcoef.p, L->zpts.p, L->partial.p, L->ood.p, logn, (int)B, (int)ext, s, DeepCoinStep{}, cc);
         HIPCHK(hipMemcpyAsync(ood_out, L->ood.p, B * 15 * D * 8, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         std::vector<DeepParams> dps(B);
@@ -462,7 +513,7 @@ int xfg_debug_ood_deep_e(xfg_ctx* c, uint32_t count, uint64_t n, uint32_t ext, c
             put(dp.c2, c2);
         }
         HIPCHK(hipMemcpyAsync(L->dp.p, dps.data(), B * sizeof(DeepParams), hipMemcpyHostToDevice, s));
-        launch_deep(L->coef.p, L->hcoef.p, L->dp.p, L->partial.p, L->carry.p, L->deep.p, logn, (int)B, (int)ext, s);
+        launch_deep(L->coef.p, L->hcoef.p, L->dp.p, L->partial.p, L->carry.p, L->deep.p, logn, (int)B, (int)ext, s, cc);
         HIPCHK(hipMemcpyAsync(deep_out, L->deep.p, B * D * n * 8, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return XFG_OK;

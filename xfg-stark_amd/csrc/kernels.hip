@@ -98,8 +98,9 @@ struct CeArgs {
 // The divisor inverses are data independent and come from a per-(n, beta) table.
 // D = extension degree of the composition coefficients (1: FieldExtension::None, 2: Quadratic);
 // the evaluations are written as D coordinate planes ce[proof][c][nce].
-// CC: the frame's cells of a flagged column (the next row's column 4 among them) are the column's value,
-// read once per block (the block's proof is blockIdx.y) in place of their loads; the AIR stays generic.
+// CC: the frame's cells of a constant column (the next row's column 4 among them) are the column's value,
+// read once per block (the block's proof is blockIdx.y) in place of their loads, and those of a shared
+// column come from proof 0's planes (a.lde itself); the AIR stays generic.
 template <int D, bool CC>
 __global__ __launch_bounds__(256) void constraint_eval_kernel(CeArgs a) {
     using F = FE<D>;
@@ -118,10 +119,10 @@ __global__ __launch_bounds__(256) void constraint_eval_kernel(CeArgs a) {
 #pragma unroll
         for (int c = 0; c < 7; c++) {
             if ((rc.mask >> c) & 1) cur[c] = rc.v[c];
-            else cur[c] = lde[(((u64)c << a.logbeta) + t) * n + m];
+            else cur[c] = rc.plane(c, lde, a.lde)[(((u64)c << a.logbeta) + t) * n + m];
         }
         if ((rc.mask >> 4) & 1) nxt4 = rc.v[4];
-        else nxt4 = lde[((4ULL << a.logbeta) + t) * n + mn];
+        else nxt4 = rc.plane(4, lde, a.lde)[((4ULL << a.logbeta) + t) * n + mn];
     } else {
 #pragma unroll
         for (int c = 0; c < 7; c++) cur[c] = lde[(((u64)c << a.logbeta) + t) * n + m];
@@ -266,9 +267,13 @@ __device__ __forceinline__ FE<D> fe_plane(const u64* planes, u64 plane_stride, u
 
 // zpts [proof][2][D] = (z, z g); coef [proof][7][n] (base); hcoef [proof][D][n];
 // partial [proof][block][15][D]
-template <int D>
+// CC (the trace's coefficients behind a ColConst: the planes of its flagged columns hold nothing). A
+// constant column's polynomial is the constant v, so both of its frame entries are v: block 0's partials
+// are (v, 0) and every other block's 0, which is what the dense sums of (v, 0, ..., 0) come to, and the
+// column takes no load and no multiply. A shared column is read from proof 0's coefficients (coef itself)
+template <int D, bool CC>
 __global__ __launch_bounds__(256) void ood_kernel(const u64* coef, const u64* hcoef, const u64* zpts, u64* partial,
-                                                  int logn) {
+                                                  int logn, ColConst colc) {
     using F = FE<D>;
     __shared__ u64 zb[4][D];
     __shared__ u64 red[4][15][D];
@@ -289,12 +294,19 @@ __global__ __launch_bounds__(256) void ood_kernel(const u64* coef, const u64* hc
     // the 8 (7 columns + H) values of index j + T are loaded before the products of index j run:
     // a load next to its multiply would be waited for one at a time (the field primitives are asm
     // statements the scheduler does not move loads across)
-    u64 cur[7], nxt[7];
+    // CC: the proof's flags are wave-uniform (a block per proof), so the branches around a constant
+    // column's loads and products are scalar; live(c) is a compile-time true without CC
+    RowConst rc = {};
+    if constexpr (CC) rc = row_const_uniform(colc, (u64)proof);
+    auto live = [&](int c) { return !CC || !((rc.mask >> c) & 1); };
+    auto col = [&](int c) { return (CC ? rc.plane(c, co, coef) : co) + (u64)c * n; };
+    u64 cur[7] = {}, nxt[7] = {};
     F hc, hn;
     {
         const u64 j = base + t;
 #pragma unroll
-        for (int c = 0; c < 7; c++) cur[c] = co[(u64)c * n + j];
+        for (int c = 0; c < 7; c++)
+            if (live(c)) cur[c] = col(c)[j];
         hc = fe_plane<D>(h, n, j);
     }
 #pragma unroll
@@ -302,11 +314,13 @@ __global__ __launch_bounds__(256) void ood_kernel(const u64* coef, const u64* hc
         if (r + 1 < OOD_R) {
             const u64 j = base + (u64)(r + 1) * T + t;
 #pragma unroll
-            for (int c = 0; c < 7; c++) nxt[c] = co[(u64)c * n + j];
+            for (int c = 0; c < 7; c++)
+                if (live(c)) nxt[c] = col(c)[j];
             hn = fe_plane<D>(h, n, j);
         }
 #pragma unroll
         for (int c = 0; c < 7; c++) {
+            if (!live(c)) continue;
             acc[2 * c] = fe_add(acc[2 * c], fe_mulb(pz, cur[c]));
             acc[2 * c + 1] = fe_add(acc[2 * c + 1], fe_mulb(pzg, cur[c]));
         }
@@ -337,6 +351,11 @@ __global__ __launch_bounds__(256) void ood_kernel(const u64* coef, const u64* hc
         const int q = qc / D, cc = qc % D;
         u64 v = red[0][q][cc];
         for (int w = 1; w < (T + 63) / 64; w++) v = gl_add(v, red[w][q][cc]);
+        if constexpr (CC) {  // both frame entries of a constant column: v in block 0's partial, 0 elsewhere
+#pragma unroll
+            for (int c = 0; c < 7; c++)
+                if ((q >> 1) == c && q < 14 && ((rc.mask >> c) & 1)) v = (blockIdx.x == 0 && cc == 0) ? rc.v[c] : 0;
+        }
         partial[((u64)proof * gridDim.x + blockIdx.x) * 15 * D + qc] = v;
     }
 }
@@ -423,13 +442,17 @@ __global__ __launch_bounds__(128) void ood_final_kernel(const u64* partial, int 
     deep_coin_block(dc, proof, o, d);
 }
 void launch_ood(const u64* coef, const u64* hcoef, const u64* zpts, u64* partial, u64* ood, int logn, int npoly,
-                int ext, hipStream_t s, const DeepCoinStep& dc) {
+                int ext, hipStream_t s, const DeepCoinStep& dc, const ColConst& cc) {
     const u64 n = 1ULL << logn;
     const int T = ood_threads(n), nblk = (int)(n / ((u64)T * OOD_R));
-    if (ext == 2)
-        hipLaunchKernelGGL(ood_kernel<2>, dim3(nblk, npoly), dim3(T), 0, s, coef, hcoef, zpts, partial, logn);
-    else
-        hipLaunchKernelGGL(ood_kernel<1>, dim3(nblk, npoly), dim3(T), 0, s, coef, hcoef, zpts, partial, logn);
+    const dim3 g(nblk, npoly), b(T);
+    if (cc.flags) {
+        if (ext == 2) hipLaunchKernelGGL((ood_kernel<2, true>), g, b, 0, s, coef, hcoef, zpts, partial, logn, cc);
+        else hipLaunchKernelGGL((ood_kernel<1, true>), g, b, 0, s, coef, hcoef, zpts, partial, logn, cc);
+    } else {
+        if (ext == 2) hipLaunchKernelGGL((ood_kernel<2, false>), g, b, 0, s, coef, hcoef, zpts, partial, logn, cc);
+        else hipLaunchKernelGGL((ood_kernel<1, false>), g, b, 0, s, coef, hcoef, zpts, partial, logn, cc);
+    }
     hipLaunchKernelGGL(ood_final_kernel, dim3(npoly), dim3(dc.coins ? 128 : 64), 0, s, partial, nblk, ext, ood, dc);
     XFG_CHECK_LAUNCH();
 }
@@ -495,9 +518,13 @@ __global__ __launch_bounds__(1024) void deep_carry_kernel(const u64* partial, co
     }
 }
 __device__ __forceinline__ int dpad(int i) { return i + i / OOD_R; }  // chunk stride R+1: no bank pile-up
-template <int D>
+// CC (as ood_kernel): a constant column's coefficients are (v, 0, ..., 0), so it appears in P1_j, P2_j at
+// j = 0 alone, as a_c v, added there (every field addition returns the canonical value, so the order of
+// the terms changes no bit); c1, c2 and the DeepParams are what they were. A shared column is read
+// from proof 0's coefficients (coef itself)
+template <int D, bool CC>
 __global__ __launch_bounds__(256) void deep_final_kernel(const u64* coef, const u64* hcoef, const DeepParams* dp,
-                                                         const u64* carry, u64* deep, int logn) {
+                                                         const u64* carry, u64* deep, int logn, ColConst colc) {
     using F = FE<D>;
     constexpr int R = OOD_R, CHMAX = 256 * OOD_R, PADN = CHMAX + CHMAX / R;
     __shared__ u64 s1[D][PADN], s2[D][PADN];
@@ -522,6 +549,8 @@ __global__ __launch_bounds__(256) void deep_final_kernel(const u64* coef, const 
         arr[0][k] = v.a;
         if constexpr (D == 2) arr[1][k] = v.b;
     };
+    RowConst rc = {};
+    if constexpr (CC) rc = row_const_uniform(colc, (u64)proof);
     // 1. P1, P2 (coalesced reads) into LDS
 #pragma unroll 2
     for (int r = 0; r < R; r++) {
@@ -529,7 +558,21 @@ __global__ __launch_bounds__(256) void deep_final_kernel(const u64* coef, const 
         const u64 j = base + li;
         F sacc = F::zero();
 #pragma unroll
-        for (int c = 0; c < 7; c++) sacc = fe_add(sacc, fe_mulb(ac[c], co[(u64)c * n + j]));
+        for (int c = 0; c < 7; c++) {
+            if constexpr (CC) {
+                if ((rc.mask >> c) & 1) continue;  // wave-uniform
+                sacc = fe_add(sacc, fe_mulb(ac[c], rc.plane(c, co, coef)[(u64)c * n + j]));
+            } else {
+                sacc = fe_add(sacc, fe_mulb(ac[c], co[(u64)c * n + j]));
+            }
+        }
+        if constexpr (CC) {
+            if (j == 0) {
+#pragma unroll
+                for (int c = 0; c < 7; c++)
+                    if ((rc.mask >> c) & 1) sacc = fe_add(sacc, fe_mulb(ac[c], rc.v[c]));
+            }
+        }
         F p1 = fe_add(sacc, fe_mul(gam, fe_plane<D>(h, n, j))), p2 = sacc;
         if (j == 0) {
             p1 = fe_sub(p1, F::load(P.c1));
@@ -595,19 +638,22 @@ __global__ __launch_bounds__(256) void deep_final_kernel(const u64* coef, const 
     }
 }
 void launch_deep(const u64* coef, const u64* hcoef, const DeepParams* dp, const u64* partial, u64* carry, u64* deep,
-                 int logn, int npoly, int ext, hipStream_t s) {
+                 int logn, int npoly, int ext, hipStream_t s, const ColConst& cc) {
     const u64 n = 1ULL << logn;
     const int T = ood_threads(n), nblk = (int)(n / ((u64)T * OOD_R));
     int logch = 0;
     while ((1ULL << logch) < (u64)T * OOD_R) logch++;
     int ct = 64;
     while (ct < nblk) ct <<= 1;  // nblk <= 1024 (n <= 2^21, 2048 coefficients per block)
-    if (ext == 2) {
-        hipLaunchKernelGGL(deep_carry_kernel<2>, dim3(npoly), dim3(ct), 0, s, partial, dp, carry, nblk, logch);
-        hipLaunchKernelGGL(deep_final_kernel<2>, dim3(nblk, npoly), dim3(T), 0, s, coef, hcoef, dp, carry, deep, logn);
+    const dim3 g(nblk, npoly), b(T);
+    if (ext == 2) hipLaunchKernelGGL(deep_carry_kernel<2>, dim3(npoly), dim3(ct), 0, s, partial, dp, carry, nblk, logch);
+    else hipLaunchKernelGGL(deep_carry_kernel<1>, dim3(npoly), dim3(ct), 0, s, partial, dp, carry, nblk, logch);
+    if (cc.flags) {
+        if (ext == 2) hipLaunchKernelGGL((deep_final_kernel<2, true>), g, b, 0, s, coef, hcoef, dp, carry, deep, logn, cc);
+        else hipLaunchKernelGGL((deep_final_kernel<1, true>), g, b, 0, s, coef, hcoef, dp, carry, deep, logn, cc);
     } else {
-        hipLaunchKernelGGL(deep_carry_kernel<1>, dim3(npoly), dim3(ct), 0, s, partial, dp, carry, nblk, logch);
-        hipLaunchKernelGGL(deep_final_kernel<1>, dim3(nblk, npoly), dim3(T), 0, s, coef, hcoef, dp, carry, deep, logn);
+        if (ext == 2) hipLaunchKernelGGL((deep_final_kernel<2, false>), g, b, 0, s, coef, hcoef, dp, carry, deep, logn, cc);
+        else hipLaunchKernelGGL((deep_final_kernel<1, false>), g, b, 0, s, coef, hcoef, dp, carry, deep, logn, cc);
     }
     XFG_CHECK_LAUNCH();
 }
@@ -697,8 +743,9 @@ void launch_fri_fold(const u64* vals, u64 val_stride, u64 comp_stride, bool cose
 // ============================================================================ gathers
 // all of a unit's opening gathers in one launch: thread i of the grid serves element i - first[k] of
 // segment k (the segments are laid end to end in index order; at most GatherSet::MAX of them).
-// An element of segment cc_seg whose plane is a flagged column is the column's value: that plane of
-// the trace LDE is not written
+// An element of segment cc_seg whose plane is a constant column is the column's value, and one whose
+// plane is a shared column is read at the same place of proof 0's plane (plane = proof * 7 + column):
+// those planes of the trace LDE are not written
 __global__ void gather_set_kernel(GatherSet g, const u64* idx) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= g.first[g.nseg]) return;
@@ -711,7 +758,9 @@ __global__ void gather_set_kernel(GatherSet g, const u64* idx) {
     } else {
         u64 v;
         const u64 plane = src >> g.cc_shift;
-        if (k == g.cc_seg && g.cc.flags[plane]) v = g.cc.vals[plane * g.cc.val_stride];
+        const unsigned f = k == g.cc_seg ? g.cc.flags[plane] : 0u;
+        if (f & COL_CONST) v = g.cc.vals[plane * g.cc.val_stride];
+        else if (f & COL_SHARED) v = ((const u64*)g.src[k])[src - ((plane - plane % 7) << g.cc_shift)];  // proof 0's plane
         else v = ((const u64*)g.src[k])[src];
         ((u64*)g.dst[k])[i - g.first[k]] = v;
     }

@@ -66,30 +66,51 @@ void build_pass_tables(u64* out, int logn, int logbeta, const Tables& T, hipStre
 // inverse: evals[poly][n] at 7^off7 * w_n^i -> coefficients (first `keep` written, stride out_stride)
 void launch_interpolate(const u64* evals, u64 in_stride, u64* out, u64 out_stride, u64* scratch, int npoly, int logn,
                         bool off7, u64 keep, const Tables& T, hipStream_t s, const unsigned char* skip = nullptr);
-// constant columns: flags[col] = 1 where cols[col][0..n) holds one value in every row, else 0
-// (flags: ncols bytes; detection blocks cover CONST_DETECT_SPAN rows each)
+// constant columns: flags[col] = COL_CONST where cols[col][0..n) holds one value in every row, else 0
+// (flags: ncols bytes, the allocation padded to whole 32-bit words; detection blocks cover
+// CONST_DETECT_SPAN rows each).
+// period > 0 (a unit of ncols / period traces of `period` columns each, more than one trace): the same
+// pass also compares column col >= period with column col % period of trace 0, element for element,
+// and flags[col] = COL_SHARED where they are equal and the column is not constant (a constant column
+// stays constant); trace 0's columns are never shared. The allocation then holds const_flag_bytes(ncols):
+// the pass keeps a second byte per column behind the flags.
+// vals (or nullptr): vals[col] = cols[col][0], the value of the column where it is constant
 constexpr int CONST_DETECT_SPAN = 1024, CONST_FILL_SPAN = 4096;
-void launch_const_detect(const u64* cols, int ncols, int logn, unsigned char* flags, hipStream_t s);
+constexpr unsigned char COL_CONST = 1, COL_SHARED = 2;
+__host__ __device__ constexpr size_t detect_same_off(size_t ncols) { return (ncols + 3) & ~(size_t)3; }
+constexpr size_t const_flag_bytes(size_t ncols) { return 2 * detect_same_off(ncols); }
+// a flag byte as a class: 0 live, 1 constant, 2 the same as the unit's first trace's column
+__host__ __device__ constexpr int col_class(unsigned char f) { return (f & COL_CONST) ? 1 : ((f & COL_SHARED) ? 2 : 0); }
+void launch_const_detect(const u64* cols, int ncols, int logn, unsigned char* flags, hipStream_t s, int period = 0,
+                         u64* vals = nullptr);
 // what the NTTs would have produced for the flagged columns, v = src[col * src_stride]:
 // coef[col] = (v, 0, ..., 0) and lde[col][t][m] = v (coset-major planes); coef or lde may be nullptr.
-// The prover fills the coefficients only (launch_trace_lde); the planes are written for xfg_debug_lde_skip alone
+// Outside the prover's chain (its readers take a ColConst): xfg_debug_lde_skip and xfg_debug_interpolate_skip
 void launch_const_fill(const unsigned char* flags, const u64* src, u64 src_stride, u64* coef, u64* lde, int ncols,
                        int logn, int logbeta, hipStream_t s);
 
-// The constant columns as the consumers of a trace LDE [B][7][beta][n] take them: the LDE plane of a
-// flagged column is never written (launch_trace_lde) and its every element is the column's value.
-//   flags  [B * 7] the detection's bytes (device, 4-byte aligned, the allocation padded to whole 32-bit
-//          words); nullptr: dense, every plane is read
-//   vals   the value of column c of proof b lies at vals[(b * 7 + c) * val_stride] (coefficient 0 in coef)
+// The flagged columns as the consumers of the trace's planes take them (the LDE [B][7][beta][n] and the
+// coefficients [B][7][n]): neither plane of a flagged column is ever written (launch_trace_lde). Every
+// element of a constant column's LDE plane is the column's value; a shared column's planes are those of
+// the same column of proof 0, which lie in proof 0's slot of the same buffer.
+//   flags  [B * 7] the detection's bytes (COL_CONST, COL_SHARED; device, 4-byte aligned, the allocation
+//          padded to whole 32-bit words); nullptr: dense, every plane is read
+//   vals   the value of column c of proof b lies at vals[(b * 7 + c) * val_stride]
 struct ColConst {
     const unsigned char* flags = nullptr;
     const u64* vals = nullptr;
     u64 val_stride = 0;
 };
-// one proof's flagged columns in registers: bit c of mask, and v[c] where it is set
+// one proof's flagged columns in registers: bit c of mask (constant) and v[c] where it is set; bit c of
+// shared (never set beside the same bit of mask): the column is read from proof 0's planes
 struct RowConst {
-    unsigned mask;
+    unsigned mask, shared;
     u64 v[7];
+    // base[i] of the proof's own planes, or of proof 0's for a shared column: one select between the
+    // two bases (both wave-uniform in a kernel that runs a block per proof), not a pointer per column
+    __device__ __forceinline__ const u64* plane(int c, const u64* own, const u64* first) const {
+        return (shared >> c) & 1 ? first : own;
+    }
 };
 // for a proof that is the same in every lane (a block per proof): the seven flags come out of two or
 // three aligned 32-bit loads and the values of 64-bit ones at wave-uniform addresses (scalar loads),
@@ -101,10 +122,15 @@ __device__ __forceinline__ RowConst row_const_uniform(const ColConst& cc, u64 pr
     u64 bytes = ((u64)w[0] | ((u64)w[1] << 32)) >> (8 * r);  // flags o .. o + 7 - r
     if (r >= 2) bytes |= (u64)w[2] << (64 - 8 * r);           // o + 8 - r .. (inside the padded allocation)
     RowConst rc;
-    rc.mask = 0;
+    rc.mask = rc.shared = 0;
 #pragma unroll
-    for (int c = 0; c < 7; c++) rc.mask |= ((bytes >> (8 * c)) & 0xFF ? 1u : 0u) << c;
+    for (int c = 0; c < 7; c++) {
+        const unsigned f = (unsigned)(bytes >> (8 * c)) & 0xFF;
+        rc.mask |= (f & COL_CONST ? 1u : 0u) << c;
+        rc.shared |= ((f & (COL_CONST | COL_SHARED)) == COL_SHARED ? 1u : 0u) << c;
+    }
     rc.mask = __builtin_amdgcn_readfirstlane(rc.mask);
+    rc.shared = __builtin_amdgcn_readfirstlane(rc.shared);
 #pragma unroll
     for (int c = 0; c < 7; c++) {
         rc.v[c] = 0;
@@ -122,11 +148,13 @@ __device__ __forceinline__ RowConst row_const_uniform(const ColConst& cc, u64 pr
 // are in flight beside the flags and not behind them: a lone proof waits on this chain
 __device__ __forceinline__ RowConst row_const_lane(const ColConst& cc, u64 proof) {
     RowConst rc;
-    rc.mask = 0;
+    rc.mask = rc.shared = 0;
 #pragma unroll
     for (int c = 0; c < 7; c++) {
         rc.v[c] = cc.vals[(proof * 7 + c) * cc.val_stride];
-        rc.mask |= (cc.flags[proof * 7 + c] ? 1u : 0u) << c;
+        const unsigned f = cc.flags[proof * 7 + c];
+        rc.mask |= (f & COL_CONST ? 1u : 0u) << c;
+        rc.shared |= ((f & (COL_CONST | COL_SHARED)) == COL_SHARED ? 1u : 0u) << c;
     }
     return rc;
 }
@@ -210,12 +238,14 @@ void launch_constraint_eval(const u64* lde, const AirConst* air, const u64* coef
 // ---- OOD / DEEP ----
 // partial: [B][ood_partial_count(logn)][15] per-block sums, kept for launch_deep
 // ext = D: zpts [B][2][D], hcoef planes [B][D][n], partial [B][count][15][D], ood [B][15][D]
+// cc (both; flags set): coef is the trace's coefficients [B][7][n] whose flagged columns' planes hold
+// nothing -- a constant column is its value, a shared one proof 0's plane; without it every plane is read
 void launch_ood(const u64* coef, const u64* hcoef, const u64* zpts, u64* partial, u64* ood, int logn, int npoly,
-                int ext, hipStream_t s, const DeepCoinStep& dc = DeepCoinStep{});
+                int ext, hipStream_t s, const DeepCoinStep& dc = DeepCoinStep{}, const ColConst& cc = ColConst{});
 u64 ood_partial_count(int logn);
 // carry: [B][ood_partial_count(logn)][2][D]; deep planes [B][D][n]
 void launch_deep(const u64* coef, const u64* hcoef, const DeepParams* dp, const u64* partial, u64* carry, u64* deep,
-                 int logn, int npoly, int ext, hipStream_t s);
+                 int logn, int npoly, int ext, hipStream_t s, const ColConst& cc = ColConst{});
 
 // ---- FRI ----
 // FRI layer value at natural index K of a layer stored coset-major (layer 0) or natural
@@ -234,7 +264,8 @@ void launch_fri_fold(const u64* vals, u64 val_stride, u64 comp_stride, bool cose
 // several gathers in one launch: segment k copies src[k][idx[first[k] + j]] to dst[k][j],
 // j < first[k + 1] - first[k], as u64 or as Digest (digest[k]).
 // Segment cc_seg (-1: none) reads a trace LDE whose flagged planes hold nothing: an index whose plane
-// idx >> cc_shift (cc_shift = logn + logbeta, the plane = proof * 7 + column) is flagged yields cc's value
+// idx >> cc_shift (cc_shift = logn + logbeta, the plane = proof * 7 + column) is constant yields cc's value,
+// and one whose plane is shared is read from the same column's plane of proof 0
 struct GatherSet {
     static constexpr int MAX = 24;
     int nseg = 0;

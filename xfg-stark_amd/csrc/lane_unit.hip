@@ -34,7 +34,8 @@ void size_trace_lde(Lane* c, size_t B, const ProofShape& sh) {
     c->coef.ensure(B * 7 * sh.n);
     c->scratch.ensure(B * 7 * sh.N);
     c->lde.ensure(B * 7 * sh.N);
-    c->const_col.ensure((B * 7 + 3) & ~(size_t)3);
+    c->const_col.ensure(const_flag_bytes(B * 7));
+    c->const_val.ensure(B * 7);
 }
 void size_constraint_eval(Lane* c, size_t B, const ProofShape& sh) {
     c->air.ensure(B);
@@ -160,17 +161,22 @@ static void upload_unit_inputs(Lane* c, ProofJob* jobs, int B, const ProofShape&
 ColConst trace_const(const Lane* c, const ProofShape& sh) {
     ColConst cc;
     cc.flags = c->const_col.p;
-    cc.vals = c->coef.p;  // coefficient 0 of a constant column is its value (launch_const_fill)
-    cc.val_stride = sh.n;
+    cc.vals = c->const_val.p;  // [B][7], element 0 of every column (launch_const_detect)
+    cc.val_stride = 1;
     return cc;
 }
 
 void launch_trace_lde(Lane* c, const Tables& T, int B, const ProofShape& sh, bool probe) {
     hipStream_t s = c->stream;
     const unsigned char* skip = c->const_col.p;
-    // xfg_debug_poison_lde: nothing an earlier unit left in the buffer can pass for a plane of this one
-    if (c->poison_lde) HIPCHK(hipMemsetAsync(c->lde.p, 0xFF, (size_t)B * 7 * sh.N * 8, s));
-    launch_const_detect(c->trace.p, B * 7, sh.logn, c->const_col.p, s);
+    // xfg_debug_poison_lde: nothing an earlier unit left in the buffers can pass for a plane of this one
+    // (the LDE planes and the coefficients of constant and shared columns are never written)
+    if (c->poison_lde) {
+        HIPCHK(hipMemsetAsync(c->lde.p, 0xFF, (size_t)B * 7 * sh.N * 8, s));
+        HIPCHK(hipMemsetAsync(c->coef.p, 0xFF, (size_t)B * 7 * sh.n * 8, s));
+    }
+    // constant columns, and the columns of proofs 1 .. B - 1 that equal proof 0's: one pass over the trace
+    launch_const_detect(c->trace.p, B * 7, sh.logn, c->const_col.p, s, 7, c->const_val.p);
     launch_interpolate(c->trace.p, sh.n, c->coef.p, sh.n, c->scratch.p, B * 7, sh.logn, false, sh.n, T, s, skip);
     if (probe) {
         if (!c->lde_ev[0]) {
@@ -181,10 +187,8 @@ void launch_trace_lde(Lane* c, const Tables& T, int B, const ProofShape& sh, boo
     }
     launch_lde(c->coef.p, sh.n, c->lde.p, c->scratch.p, B * 7, sh.logn, sh.logbeta, T, s, skip);
     if (probe) HIPCHK(hipEventRecord(c->lde_ev[1], s));
-    // the constant columns' coefficients (outside the probe's window: it times the transforms of the
-    // polynomials it counts). Their LDE planes are never written: every reader of c->lde takes such a
-    // column's value from trace_const
-    launch_const_fill(skip, c->trace.p, sh.n, c->coef.p, nullptr, B * 7, sh.logn, sh.logbeta, s);
+    // the planes of the flagged columns, in c->coef and in c->lde, are never written: every reader of
+    // either takes trace_const along
 }
 
 // FRI layers (FriProver::build_layers), folding factor `fold`: commit -> reseed -> draw alpha -> fold,
@@ -335,10 +339,10 @@ static ReplayView enqueue_commit_chain(Lane* c, const Tables& T, const u64* ce_d
     dc.zpts = c->zpts.p;
     dc.dp = c->dp.p;
     dc.ginv = gl_inv(g);
-    launch_ood(c->coef.p, c->hcoef.p, c->zpts.p, c->partial.p, c->ood.p, logn, B, DE, s, dc);
+    launch_ood(c->coef.p, c->hcoef.p, c->zpts.p, c->partial.p, c->ood.p, logn, B, DE, s, dc, cc);
     stage_mark(c, 6);
     // ---- 5. DEEP composition polynomial (coefficient form) + its LDE
-    launch_deep(c->coef.p, c->hcoef.p, c->dp.p, c->partial.p, c->carry.p, c->deep.p, logn, B, DE, s);
+    launch_deep(c->coef.p, c->hcoef.p, c->dp.p, c->partial.p, c->carry.p, c->deep.p, logn, B, DE, s, cc);
     launch_lde(c->deep.p, n, c->f0.p, c->scratch.p, B * DE, logn, logbeta, T, s);
     // degree check: deg(DEEP) == n - 2  <=>  coefficient n-2 != 0 (coefficient n-1 is 0 by construction)
     HIPCHK(hipMemcpy2DAsync(c->dn2.p, 8, c->deep.p + (n - 2), n * 8, 8, (size_t)B * DE, hipMemcpyDeviceToDevice, s));
@@ -436,9 +440,13 @@ void prove_lane(Lane* c, const Tables& T, const u64* ce_div, ProofJob* jobs, int
     const ReplayView rv = enqueue_commit_chain(c, T, ce_div, jobs, B, ts, sh, o, g, ht);
     HIPCHK(hipStreamSynchronize(c->stream));
     ht.mark("sync_rem");
-    // trace columns that went through the NTTs (the rest were constant: detected, filled in)
-    u64 live_cols = 0;
-    for (int k = 0; k < B * 7; k++) live_cols += c->h_const_col[k] ? 0 : 1;
+    // trace columns that went through the NTTs; the rest were found constant, or the same as proof 0's
+    u64 live_cols = 0, shared_cols = 0;
+    for (int k = 0; k < B * 7; k++) {
+        const int cls = col_class(c->h_const_col[k]);
+        live_cols += cls == 0 ? 1 : 0;
+        shared_cols += cls == 2 ? 1 : 0;
+    }
     pool.parallel_for(B, [jobs, B, &sh, g, &rv](int b) { replay_transcript(jobs[b], b, B, sh, g, rv); });
 
     const auto t_q0 = clk::now();
@@ -495,7 +503,7 @@ void prove_lane(Lane* c, const Tables& T, const u64* ce_div, ProofJob* jobs, int
         else if (key != TRACE_KEY_VALID)
             jobs[b].status = (key >> 62) == TRACE_KEY_NONCANONICAL ? XFG_INVALID_ARGUMENT : XFG_INVALID_TRACE;
     }
-    ht.dump(B, (long)((u64)B * 7 - live_cols));
+    ht.dump(B, (long)((u64)B * 7 - live_cols - shared_cols), (long)shared_cols);
     if (c->lde_probe) {  // the stream has passed both events (root / query fetches synchronised it)
         float ms = 0;
         HIPCHK(hipEventSynchronize(c->lde_ev[1]));

@@ -91,10 +91,15 @@ __device__ __forceinline__ void quad_level(const Digest* src, bool act, int i, i
 // ============================================================================ LDE leaves
 // One leaf's elements: row[c] = column c of the LDE at coset t, row m. CC (a trace LDE with constant
 // columns, NC = 7; kernels.hpp ColConst): a column flagged in rc comes from rc and its load is not
-// issued. CC = false is the dense read and takes no RowConst (NoConst)
+// issued; a column shared in rc is read at the same place of proof 0's planes, `back` words before the
+// proof's own (one offset, selected per column: wave-uniform where a block serves one proof, per lane in
+// the openings). CC = false is the dense read and takes no RowConst (NoConst)
 struct NoConst {};
+struct RowConstBack : RowConst {
+    u64 back;  // words from proof 0's planes to the proof's own: proof * 7 * beta * n
+};
 template <bool CC>
-using RowConstOf = std::conditional_t<CC, RowConst, NoConst>;
+using RowConstOf = std::conditional_t<CC, RowConstBack, NoConst>;
 template <int NC, int LOGB, bool CC>
 __device__ __forceinline__ void lde_row(const u64* base, u64 n, u64 m, int t, const RowConstOf<CC>& rc, u64 (&row)[NC]) {
     static_assert(!CC || NC == 7, "constant columns are those of the trace");
@@ -105,8 +110,10 @@ __device__ __forceinline__ void lde_row(const u64* base, u64 n, u64 m, int t, co
                 row[c] = rc.v[c];
                 continue;
             }
+            row[c] = (base - ((rc.shared >> c) & 1 ? rc.back : 0))[((u64)c * (1 << LOGB) + t) * n + m];
+        } else {
+            row[c] = base[((u64)c * (1 << LOGB) + t) * n + m];
         }
-        row[c] = base[((u64)c * (1 << LOGB) + t) * n + m];
     }
 }
 
@@ -145,10 +152,17 @@ __device__ __forceinline__ Digest lde_subtree_wide(const u64* base, u64 n, u64 m
 }
 
 // the constant columns of a block's proof (a block per proof: flags and values are read once, wave-uniform)
+// back: the words between proof 0's planes and this proof's (RowConstBack)
 template <bool CC>
-__device__ __forceinline__ RowConstOf<CC> block_row_const(const ColConst& cc, int proof) {
-    if constexpr (CC) return row_const_uniform(cc, (u64)proof);
-    else return NoConst{};
+__device__ __forceinline__ RowConstOf<CC> block_row_const(const ColConst& cc, int proof, u64 back) {
+    if constexpr (CC) {
+        RowConstBack rc;
+        static_cast<RowConst&>(rc) = row_const_uniform(cc, (u64)proof);
+        rc.back = back;
+        return rc;
+    } else {
+        return NoConst{};
+    }
 }
 
 // one LDE row per thread, min(256, n) rows per block: the row's 2^LOGB-leaf subtree (top at heap level
@@ -165,8 +179,9 @@ __global__ __launch_bounds__(256) void leaves_row_kernel(const u64* lde, Digest*
     const u64 n = 1ULL << logn;
     const int proof = blockIdx.y;
     const u64 m = (u64)blockIdx.x * blockDim.x + threadIdx.x;  // grid covers n exactly
-    const u64* base = lde + (u64)proof * NC * (1 << LOGB) * n;
-    const RowConstOf<CC> rc = block_row_const<CC>(cc, proof);
+    const u64 back = (u64)proof * NC * (1 << LOGB) * n;
+    const u64* base = lde + back;
+    const RowConstOf<CC> rc = block_row_const<CC>(cc, proof, back);
     Digest d = lde_subtree_wide<NC, LOGB, LOGB, CC>(base, n, m, 0, rc);
     block_tree_up(d, nodes_all + (u64)proof * node_stride, n, lds, blockDim.x / 4);
 }
@@ -186,8 +201,9 @@ __global__ __launch_bounds__(256) void leaves_row2_kernel(const u64* lde, Digest
     const u64 n = 1ULL << logn;
     const int proof = blockIdx.y, t = threadIdx.x, h = t & ((1 << LOGL) - 1), rl = t >> LOGL;
     const u64 m = (u64)blockIdx.x * RB + rl;
-    const u64* base = lde + (u64)proof * NC * (1 << LOGB) * n + (u64)h * (1 << (LOGB - LOGL)) * n;
-    const RowConstOf<CC> rc = block_row_const<CC>(cc, proof);
+    const u64 back = (u64)proof * NC * (1 << LOGB) * n;
+    const u64* base = lde + back + (u64)h * (1 << (LOGB - LOGL)) * n;
+    const RowConstOf<CC> rc = block_row_const<CC>(cc, proof, back);
     Digest d = lde_subtree_wide<NC, LOGB, LOGB - LOGL, CC>(base, n, m, 0, rc);
 #pragma unroll
     for (int k = 0; k < LOGL; k++) {
@@ -228,7 +244,10 @@ __global__ __launch_bounds__(64) void open_rows_kernel(const u64* lde, const u64
     const u64* base = lde + proof * NC * (1 << LOGB) * n;
     Digest* local = out + e * (2 << LOGB);
     RowConstOf<CC> rc;
-    if constexpr (CC) rc = row_const_lane(cc, proof);
+    if constexpr (CC) {
+        static_cast<RowConst&>(rc) = row_const_lane(cc, proof);
+        rc.back = proof * NC * (1 << LOGB) * n;
+    }
     u64 row[NC];
     lde_row<NC, LOGB, CC>(base, n, m, t, rc, row);
     Digest d = b3_hash_elems<NC>(row);

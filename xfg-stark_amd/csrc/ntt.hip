@@ -980,30 +980,76 @@ static void ntt_run(NttArgs& a, int npoly, bool inv, hipStream_t s) {
 // ---------------------------------------------------------------- constant columns
 // A column that holds one value v in every row interpolates to the constant v, and its LDE is v at
 // every point: such columns take no NTT. const_detect_kernel finds them in whatever trace arrives,
-// the NTT kernels return at once for them (NttArgs::skip), const_fill_kernel writes their coefficients.
-// Their LDE planes stay unwritten in the prover: the readers of the trace LDE take the value from a
-// ColConst (kernels.hpp); const_fill_kernel's lde branch serves xfg_debug_lde_skip alone.
-__global__ void const_flags_init_kernel(unsigned char* flags, int count) {
+// the NTT kernels return at once for them (NttArgs::skip). Their coefficient and LDE planes stay
+// unwritten in the prover: every reader of either takes the value from a ColConst (kernels.hpp);
+// const_fill_kernel serves xfg_debug_lde_skip and xfg_debug_interpolate_skip alone.
+//
+// Shared columns: a column of proof b > 0 of a unit that equals the same column of the unit's proof 0
+// element for element has proof 0's coefficients and proof 0's LDE: it takes no NTT either, and its
+// readers go to proof 0's planes (ColConst). The same detection pass finds them, in whatever traces
+// arrive; the representative is proof 0 and nothing more general, so a unit whose first trace differs
+// from the others shares nothing. A column that is constant stays constant (cheaper for every reader).
+// The pass keeps two bytes per column, both preset to 1 and both only ever overwritten with 0, so that
+// every writer of a byte stores the same value and nothing needs an atomic (one byte with two bits,
+// cleared by atomic ANDs, measured 127 us per 64-proof unit against 41 for the constancy pass alone and
+// 51 for this form, profiles/r15: the blocks of a proof's columns all hit the same one or two words):
+// flags[col], the constancy, and same[col] = flags[detect_same_off(ncols)
+// + col]. const_class_kernel then folds the second into the first as COL_SHARED
+__global__ void const_flags_init_kernel(unsigned char* flags, int count, int period) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) flags[i] = 1;
+    if (i >= count) return;
+    flags[i] = 1;
+    if (period) flags[detect_same_off(count) + i] = i >= period ? 1 : 0;  // trace 0's columns are never shared
 }
-// flags[col] (preset to 1) -> 0 where some element of cols[col][0..n) differs from element 0. One block
-// per CONST_DETECT_SPAN rows of a column (min(256, n) threads, coalesced strides); a thread that saw
-// a difference stores 0 -- every writer stores the same byte, so no atomics
-__global__ __launch_bounds__(256) void const_detect_kernel(const u64* cols, u64 n, unsigned char* flags) {
+// flags[col] (preset to 1) -> 0 where some element of cols[col][0..n) differs from element 0 and, SHARE,
+// same[col] -> 0 where some element differs from the same element of column col % period (trace 0's; the
+// columns below period are trace 0's own and are compared with nothing). One block per
+// CONST_DETECT_SPAN rows of a column (min(256, n) threads, coalesced strides); a thread that saw a
+// difference stores 0. The pass reads the trace once; trace 0's column (8 n bytes) is read again by
+// every other trace's blocks, from the cache.
+// vals[col] = element 0 (block 0 of the column; read only where the column turns out constant)
+template <bool SHARE>
+__global__ __launch_bounds__(256) void const_detect_kernel(const u64* cols, u64 n, unsigned char* flags, int period,
+                                                           u64* vals) {
     const int col = blockIdx.y;
     const u64* c = cols + (u64)col * n;
     const u64 first = c[0];
     const u64 i0 = (u64)blockIdx.x * CONST_DETECT_SPAN, i1 = i0 + CONST_DETECT_SPAN < n ? i0 + CONST_DETECT_SPAN : n;
+    if (vals && blockIdx.x == 0 && threadIdx.x == 0) vals[col] = first;
     u64 diff = 0;
-    for (u64 i = i0 + threadIdx.x; i < i1; i += blockDim.x) diff |= c[i] ^ first;
+    if (SHARE && col >= period) {  // block-uniform
+        const u64* c0 = cols + (u64)(col % period) * n;
+        u64 diff0 = 0;
+#pragma unroll 4
+        for (u64 i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
+            const u64 x = c[i];
+            diff |= x ^ first;
+            diff0 |= x ^ c0[i];
+        }
+        if (diff0) flags[detect_same_off(gridDim.y) + col] = 0;
+    } else {
+        for (u64 i = i0 + threadIdx.x; i < i1; i += blockDim.x) diff |= c[i] ^ first;
+    }
     if (diff) flags[col] = 0;
 }
-void launch_const_detect(const u64* cols, int ncols, int logn, unsigned char* flags, hipStream_t s) {
+// flags[col]: 1 -> COL_CONST, else COL_SHARED where same[col] is still set, else 0
+__global__ void const_class_kernel(unsigned char* flags, int count) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) flags[i] = flags[i] ? COL_CONST : (flags[detect_same_off(count) + i] ? COL_SHARED : 0);
+}
+void launch_const_detect(const u64* cols, int ncols, int logn, unsigned char* flags, hipStream_t s, int period,
+                         u64* vals) {
     const u64 n = 1ULL << logn;
-    hipLaunchKernelGGL(const_flags_init_kernel, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, s, flags, ncols);
-    hipLaunchKernelGGL(const_detect_kernel, dim3((unsigned)((n + CONST_DETECT_SPAN - 1) / CONST_DETECT_SPAN), ncols),
-                       dim3((unsigned)std::min<u64>(256, n)), 0, s, cols, n, flags);
+    if (period <= 0 || ncols <= period) period = 0;  // one trace: nothing to share, nothing extra is run
+    const dim3 gi((unsigned)((ncols + 255) / 256)), bi(256);
+    hipLaunchKernelGGL(const_flags_init_kernel, gi, bi, 0, s, flags, ncols, period);
+    const dim3 g((unsigned)((n + CONST_DETECT_SPAN - 1) / CONST_DETECT_SPAN), ncols), b((unsigned)std::min<u64>(256, n));
+    if (period) {
+        hipLaunchKernelGGL(const_detect_kernel<true>, g, b, 0, s, cols, n, flags, period, vals);
+        hipLaunchKernelGGL(const_class_kernel, gi, bi, 0, s, flags, ncols);
+    } else {
+        hipLaunchKernelGGL(const_detect_kernel<false>, g, b, 0, s, cols, n, flags, period, vals);
+    }
 }
 // outputs of the flagged columns, v = src[col * src_stride]: coef[col] = (v, 0, ..., 0) (n entries) and
 // lde[col][t][m] = v (N = beta n entries, the coset-major plane is simply full of v); either may be null.

@@ -60,10 +60,12 @@ struct Lane {
     DBuf<DeepParams> dp;
     DBuf<DevCoin> dcoin;  // device-side transcript
     DBuf<int> dfail;
-    // [B][7] (padded to whole 32-bit words): 1 where a trace column holds one value in every row
-    // (launch_const_detect); such columns skip the interpolation and the LDE. h_const_col: the unit's
-    // flags in the replay block, for the counters
+    // [B][7] (padded to whole 32-bit words): COL_CONST where a trace column holds one value in every row,
+    // COL_SHARED where it equals the same column of the unit's proof 0 (launch_const_detect); such columns
+    // skip the interpolation and the LDE. const_val [B][7]: element 0 of every column, the value of a
+    // constant one. h_const_col: the unit's flags in the replay block, for the counters
     DBuf<unsigned char> const_col;
+    DBuf<u64> const_val;
     const unsigned char* h_const_col = nullptr;
     // caller-supplied traces (xfg_prove_trace_batch): tkeys [B] the check kernel's word per proof
     // (launch_trace_check), h_tkeys the unit's words in the replay block; h_trace the pinned staging host
@@ -162,11 +164,13 @@ struct HostTrace {
     void mark(const char* what) {
         if (trace_on()) m.push_back({what, std::chrono::steady_clock::now()});
     }
-    // const_cols: trace columns found constant and not transformed (-1: not a proving batch)
-    void dump(int B, long const_cols = -1) {
+    // const_cols, shared_cols: trace columns found constant, or equal to the unit's first proof's, and
+    // not transformed (-1: not a proving batch)
+    void dump(int B, long const_cols = -1, long shared_cols = -1) {
         if (!trace_on() || m.size() < 2) return;
         std::string line = "[xfg] B=" + std::to_string(B);
         if (const_cols >= 0) line += " const_cols=" + std::to_string(const_cols);
+        if (shared_cols >= 0) line += " shared_cols=" + std::to_string(shared_cols);
         for (size_t i = 1; i < m.size(); i++) {
             char buf[96];
             snprintf(buf, sizeof buf, " %s=%.2f", m[i].first,
@@ -231,9 +235,10 @@ void size_trace_lde(Lane* c, size_t B, const ProofShape& sh);        // trace, c
 void size_constraint_eval(Lane* c, size_t B, const ProofShape& sh);  // air, coeffs, ce
 void size_ood_deep(Lane* c, size_t B, const ProofShape& sh);  // hcoef, zpts, partial, ood, dp, carry, deep
 // trace -> coefficients -> LDE (DefaultTraceLde::new); probe: the xfg_lde_probe events around the LDE.
-// Constant columns are detected in the trace as it lies in c->trace (whatever put it there) and not
-// transformed: the flags stay in c->const_col, their coefficients are filled in, and their planes of
-// c->lde are left unwritten. Whatever reads c->lde afterwards takes trace_const along
+// Constant columns, and columns equal to proof 0's, are detected in the trace as it lies in c->trace
+// (whatever put it there) and not transformed: the flags stay in c->const_col, the values in
+// c->const_val, and their planes of c->coef and c->lde are left unwritten. Whatever reads either
+// afterwards takes trace_const along
 void launch_trace_lde(Lane* c, const Tables& T, int B, const ProofShape& sh, bool probe);
 ColConst trace_const(const Lane* c, const ProofShape& sh);
 // the proof-of-work search on the device for the B seeds the caller wrote to grind_seeds(c, B): launched on

@@ -125,6 +125,11 @@ if hasattr(_lib, "xfg_debug_merkle_lde_const"):  # absent from builds that fill 
     _lib.xfg_debug_merkle_lde_const.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, _u64p, _u8p,
                                                 _u64p, _u64p, C.c_uint64, _u8p, _u8p]
     _lib.xfg_debug_poison_lde.argtypes = [C.c_void_p, C.c_int]
+if hasattr(_lib, "xfg_debug_col_classes"):  # absent from builds without shared trace columns (XFG_LIB A/B)
+    _lib.xfg_debug_col_classes.argtypes = [C.c_void_p, _u64p, C.c_uint32, C.c_uint64, _u8p, _u64p]
+    _lib.xfg_debug_ood_deep_const.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, _u64p, _u8p, _u64p, _u64p,
+                                              _u64p, _u64p, C.POINTER(C.c_uint32), _u64p, C.c_uint64, _u64p, _u64p,
+                                              _u64p, C.POINTER(C.c_uint32), _u64p, C.POINTER(C.c_int)]
 if hasattr(_lib, "xfg_debug_fri_fold_f"):  # absent from builds older than folding factors 2, 4 and 16
     _lib.xfg_debug_fri_fold_f.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                           C.c_uint32, _u64p, _u64p, _u64p]
@@ -881,6 +886,48 @@ class XfgBurnMintProver:
         if st:
             raise self._err(st)
         return out
+
+    def debug_col_classes(self, trace, values=False):
+        """the unit's column detection as the prover runs it (xfg_debug_col_classes): trace [B,7,n] -> classes
+        [B,7], 0 live, 1 constant, 2 the same as trace 0's column; values=True: also element 0 of every column"""
+        import numpy as np
+        tr = np.ascontiguousarray(trace, dtype=np.uint64)
+        B, width, n = tr.shape
+        if width != 7:
+            raise XfgStarkError(9, "debug_col_classes: trace [B,7,n]")
+        out = np.zeros((B, 7), dtype=np.uint8)
+        vals = np.zeros((B, 7), dtype=np.uint64)
+        st = _lib.xfg_debug_col_classes(self._ctx, tr.ctypes.data_as(_u64p), B, n, out.ctypes.data_as(_u8p),
+                                        vals.ctypes.data_as(_u64p))
+        if st:
+            raise self._err(st)
+        return (out, vals) if values else out
+
+    def debug_ood_deep_const(self, coef, flags, vals, hcoef, zpts, coeffs):
+        """debug_ood_deep_e without coins on coefficients behind a column descriptor (xfg_debug_ood_deep_const):
+        flags [B,7] 1 = constant with value vals [B,7], 2 = the coefficients of instance 0's column; the
+        flagged planes of coef are replaced by 0xFF bytes on the device -> (ood [B,15,ext], deep [B,ext,n])"""
+        import numpy as np
+        c = np.ascontiguousarray(coef, dtype=np.uint64)
+        hc = np.ascontiguousarray(hcoef, dtype=np.uint64)
+        zp = np.ascontiguousarray(zpts, dtype=np.uint64)
+        co = np.ascontiguousarray(coeffs, dtype=np.uint64)
+        f = np.ascontiguousarray(flags, dtype=np.uint8)
+        v = np.ascontiguousarray(vals, dtype=np.uint64)
+        B, _, n = c.shape
+        ext = hc.shape[1]
+        if (c.shape[1] != 7 or hc.shape != (B, ext, n) or zp.shape != (B, 2, ext) or co.shape != (B, 8, ext)
+                or f.shape != (B, 7) or v.shape != (B, 7)):
+            raise XfgStarkError(9, "debug_ood_deep_const: coef [B,7,n], flags and vals [B,7], hcoef [B,ext,n], "
+                                   "zpts [B,2,ext], coeffs [B,8,ext]")
+        ood = np.zeros((B, 15, ext), dtype=np.uint64)
+        deep = np.zeros((B, ext, n), dtype=np.uint64)
+        p = lambda a: a.ctypes.data_as(_u64p)
+        st = _lib.xfg_debug_ood_deep_const(self._ctx, B, n, ext, p(c), f.ctypes.data_as(_u8p), p(v), p(hc), p(zp), p(co),
+                                           None, None, 0, p(ood), p(deep), None, None, None, None)
+        if st:
+            raise self._err(st)
+        return ood, deep
 
     def debug_ood_deep(self, coef, hcoef, zpts, coeffs):
         """OOD + DEEP kernels: coef [B,7,n], hcoef [B,n], zpts [B,2], coeffs [B,8] -> (ood [B,15], deep [B,n])"""
