@@ -142,6 +142,22 @@ __host__ __device__ constexpr unsigned b3_perm_mask(unsigned z) {
 #define XFG_B3_ROUND_Z(m, Z) XFG_B3_ROUND_C(m)
 #endif
 
+// rounds 2-7 on the state round 1 left, then the first 8 output words; m is round 1's message (permuted here)
+template <unsigned ZM>
+__host__ __device__ __forceinline__ void b3_rounds_2_7(uint32_t (&s)[16], uint32_t m[16], uint32_t out[8]) {
+    [[maybe_unused]] constexpr unsigned Z2 = b3_perm_mask(ZM), Z3 = b3_perm_mask(Z2), Z4 = b3_perm_mask(Z3),
+                       Z5 = b3_perm_mask(Z4), Z6 = b3_perm_mask(Z5), Z7 = b3_perm_mask(Z6);
+    XFG_B3_PERMUTE(m);
+    XFG_B3_ROUND_Z(m, Z2); XFG_B3_PERMUTE(m);
+    XFG_B3_ROUND_Z(m, Z3); XFG_B3_PERMUTE(m);
+    XFG_B3_ROUND_Z(m, Z4); XFG_B3_PERMUTE(m);
+    XFG_B3_ROUND_Z(m, Z5); XFG_B3_PERMUTE(m);
+    XFG_B3_ROUND_Z(m, Z6); XFG_B3_PERMUTE(m);
+    XFG_B3_ROUND_Z(m, Z7);
+#pragma unroll
+    for (int i = 0; i < 8; i++) out[i] = b3_xor(s[i], s[i + 8]);
+}
+
 // compression returning the first 8 output words (chaining value / digest); ZM: message words known
 // to be zero (bit i = m[i]), a compile-time hint for the device rounds (any value is correct for 0)
 template <unsigned ZM = 0>
@@ -150,8 +166,6 @@ __host__ __device__ __forceinline__ void b3_compress(const uint32_t cv[8], uint3
     uint32_t s[16] = {cv[0], cv[1], cv[2], cv[3], cv[4], cv[5], cv[6], cv[7],
                       XFG_B3_IV0, XFG_B3_IV1, XFG_B3_IV2, XFG_B3_IV3,
                       (uint32_t)counter, (uint32_t)(counter >> 32), block_len, flags};
-    [[maybe_unused]] constexpr unsigned Z2 = b3_perm_mask(ZM), Z3 = b3_perm_mask(Z2), Z4 = b3_perm_mask(Z3),
-                       Z5 = b3_perm_mask(Z4), Z6 = b3_perm_mask(Z5), Z7 = b3_perm_mask(Z6);
     // round 1: the column half in C (the IV / counter / flag words of the state fold into it); the
     // diagonal half as a block too, unless a column G had no message (both words zero): its outputs
     // are then compile-time constants the C diagonal half folds (short element hashes)
@@ -162,15 +176,7 @@ __host__ __device__ __forceinline__ void b3_compress(const uint32_t cv[8], uint3
         XFG_B3_DIAG_C(m);
     else
         XFG_B3_DIAG_Z(m, ZM);
-    XFG_B3_PERMUTE(m);
-    XFG_B3_ROUND_Z(m, Z2); XFG_B3_PERMUTE(m);
-    XFG_B3_ROUND_Z(m, Z3); XFG_B3_PERMUTE(m);
-    XFG_B3_ROUND_Z(m, Z4); XFG_B3_PERMUTE(m);
-    XFG_B3_ROUND_Z(m, Z5); XFG_B3_PERMUTE(m);
-    XFG_B3_ROUND_Z(m, Z6); XFG_B3_PERMUTE(m);
-    XFG_B3_ROUND_Z(m, Z7);
-#pragma unroll
-    for (int i = 0; i < 8; i++) out[i] = b3_xor(s[i], s[i + 8]);
+    b3_rounds_2_7<ZM>(s, m, out);
 }
 
 // BLAKE3 of a single block of `len` (<= 64) bytes given as 16 LE words (zero padded)
@@ -232,6 +238,116 @@ __host__ __device__ __forceinline__ Digest b3_hash_elems(const uint64_t* e) {
         b3_compress<0xFFFFu & ~((1u << (2 * KL)) - 1u)>(cv, m, 8 * KL, 0, B3_CHUNK_END | B3_ROOT, d.w);
         return d;
     }
+}
+
+// ---- the hash of a seven-element row (b3_hash_elems<7>: one compression, element c = message words 2c and
+// 2c + 1, words 14 and 15 zero, a compile-time initial state) when some elements are the same for every
+// row hashed (the constant columns of a trace, bit c of const_mask). Round 1's G functions whose inputs are
+// all such elements give the same state words for every row: they are run once (b3_row7_prefix) and each
+// row resumes from them (b3_hash_row7), running the round-1 G's left and rounds 2-7.
+// Which G's, bit g of the result (0..3 the column half's G_g, 4..7 the diagonal half's): column G_i reads
+// element i alone; a diagonal G reads one output word of every column G, and elements 4, 5, 6 or (bit 7)
+// the zero words
+__host__ __device__ constexpr unsigned b3_row7_uniform_gs(unsigned const_mask) {
+    unsigned u = 0;
+    for (int i = 0; i < 4; i++)
+        if ((const_mask >> i) & 1) u |= 1u << i;
+    if (u == 0xFu) {
+        for (int j = 0; j < 3; j++)
+            if ((const_mask >> (4 + j)) & 1) u |= 16u << j;
+        u |= 128u;
+    }
+    return u;
+}
+// G on operands that are the same in every lane, in scalar instructions on the device. There is no scalar
+// rotate, and the compiler takes a rotate it recognises to the vector unit (v_alignbit_b32) with everything
+// behind it: the empty asm keeps one shift in a scalar register and the pair apart
+__host__ __device__ __forceinline__ uint32_t b3_rotr_scalar(uint32_t x, int n) {
+    uint32_t lo = x >> n;
+    const uint32_t hi = x << (32 - n);
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+s"(lo));
+#endif
+    return lo | hi;
+}
+#define XFG_B3_G_PLAIN(a, b, c, d, x, y)              \
+    do {                                              \
+        s[a] = s[a] + s[b] + (x);                     \
+        s[d] = b3_rotr_scalar(s[d] ^ s[a], 16);       \
+        s[c] = s[c] + s[d];                           \
+        s[b] = b3_rotr_scalar(s[b] ^ s[c], 12);       \
+        s[a] = s[a] + s[b] + (y);                     \
+        s[d] = b3_rotr_scalar(s[d] ^ s[a], 8);        \
+        s[c] = s[c] + s[d];                           \
+        s[b] = b3_rotr_scalar(s[b] ^ s[c], 7);        \
+    } while (0)
+// state word w after the latest round-1 G in `ugs` that writes it (the initial state where there is none)
+struct B3RowPrefix {
+    uint32_t s[16];
+    unsigned ugs;
+};
+#define XFG_B3_ROW7_INIT                                                                                     \
+    {XFG_B3_IV, XFG_B3_IV0, XFG_B3_IV1, XFG_B3_IV2, XFG_B3_IV3, 0u, 0u, 56u, B3_CHUNK_START | B3_CHUNK_END | B3_ROOT}
+// v[c]: the value of constant element c (the others are not read)
+__host__ __device__ __forceinline__ B3RowPrefix b3_row7_prefix(const uint64_t* v, unsigned const_mask) {
+    B3RowPrefix p = {XFG_B3_ROW7_INIT, b3_row7_uniform_gs(const_mask & 0x7Fu)};
+    uint32_t* s = p.s;
+    const unsigned u = p.ugs;
+    if (u & 1u) XFG_B3_G_PLAIN(0, 4, 8, 12, (uint32_t)v[0], (uint32_t)(v[0] >> 32));
+    if (u & 2u) XFG_B3_G_PLAIN(1, 5, 9, 13, (uint32_t)v[1], (uint32_t)(v[1] >> 32));
+    if (u & 4u) XFG_B3_G_PLAIN(2, 6, 10, 14, (uint32_t)v[2], (uint32_t)(v[2] >> 32));
+    if (u & 8u) XFG_B3_G_PLAIN(3, 7, 11, 15, (uint32_t)v[3], (uint32_t)(v[3] >> 32));
+    if (u & 16u) XFG_B3_G_PLAIN(0, 5, 10, 15, (uint32_t)v[4], (uint32_t)(v[4] >> 32));
+    if (u & 32u) XFG_B3_G_PLAIN(1, 6, 11, 12, (uint32_t)v[5], (uint32_t)(v[5] >> 32));
+    if (u & 64u) XFG_B3_G_PLAIN(2, 7, 8, 13, (uint32_t)v[6], (uint32_t)(v[6] >> 32));
+    if (u & 128u) XFG_B3_G_PLAIN(3, 4, 9, 14, 0u, 0u);
+    return p;
+}
+// a prefix word into a vector register of the row's own: one move per row and word, where the compiler would
+// keep a second, vector copy of the whole prefix alive across the rows of a thread (16 registers)
+__host__ __device__ __forceinline__ uint32_t b3_prefix_word(uint32_t x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t r;
+    asm volatile("v_mov_b32_e32 %0, %1" : "=v"(r) : "s"(x));
+    return r;
+#else
+    return x;
+#endif
+}
+// the row's digest, equal to b3_hash_elems<7>(e) when p = b3_row7_prefix of the constant elements of e.
+// A uniform column G's four words are copied from the prefix (the final ones where their diagonal G is
+// uniform too, which then does not run); with no uniform G in a half, that half is the code of b3_compress
+#define XFG_B3_ROW7_COL(bit, a, b, c, d, x, y)                                  \
+    do {                                                                        \
+        if (u & (bit)) {                                                        \
+            s[a] = b3_prefix_word(p.s[a]); s[b] = b3_prefix_word(p.s[b]);       \
+            s[c] = b3_prefix_word(p.s[c]); s[d] = b3_prefix_word(p.s[d]);       \
+        } else {                                                                \
+            XFG_B3_G(a, b, c, d, x, y);                                         \
+        }                                                                       \
+    } while (0)
+__host__ __device__ __forceinline__ Digest b3_hash_row7(const B3RowPrefix& p, const uint64_t* e) {
+    constexpr unsigned ZM = 0xC000u;
+    uint32_t m[16];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const uint64_t v = i < 7 ? e[i] : 0;
+        m[2 * i] = (uint32_t)v;
+        m[2 * i + 1] = (uint32_t)(v >> 32);
+    }
+    uint32_t s[16] = XFG_B3_ROW7_INIT;
+    const unsigned u = p.ugs;
+    XFG_B3_ROW7_COL(1u, 0, 4, 8, 12, m[0], m[1]);
+    XFG_B3_ROW7_COL(2u, 1, 5, 9, 13, m[2], m[3]);
+    XFG_B3_ROW7_COL(4u, 2, 6, 10, 14, m[4], m[5]);
+    XFG_B3_ROW7_COL(8u, 3, 7, 11, 15, m[6], m[7]);
+    if (!(u & 16u)) XFG_B3_G(0, 5, 10, 15, m[8], m[9]);
+    if (!(u & 32u)) XFG_B3_G(1, 6, 11, 12, m[10], m[11]);
+    if (!(u & 64u)) XFG_B3_G(2, 7, 8, 13, m[12], m[13]);
+    if (!(u & 128u)) XFG_B3_G(3, 4, 9, 14, 0u, 0u);
+    Digest d;
+    b3_rounds_2_7<ZM>(s, m, d.w);
+    return d;
 }
 
 }  // namespace xfg

@@ -557,7 +557,7 @@ int xfg_debug_constraint_eval(xfg_ctx* c, uint32_t count, uint64_t n, uint32_t b
         HIPCHK(hipMemcpy(L->coeffs.p, coeffs, B * 15 * ext * 8, hipMemcpyHostToDevice));
         launch_trace_lde(L, T, (int)B, sh, false);
         launch_constraint_eval(L->lde.p, L->air.p, L->coeffs.p, ce_div, L->ce.p, sh.logn, sh.logbeta, (int)B, sh.DE, s,
-                               trace_const(L, sh));
+                               trace_const(L, sh), L->ce_uni.p);
         HIPCHK(hipMemcpyAsync(ce, L->ce.p, B * ext * 2 * n * 8, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return XFG_OK;

@@ -62,27 +62,8 @@ void launch_trace_gen(const AirConst* air, u64* trace, int logn, int npoly, hipS
     XFG_CHECK_LAUNCH();
 }
 
-// XfgBurnMintAir::evaluate_transition (reference src/burn_mint_air.rs:335-378) on one row: cur = the
-// row's seven cells, nxt4 = column 4 of the next row (the only neighbour the AIR reads). Shared by
-// the constraint evaluator (rows of the LDE) and the trace check (rows of the trace itself)
-__device__ __forceinline__ void air_transition(const AirConst& A, const u64 (&cur)[7], u64 nxt4, u64 (&r)[7]) {
-    const u64 std_burn = 8000000ULL, large_burn = 8000000000ULL;
-    r[0] = gl_mul(gl_sub(cur[0], std_burn), gl_sub(cur[0], large_burn));
-    r[1] = gl_sub(cur[1], cur[0]);
-    r[2] = gl_sub(cur[2], A.pub[2] & 0xFFFFFFFFULL);
-    r[3] = gl_sub(cur[3], A.pub[3] & 0xFFFFFFFFULL);
-    const u64 d = gl_sub(nxt4, cur[4]);
-    r[4] = gl_mul(d, gl_sub(d, 1));
-    r[5] = gl_sub(cur[5], A.nullifier);
-    r[6] = gl_sub(cur[6], A.commitment);
-}
-// the values asserted at step 0 on columns 0..6 (src/burn_mint_air.rs:380-395); the eighth assertion is
-// column 4 == AIR_LAST_STATE at step n - 1
-__device__ __forceinline__ void air_step0_values(const AirConst& A, u64 (&v0)[7]) {
-    v0[0] = A.pub[0]; v0[1] = A.pub[1]; v0[2] = A.pub[2]; v0[3] = A.pub[3];
-    v0[4] = 0; v0[5] = A.nullifier; v0[6] = A.commitment;
-}
-
+// The AIR itself (the constraints on one row, the step-0 values, which columns a constraint reads and the
+// split of the sums by constant columns) is air.hpp.
 struct CeArgs {
     const u64* lde;
     const AirConst* air;
@@ -91,7 +72,19 @@ struct CeArgs {
     u64* ce;
     int logn, logbeta;
     ColConst cc;  // CC instantiations: the trace's constant columns, whose LDE planes hold nothing
+    const CeUniform* uni;  // CC: [proof] the terms those columns make the same at every point (ce_uniform_kernel)
 };
+// The part of a proof's constraint sums that its constant columns fix (air.hpp ce_uniform_of), one thread per
+// proof, between the coefficient draw on the trace root and the evaluation: the constraints whose columns
+// are all constant, the assertion terms of the constant columns. The evaluation starts its sums from these
+template <int D>
+__global__ __launch_bounds__(64) void ce_uniform_kernel(const AirConst* air, const u64* coeffs, ColConst cc,
+                                                        CeUniform* uni, int npoly) {
+    const int proof = blockIdx.x * blockDim.x + threadIdx.x;
+    if (proof >= npoly) return;
+    const RowConst rc = row_const_lane(cc, (u64)proof);
+    uni[proof] = ce_uniform_of<D>(air[proof], coeffs + (u64)proof * 15 * D, rc.mask, rc.v);
+}
 // One thread per constraint-evaluation point i = 2m + par of the CE domain 7*<w_2n>
 // (ce_to_lde_blowup = beta/2: CE point i is LDE row i*beta/2, i.e. coset t = par*beta/2, row m).
 // Threads walk m fastest inside one parity so the coset-major LDE reads are coalesced.
@@ -100,7 +93,9 @@ struct CeArgs {
 // the evaluations are written as D coordinate planes ce[proof][c][nce].
 // CC: the frame's cells of a constant column (the next row's column 4 among them) are the column's value,
 // read once per block (the block's proof is blockIdx.y) in place of their loads, and those of a shared
-// column come from proof 0's planes (a.lde itself); the AIR stays generic.
+// column come from proof 0's planes (a.lde itself); the AIR stays generic. The sums start from the proof's
+// uniform part (a.uni) and a term in it is neither formed nor added: its mask bit is clear, the same in
+// every lane of the block, so the branches around the terms are scalar.
 template <int D, bool CC>
 __global__ __launch_bounds__(256) void constraint_eval_kernel(CeArgs a) {
     using F = FE<D>;
@@ -131,18 +126,26 @@ __global__ __launch_bounds__(256) void constraint_eval_kernel(CeArgs a) {
     // divisor inverses loaded with the frame (not next to the multiplies that use them)
     const u64 di = par * n + m;
     const u64 dv0 = a.div[di], dv1 = a.div[nce + di], dv2 = a.div[2 * nce + di];
-    u64 r[7];
-    air_transition(A, cur, nxt4, r);
-    F tr = F::zero();
+    F tr, b0, b1;
+    if constexpr (CC) {
+        const CeUniform& U = a.uni[proof];
+        const unsigned tr_live = __builtin_amdgcn_readfirstlane(U.tr_live);
+        const unsigned as_live = __builtin_amdgcn_readfirstlane(U.as_live);
+        ce_live_sums<D>(U, tr_live, as_live, co, A, cur, nxt4, tr, b0, b1);
+    } else {
+        u64 r[7];
+        air_transition(A, cur, nxt4, r);
+        tr = F::zero();
 #pragma unroll
-    for (int c = 0; c < 7; c++) tr = fe_add(tr, fe_mulb(F::load(co + c * D), r[c]));
-    // assertions (src/burn_mint_air.rs:380-395): step 0 on columns 0..6, step n-1 on column 4
-    u64 v0[7];
-    air_step0_values(A, v0);
-    F b0 = F::zero();
+        for (int c = 0; c < 7; c++) tr = fe_add(tr, fe_mulb(F::load(co + c * D), r[c]));
+        // assertions (src/burn_mint_air.rs:380-395): step 0 on columns 0..6, step n-1 on column 4
+        u64 v0[7];
+        air_step0_values(A, v0);
+        b0 = F::zero();
 #pragma unroll
-    for (int c = 0; c < 7; c++) b0 = fe_add(b0, fe_mulb(F::load(co + (7 + c) * D), gl_sub(cur[c], v0[c])));
-    const F b1 = fe_mulb(F::load(co + 14 * D), gl_sub(cur[4], AIR_LAST_STATE));
+        for (int c = 0; c < 7; c++) b0 = fe_add(b0, fe_mulb(F::load(co + (7 + c) * D), gl_sub(cur[c], v0[c])));
+        b1 = fe_mulb(F::load(co + 14 * D), gl_sub(cur[4], AIR_LAST_STATE));
+    }
     F val = fe_mulb(tr, dv0);
     val = fe_add(val, fe_mulb(b0, dv1));
     val = fe_add(val, fe_mulb(b1, dv2));
@@ -150,14 +153,19 @@ __global__ __launch_bounds__(256) void constraint_eval_kernel(CeArgs a) {
     for (int c = 0; c < D; c++) a.ce[((u64)proof * D + c) * nce + i] = val.c(c);
 }
 void launch_constraint_eval(const u64* lde, const AirConst* air, const u64* coeffs, const u64* div, u64* ce, int logn,
-                            int logbeta, int npoly, int ext, hipStream_t s, const ColConst& cc) {
+                            int logbeta, int npoly, int ext, hipStream_t s, const ColConst& cc, CeUniform* uni) {
+    if (cc.flags && !uni) throw std::invalid_argument("constraint evaluation: constant columns need the uniform-part buffer");
     CeArgs a;
     a.lde = lde; a.air = air; a.coeffs = coeffs; a.div = div; a.ce = ce; a.logn = logn; a.logbeta = logbeta;
     a.cc = cc;
+    a.uni = uni;
     u64 nce = 2ULL << logn;
     int threads = nce < 256 ? (int)nce : 256;
     dim3 g((unsigned)(nce / threads), npoly);
     if (cc.flags) {
+        const dim3 gu((unsigned)((npoly + 63) / 64));
+        if (ext == 2) hipLaunchKernelGGL(ce_uniform_kernel<2>, gu, dim3(64), 0, s, air, coeffs, cc, uni, npoly);
+        else hipLaunchKernelGGL(ce_uniform_kernel<1>, gu, dim3(64), 0, s, air, coeffs, cc, uni, npoly);
         if (ext == 2) hipLaunchKernelGGL((constraint_eval_kernel<2, true>), g, dim3(threads), 0, s, a);
         else hipLaunchKernelGGL((constraint_eval_kernel<1, true>), g, dim3(threads), 0, s, a);
     } else {

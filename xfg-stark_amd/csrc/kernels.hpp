@@ -3,18 +3,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "gl.hpp"
+#include "air.hpp"
 #include "blake3.hpp"
 #include "ntt_plan.hpp"
 
 namespace xfg {
-
-// per-proof AIR constants (reference src/burn_mint_air.rs:54-71 order + Keccak constants)
-struct AirConst {
-    u64 pub[12];
-    u64 nullifier;
-    u64 commitment;
-    u64 pad[2];
-};
 
 // per-proof DEEP parameters, every value an element of E (2 coordinates; the second is 0 without
 // a field extension): trace coefficients a_i, composition coefficient, OOD points and the
@@ -222,7 +215,6 @@ void launch_trace_gen(const AirConst* air, u64* trace, int logn, int npoly, hipS
 // (0..6 = columns 0..6 at step 0, 7 = column 4 at step n - 1; step-major order is number order), then
 // the transition constraints by step and number 0..6 (steps 0..n-2). with_air = false: the canonicity
 // test alone. Sets keys with a memset on s first; npoly <= 65535
-constexpr u64 AIR_LAST_STATE = 3;  // the value asserted on column 4 at step n - 1
 constexpr u64 TRACE_KEY_VALID = ~0ULL;
 enum : unsigned { TRACE_KEY_NONCANONICAL = 0, TRACE_KEY_ASSERTION = 1, TRACE_KEY_TRANSITION = 2 };
 __host__ __device__ constexpr u64 trace_key(unsigned kind, u64 step, unsigned index) {
@@ -232,8 +224,11 @@ void launch_trace_check(u64* trace, const AirConst* air, u64* keys, int logn, in
 // composition evaluations over the CE domain 7*<w_2n> (natural order) from the trace LDE
 // div = constraint divisor table [3][2][n] from ce_divisor_table()
 // ext = extension degree D: coeffs [B][15][D], ce planes [B][D][2n]; cc: as for launch_merkle_lde
+// uni [B] (required with cc.flags): the terms of the constraint sums that a proof's constant columns make the
+// same at every point (air.hpp CeUniform), written here by a one-thread-per-proof kernel ahead of the evaluation
 void launch_constraint_eval(const u64* lde, const AirConst* air, const u64* coeffs, const u64* div, u64* ce, int logn,
-                            int logbeta, int npoly, int ext, hipStream_t s, const ColConst& cc = ColConst{});
+                            int logbeta, int npoly, int ext, hipStream_t s, const ColConst& cc = ColConst{},
+                            CeUniform* uni = nullptr);
 
 // ---- OOD / DEEP ----
 // partial: [B][ood_partial_count(logn)][15] per-block sums, kept for launch_deep

@@ -41,6 +41,7 @@ void size_constraint_eval(Lane* c, size_t B, const ProofShape& sh) {
     c->air.ensure(B);
     c->coeffs.ensure(B * 15 * sh.DE);
     c->ce.ensure(B * sh.DE * 2 * sh.n);
+    c->ce_uni.ensure(B);
 }
 void size_ood_deep(Lane* c, size_t B, const ProofShape& sh) {
     c->hcoef.ensure(B * sh.DE * sh.n);
@@ -321,7 +322,8 @@ static ReplayView enqueue_commit_chain(Lane* c, const Tables& T, const u64* ce_d
     launch_merkle_lde(c->lde.p, 7, c->tnodes.p, B, logn, logbeta, s, cs, cc);
     stage_mark(c, 2);
     // ---- 3. constraint evaluation + composition polynomial + commitment
-    launch_constraint_eval(c->lde.p, c->air.p, c->coeffs.p, ce_div, c->ce.p, logn, logbeta, B, DE, s, cc);
+    launch_constraint_eval(c->lde.p, c->air.p, c->coeffs.p, ce_div, c->ce.p, logn, logbeta, B, DE, s, cc,
+                           c->ce_uni.p);
     stage_mark(c, 3);
     launch_interpolate(c->ce.p, 2 * n, c->hcoef.p, n, c->scratch.p, B * DE, logn + 1, true, n, T, s);
     launch_lde(c->hcoef.p, n, c->hlde.p, c->scratch.p, B * DE, logn, logbeta, T, s);

@@ -97,7 +97,15 @@ __device__ __forceinline__ void quad_level(const Digest* src, bool act, int i, i
 struct NoConst {};
 struct RowConstBack : RowConst {
     u64 back;  // words from proof 0's planes to the proof's own: proof * 7 * beta * n
+    // the leaf kernels (a block per proof): what the constant columns fix of round 1 of every leaf's hash
+    // (blake3.hpp b3_row7_prefix), in scalar registers; pre.ugs = 0 (nothing to resume from) elsewhere
+    B3RowPrefix pre;
 };
+// The blowups whose leaf kernels resume their leaves from the prefix: all but 64. There the two-lane kernel
+// goes from 93 to 98 vector registers with it and loses a wave (profiles/r16/kernel_resources.txt), so both
+// kernels of that blowup keep the whole hash; 32 and 128 take three registers more and keep their waves.
+template <int LOGB>
+constexpr bool leaf_prefix_on() { return LOGB != 6; }
 template <bool CC>
 using RowConstOf = std::conditional_t<CC, RowConstBack, NoConst>;
 template <int NC, int LOGB, bool CC>
@@ -124,6 +132,9 @@ __device__ __forceinline__ Digest lde_subtree(const u64* base, u64 n, u64 m, con
     if constexpr (LOG == 0) {
         u64 row[NC];
         lde_row<NC, LOGB, CC>(base, n, m, T0, rc, row);
+        if constexpr (CC && leaf_prefix_on<LOGB>()) {
+            if (rc.pre.ugs) return b3_hash_row7(rc.pre, row);  // wave-uniform; nothing to resume from: the whole hash
+        }
         return b3_hash_elems<NC>(row);
     } else {
         Digest l = lde_subtree<NC, LOGB, LOG - 1, T0, CC>(base, n, m, rc);
@@ -153,12 +164,21 @@ __device__ __forceinline__ Digest lde_subtree_wide(const u64* base, u64 n, u64 m
 
 // the constant columns of a block's proof (a block per proof: flags and values are read once, wave-uniform)
 // back: the words between proof 0's planes and this proof's (RowConstBack)
-template <bool CC>
+// PREFIX: with the uniform part of the leaf hash's round 1, computed here once for the thread's whole subtree
+// on the wave-uniform values (every word made a scalar)
+template <bool CC, bool PREFIX>
 __device__ __forceinline__ RowConstOf<CC> block_row_const(const ColConst& cc, int proof, u64 back) {
     if constexpr (CC) {
         RowConstBack rc;
         static_cast<RowConst&>(rc) = row_const_uniform(cc, (u64)proof);
         rc.back = back;
+        rc.pre.ugs = 0;
+        if constexpr (PREFIX) {
+            rc.pre = b3_row7_prefix(rc.v, rc.mask);
+#pragma unroll
+            for (int w = 0; w < 16; w++) rc.pre.s[w] = (uint32_t)__builtin_amdgcn_readfirstlane((int)rc.pre.s[w]);
+            rc.pre.ugs = (unsigned)__builtin_amdgcn_readfirstlane((int)rc.pre.ugs);
+        }
         return rc;
     } else {
         return NoConst{};
@@ -181,7 +201,7 @@ __global__ __launch_bounds__(256) void leaves_row_kernel(const u64* lde, Digest*
     const u64 m = (u64)blockIdx.x * blockDim.x + threadIdx.x;  // grid covers n exactly
     const u64 back = (u64)proof * NC * (1 << LOGB) * n;
     const u64* base = lde + back;
-    const RowConstOf<CC> rc = block_row_const<CC>(cc, proof, back);
+    const RowConstOf<CC> rc = block_row_const<CC, leaf_prefix_on<LOGB>()>(cc, proof, back);
     Digest d = lde_subtree_wide<NC, LOGB, LOGB, CC>(base, n, m, 0, rc);
     block_tree_up(d, nodes_all + (u64)proof * node_stride, n, lds, blockDim.x / 4);
 }
@@ -203,7 +223,7 @@ __global__ __launch_bounds__(256) void leaves_row2_kernel(const u64* lde, Digest
     const u64 m = (u64)blockIdx.x * RB + rl;
     const u64 back = (u64)proof * NC * (1 << LOGB) * n;
     const u64* base = lde + back + (u64)h * (1 << (LOGB - LOGL)) * n;
-    const RowConstOf<CC> rc = block_row_const<CC>(cc, proof, back);
+    const RowConstOf<CC> rc = block_row_const<CC, leaf_prefix_on<LOGB>()>(cc, proof, back);
     Digest d = lde_subtree_wide<NC, LOGB, LOGB - LOGL, CC>(base, n, m, 0, rc);
 #pragma unroll
     for (int k = 0; k < LOGL; k++) {
@@ -247,6 +267,7 @@ __global__ __launch_bounds__(64) void open_rows_kernel(const u64* lde, const u64
     if constexpr (CC) {
         static_cast<RowConst&>(rc) = row_const_lane(cc, proof);
         rc.back = proof * NC * (1 << LOGB) * n;
+        rc.pre.ugs = 0;
     }
     u64 row[NC];
     lde_row<NC, LOGB, CC>(base, n, m, t, rc, row);

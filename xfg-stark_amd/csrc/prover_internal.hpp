@@ -54,6 +54,7 @@ struct Lane {
     u64 lde_sets = 0, lde_polys = 0;
     bool poison_lde = false;  // xfg_debug_poison_lde: launch_trace_lde sets c->lde to 0xFF bytes first
     DBuf<AirConst> air;
+    DBuf<CeUniform> ce_uni;  // [B] launch_constraint_eval's per-proof uniform part (constant trace columns)
     DBuf<u64> coeffs, trace, coef, scratch, lde, ce, hcoef, hlde, zpts, partial, ood, carry, deep, f0, alpha7,
         rem, dn2, falpha;
     DBuf<Digest> tnodes, hnodes, droots;
@@ -232,7 +233,7 @@ void prove_lane(Lane* c, const Tables& T, const u64* ce_div, ProofJob* jobs, int
 // buffer sizing and launch sets of the proving chain that the debug entry points run too; of the
 // shape they read n, beta and DE only
 void size_trace_lde(Lane* c, size_t B, const ProofShape& sh);        // trace, coef, scratch, lde
-void size_constraint_eval(Lane* c, size_t B, const ProofShape& sh);  // air, coeffs, ce
+void size_constraint_eval(Lane* c, size_t B, const ProofShape& sh);  // air, coeffs, ce, ce_uni
 void size_ood_deep(Lane* c, size_t B, const ProofShape& sh);  // hcoef, zpts, partial, ood, dp, carry, deep
 // trace -> coefficients -> LDE (DefaultTraceLde::new); probe: the xfg_lde_probe events around the LDE.
 // Constant columns, and columns equal to proof 0's, are detected in the trace as it lies in c->trace
