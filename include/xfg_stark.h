@@ -276,6 +276,13 @@ int xfg_debug_lde_skip(xfg_ctx* ctx, const uint64_t* coef, uint32_t npoly, uint6
                        const uint8_t* skip, uint64_t* out);
 int xfg_debug_interpolate_skip(xfg_ctx* ctx, const uint64_t* evals, uint32_t npoly, uint64_t n, int offset7,
                                const uint8_t* skip, uint64_t* out);
+/* the inverse transform as the prover launches it for the composition polynomial and the FRI remainder:
+ * only the first `keep` coefficients of each polynomial are written, `keep` words apart. evals
+ * [npoly][n] -> out [npoly][keep] followed by 8 guard words. The device buffer is set to 0xFF bytes (no
+ * field element) before the launch and npoly * keep + 8 words of it are copied back, so a store past
+ * `keep` shows in the next polynomial's words or in the guard. 1 <= keep <= n, else XFG_INVALID_ARGUMENT */
+int xfg_debug_interpolate_keep(xfg_ctx* ctx, const uint64_t* evals, uint32_t npoly, uint64_t n, uint64_t keep,
+                               int offset7, uint64_t* out);
 /* Goldilocks primitive self test on the device: out[i] = op(a[i], b[i]) with op 0 mul, 1 add,
  * 2 sub, 3 canonical(a), 4 a * 2^(b mod 96), 5 a + (b mod 2^32) * (2^32 - 1), 6 a - b with one
  * borrow fold (the weak subtraction of the NTT butterflies), 7 a + b with one carry fold (the weak

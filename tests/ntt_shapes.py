@@ -26,6 +26,82 @@ INTERPOLATE_2POLY = [(8, False), (64, True), (2048, False), (2048, True), (1 << 
 # one polynomial: test_interpolate_kernel_tile_paths_match_oracle
 INTERPOLATE_1POLY = [(1 << 18, True), (1 << 22, False)]
 
+# The adversarial inputs of tests/ntt_adversarial.py (test_ntt_adversarial_gpu.py): for each of the 48 kernels
+# the smallest (direction, log2 n, log2 blowup, polynomials) of the planner's printed domain that plans it
+# (smallest: fewest output words, then the smaller n), and which of its two passes is there for that reason
+# ("a", "b" or "ab"): that pass gets the first-step boundaries at this shape (B_step where it has more than
+# one step; B_in up to n = 2^20: its targets probe the butterfly network, whose radix-8 and radix-16
+# instances at 2^21 and 2^22 are those of the smaller sizes), both passes get B_out and B_pass.
+# tests/test_ntt_plan.py checks the list against the planner.
+ADVERSARIAL = (
+    [(d, 3, lb, 1, "ab") for d, lb in (("fwd", 1), ("inv", 0))] +
+    [(d, logn, lb, 1, "a" if logn % 2 == 0 else "b") for logn in range(4, 17) for d, lb in (("fwd", 1), ("inv", 0))] +
+    [("fwd", 16, 1, 32, "ab"),   # ntt_pass_a_cos, ntt_pass_b_tq
+     ("fwd", 16, 2, 32, "a"),    # ntt_pass_a_cos2
+     ("fwd", 17, 1, 1, "b"), ("inv", 17, 0, 1, "b"),   # ntt_pass_b<9>
+     ("fwd", 18, 1, 1, "b"),     # ntt_pass_b_pers
+     ("fwd", 18, 1, 8, "b"), ("inv", 18, 0, 1, "b"),   # ntt_pass_b<10>
+     ("fwd", 19, 1, 1, "a"), ("inv", 19, 0, 1, "a"),   # ntt_pass_a<9>
+     ("fwd", 20, 1, 1, "a"), ("inv", 20, 0, 1, "a"),   # ntt_pass_a<10>: 256 threads forward, 512 inverse
+     ("fwd", 20, 3, 1, "ab"),    # ntt_pass_a_r1024, ntt_pass_b_r1024
+     ("fwd", 21, 1, 1, "b"), ("inv", 21, 0, 1, "b"),   # ntt_pass_b<11>: the 1024-thread C = 2048 tiles
+     ("fwd", 22, 1, 1, "b"), ("inv", 22, 0, 1, "b")])  # ntt_pass_b<12>
+# the composed blowups (lde_plan: blowup / 16 blowup-16 transforms of twisted coefficients), (log2 n, log2 blowup):
+# B_out and B_pass only
+ADVERSARIAL_COMPOSED = [(6, 5), (6, 7), (12, 5), (12, 7)]
+
+
+def ntt_split(logn):
+    """(log2 R, log2 C) of n = R C: ntt_split of ntt_plan.hpp, restated"""
+    logc = (10 if logn == 20 else logn // 2 + 1) if logn >= 18 else logn - logn // 2
+    return logn - logc, logc
+
+
+def pass_loge(logn):
+    """log2 elements per thread of pass A and pass B (ntt_plan: radix-32 steps for pass sizes 2^9 and 2^10)"""
+    logr, logc = ntt_split(logn)
+    return (5 if 9 <= logr <= 10 and logc >= 4 else 4), (5 if 9 <= logc <= 10 and logr >= 3 else 4)
+
+
+def step_plan(logs, loge):
+    """(steps, log2 of the first step's radix) of a size-2^logs pass: Plan<LOGS, LOGE> of ntt.hip"""
+    rem = logs % loge
+    return logs // loge + (1 if rem else 0), rem if rem else loge
+
+
+def pass_a_variant(direction, logn, logbeta, npoly):
+    """which forward pass A runs, as far as its arithmetic differs (ntt_plan, with the tables the debug
+    entries build): "cos2" and "r1024" move coset factors between the loads and the twiddles"""
+    logr, logc = ntt_split(logn)
+    if direction != "fwd":
+        return "plain"
+    has_t4 = logn + logbeta <= 22
+    if not has_t4 and logr == 10 and logc == 10:
+        return "r1024"
+    if has_t4 and logr == 8 and logbeta >= 2 and npoly * ((1 << logc) >> min(logc, 4)) >= 512:
+        return "cos2"
+    return "plain"
+
+
+def adversarial_cases():
+    """[(shape, boundary)]: shape an entry of ADVERSARIAL (or ("fwd", logn, logbeta, 1, "") for the composed
+    blowups), boundary one of out, pass, step_a, step_b, in_a, in_b"""
+    cases = []
+    for shape in ADVERSARIAL:
+        _, logn, _, _, subject = shape
+        logr, logc = ntt_split(logn)
+        ea, eb = pass_loge(logn)
+        cases += [(shape, "out"), (shape, "pass")]
+        for which, logs, loge in (("a", logr, ea), ("b", logc, eb)):
+            if which in subject:
+                if step_plan(logs, loge)[0] > 1:
+                    cases.append((shape, "step_" + which))
+                if logn <= 20:
+                    cases.append((shape, "in_" + which))
+    for logn, logbeta in ADVERSARIAL_COMPOSED:
+        cases += [(("fwd", logn, logbeta, 1, ""), "out"), (("fwd", logn, logbeta, 1, ""), "pass")]
+    return cases
+
 
 def launches():
     """(direction, log2 n, log2 blowup, polynomials) of every call above"""

@@ -71,3 +71,55 @@ def test_gpu_parity_shapes_reach_every_kernel(plans):
         assert plans.get(key) is not None, key
         reached |= {p["kernel"] for p in plans[key]}
     assert listed - reached == set()
+
+
+KERNEL = re.compile(r"ntt_pass_([ab])(\w*)(?:<(.*)>)?")
+
+
+def _steps(name):
+    """(pass, Stockham steps) of a kernel the planner names: Plan<LOGS, LOGE> of ntt.hip. The generic kernels
+    carry <LOGS, INV, LOGT, LOGE>; the dedicated ones are 16 x 16 (R or C = 256) or 32 x 32 (1024)"""
+    which, special, args = KERNEL.fullmatch(name).groups()
+    if special:
+        assert special in ("_cos", "_cos2", "_r1024", "_tq", "_pers"), name
+        return which, 2
+    logs, _, _, loge = [a.strip() for a in args.split(",")]
+    return which, -(-int(logs) // int(loge))
+
+
+def test_adversarial_shapes_reach_every_kernel(plans):
+    """the adversarial inputs (tests/ntt_adversarial.py) run on every kernel, and every kernel whose pass has
+    more than one step gets targets at the outputs of its first step (B_step) at a shape that plans it"""
+    listed = {p["kernel"] for ps in plans.values() if ps for p in ps}
+    assert len(listed) == 48
+    cases = ntt_shapes.adversarial_cases()
+    reached, stepped = set(), set()
+    for shape in ntt_shapes.ADVERSARIAL:
+        d, logn, logbeta, npoly, subject = shape
+        assert plans.get((d, logn, logbeta, npoly)) is not None, shape
+        a, b = (p["kernel"] for p in plans[(d, logn, logbeta, npoly)])
+        reached |= {a, b}
+        # the Python restatement of the planner that the generators model the kernels by
+        logr, logc = ntt_shapes.ntt_split(logn)
+        ea, eb = ntt_shapes.pass_loge(logn)
+        variant = {"ntt_pass_a_cos2": "cos2", "ntt_pass_a_r1024": "r1024"}.get(a, "plain")
+        assert ntt_shapes.pass_a_variant(d, logn, logbeta, npoly) == variant, shape
+        for name, which, logs, loge in ((a, "a", logr, ea), (b, "b", logc, eb)):
+            assert _steps(name) == (which, ntt_shapes.step_plan(logs, loge)[0]), (shape, name)
+            if "<" in name and not name.startswith(("ntt_pass_a_cos<", "ntt_pass_b_pers<")):
+                args = name[name.index("<") + 1:-1].split(",")
+                assert (int(args[0]), int(args[-1])) == (logs, loge), (shape, name)
+            if (shape, "step_" + which) in cases:
+                stepped.add(name)
+            assert ((shape, "in_" + which) in cases) == (which in subject and logn <= 20), shape
+        assert (shape, "out") in cases and (shape, "pass") in cases
+    assert listed - reached == set()
+    assert {k for k in listed if _steps(k)[1] > 1} - stepped == set()
+    # every shape is the smallest of the printed domain that plans the kernel it is listed for
+    cost = lambda key: (key[3] << (key[1] + key[2]), key[1], key[2], key[3])
+    smallest = {}
+    for key, ps in plans.items():
+        for p in ps or []:
+            if p["kernel"] not in smallest or cost(key) < cost(smallest[p["kernel"]]):
+                smallest[p["kernel"]] = key
+    assert set(smallest.values()) == {s[:4] for s in ntt_shapes.ADVERSARIAL}

@@ -176,6 +176,35 @@ static int debug_interpolate(xfg_ctx* c, const uint64_t* evals, uint32_t npoly, 
     });
 }
 
+// xfg_debug_interpolate_keep: launch_interpolate as the prover calls it for the composition polynomial
+// and the FRI remainder (keep < n coefficients per polynomial, out_stride = keep)
+static constexpr u64 KEEP_GUARD_WORDS = 8;
+static int debug_interpolate_keep(xfg_ctx* c, const uint64_t* evals, uint32_t npoly, uint64_t n, uint64_t keep,
+                                  int offset7, uint64_t* out) {
+    if (!c || !evals || !out || npoly == 0 || !is_pow2(n) || n < 8 || !ntt_supported((int)ilog2(n), 0, true) ||
+        keep < 1 || keep > n)
+        return XFG_INVALID_ARGUMENT;
+    return on_lane0(c, [&](Lane* L) -> int {
+        const int logn = (int)ilog2(n);
+        ensure_tables(c, std::max(logn, c->tables.LM));
+        // inverse tables up to size n, for n = 8 too: always the table path, which is the prover's
+        ensure_fourstep(c, std::max(logn - 1, 3), 1);
+        Tables T = tables_of(c);
+        const size_t words = (size_t)npoly * keep + KEEP_GUARD_WORDS;
+        L->trace.ensure((size_t)npoly * n);
+        L->coef.ensure((size_t)npoly * n + KEEP_GUARD_WORDS);
+        L->scratch.ensure((size_t)npoly * n);
+        HIPCHK(hipMemcpy(L->trace.p, evals, (size_t)npoly * n * 8, hipMemcpyHostToDevice));
+        // the whole buffer, so that a store anywhere past a polynomial's keep words lands on 0xFF bytes
+        HIPCHK(hipMemsetAsync(L->coef.p, 0xFF, ((size_t)npoly * n + KEEP_GUARD_WORDS) * 8, L->stream));
+        launch_interpolate(L->trace.p, n, L->coef.p, keep, L->scratch.p, npoly, logn, offset7 != 0, keep, T, L->stream,
+                           nullptr);
+        HIPCHK(hipMemcpyAsync(out, L->coef.p, words * 8, hipMemcpyDeviceToHost, L->stream));
+        HIPCHK(hipStreamSynchronize(L->stream));
+        return XFG_OK;
+    });
+}
+
 extern "C" {
 
 int xfg_bench_lde(xfg_ctx* c, uint32_t count, uint64_t n, uint32_t blowup, uint32_t iters, double* avg_ms) {
@@ -251,6 +280,10 @@ int xfg_debug_interpolate_skip(xfg_ctx* c, const uint64_t* evals, uint32_t npoly
                                const uint8_t* skip, uint64_t* out) {
     if (!skip) return XFG_INVALID_ARGUMENT;
     return debug_interpolate(c, evals, npoly, n, offset7, skip, out);
+}
+int xfg_debug_interpolate_keep(xfg_ctx* c, const uint64_t* evals, uint32_t npoly, uint64_t n, uint64_t keep,
+                               int offset7, uint64_t* out) {
+    return debug_interpolate_keep(c, evals, npoly, n, keep, offset7, out);
 }
 
 int xfg_debug_const_columns(xfg_ctx* c, const uint64_t* trace, uint32_t count, uint32_t width, uint64_t n,

@@ -106,6 +106,8 @@ if hasattr(_lib, "xfg_debug_const_columns"):  # absent from builds older than th
     _lib.xfg_debug_const_columns.argtypes = [C.c_void_p, _u64p, C.c_uint32, C.c_uint32, C.c_uint64, _u8p]
     _lib.xfg_debug_lde_skip.argtypes = [C.c_void_p, _u64p, C.c_uint32, C.c_uint64, C.c_uint32, _u8p, _u64p]
     _lib.xfg_debug_interpolate_skip.argtypes = [C.c_void_p, _u64p, C.c_uint32, C.c_uint64, C.c_int, _u8p, _u64p]
+if hasattr(_lib, "xfg_debug_interpolate_keep"):  # absent from builds older than the truncated inverse hook (XFG_LIB A/B)
+    _lib.xfg_debug_interpolate_keep.argtypes = [C.c_void_p, _u64p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, _u64p]
 if hasattr(_lib, "xfg_debug_constraint_eval"):  # absent from builds older than the kernel-level parity hooks
     _lib.xfg_debug_constraint_eval.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _u64p,
                                                C.POINTER(_AirConsts), _u64p, _u64p]
@@ -1159,6 +1161,22 @@ class XfgBurnMintProver:
         if st:
             raise self._err(st)
         return out
+
+    def debug_interpolate_keep(self, evals, n, keep, offset7=False):
+        """the truncated inverse transform of the composition polynomial and the FRI remainder: the first
+        `keep` coefficients of every polynomial, `keep` words apart. -> (coefficients [npoly][keep], the 8
+        guard words behind them, which a correct run leaves at 0xFF..FF)"""
+        import numpy as np
+        e = np.ascontiguousarray(np.asarray(evals, dtype=np.uint64)).reshape(-1, n)
+        keep = int(keep)
+        if not 0 <= keep < 1 << 64:
+            raise XfgStarkError(9, "debug_interpolate_keep: keep is 1..n")
+        out = np.zeros(e.shape[0] * min(keep, n) + 8, dtype=np.uint64)
+        st = _lib.xfg_debug_interpolate_keep(self._ctx, e.ctypes.data_as(_u64p), e.shape[0], n, keep,
+                                             1 if offset7 else 0, out.ctypes.data_as(_u64p))
+        if st:
+            raise self._err(st)
+        return out[:-8].reshape(e.shape[0], keep), out[-8:]
 
     def debug_interpolate_skip(self, evals, n, skip, offset7=False):
         """debug_interpolate with a flag per polynomial (see debug_lde_skip)"""
