@@ -267,6 +267,31 @@ int xfg_debug_const_columns(xfg_ctx* ctx, const uint64_t* trace, uint32_t count,
  * vals_out [count][7] (or NULL): element 0 of every column, the value of a constant one */
 int xfg_debug_col_classes(xfg_ctx* ctx, const uint64_t* trace, uint32_t count, uint64_t n, uint8_t* classes_out,
                           uint64_t* vals_out);
+/* a synthetic row generator for xfg_debug_trace_probe, one pattern per column c. With v = the instance's
+ * pub_inputs[c] and f(row) = 3 row + c (64-bit wrapping), kind[c] is
+ *   0  v in every row (constant per instance)
+ *   1  f(row): every instance the same, not constant
+ *   2  f(row) + v: a function of row and instance
+ *   3  v, but v + 1 at row[c]: constant except at one row
+ *   4  f(row), but f(row) + 1 at row[c] of the instances whose pub_inputs[7] equals `proof` */
+typedef struct xfg_probe_pattern {
+    uint32_t kind[7];
+    uint32_t reserved;
+    uint64_t row[7];
+    uint64_t proof;
+} xfg_probe_pattern;
+/* the front end of a unit of `count` generated traces as the prover's chain runs it, without the
+ * transforms: the trace buffer [count][7][n] is set to 0xFF bytes, the columns are classified from the rows
+ * as the generator returns them (no trace in memory), and the generator then writes the live columns only.
+ * generator 0: the burn AIR's rows from airs [count] (pattern unused, may be NULL); 1: the synthetic
+ * generator of `pattern`. classes_out and vals_out [count][7] as for xfg_debug_col_classes, which they
+ * equal on the same trace materialised; trace_out [count][7][n]: the buffer as left, the planes of
+ * constant (1) and shared (2) columns still 0xFF bytes.
+ * Refused with XFG_INVALID_ARGUMENT: a null pointer, count 0 or count * 7 > 65535, n no power of two in
+ * [8, 2^24], an AIR constant that is not canonical, a generator other than 0 or 1, a kind above 4 */
+int xfg_debug_trace_probe(xfg_ctx* ctx, uint32_t count, uint64_t n, const xfg_air_consts* airs, uint32_t generator,
+                          const xfg_probe_pattern* pattern, uint8_t* classes_out, uint64_t* vals_out,
+                          uint64_t* trace_out);
 /* xfg_debug_lde / xfg_debug_interpolate with a caller-supplied flag vector skip [npoly]: polynomials
  * with a non-zero flag take no transform and are filled in as constants (coefficient / evaluation 0 of
  * the input is the value), as the prover does for the columns it detects. The caller vouches that a
@@ -385,7 +410,8 @@ int xfg_debug_merkle_lde_const(xfg_ctx* ctx, uint32_t count, uint32_t nc, uint64
 /* on != 0: from now on every unit sets its whole trace LDE buffer and its trace coefficient buffer to 0xFF
  * bytes before the transforms. The planes of constant columns, and of columns shared with the unit's first
  * proof, are never written, and without this one that a previous unit left there can hold the right value
- * by accident. Refused while batches are pending */
+ * by accident. A unit whose traces the prover generates also sets its trace buffer to 0xFF bytes before the
+ * generator runs, which writes the live columns only. Refused while batches are pending */
 int xfg_debug_poison_lde(xfg_ctx* ctx, int on);
 /* Merkle commitment of `count` FRI layers (leaf i = the 8 E values at natural indices i + k rows,
  * k < 8, rows = D / 8), vals, the layout arguments and their checks as for xfg_debug_fri_fold; count <= 65535.

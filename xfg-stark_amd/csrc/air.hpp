@@ -62,6 +62,32 @@ __host__ __device__ __forceinline__ void air_step0_values(const AirConst& A, u64
     v0[4] = 0; v0[5] = A.nullifier; v0[6] = A.commitment;
 }
 
+// ---- row generators: (AirConst, logn, row) -> the seven cells of that row of a proof's trace. The kernels that
+// classify the columns of a generated trace and write it (trace_probe_kernel, trace_gen_kernel) are templates
+// over one and learn nothing about its columns but the values it returns.
+// The burn proof's execution trace (src/burn_mint_air.rs:442-476): the step-0 values in every row, and the
+// state column = floor(4 step / n)
+struct BurnRowGen {
+    __host__ __device__ __forceinline__ void operator()(const AirConst& A, int logn, u64 row, u64 (&r)[7]) const {
+        air_step0_values(A, r);
+        r[4] = (4 * row) >> logn;
+    }
+};
+// a synthetic trace for xfg_debug_trace_probe, one pattern per column. v = the proof's pub[c], f(row) = 3 row + c:
+// 0 v, 1 f (every proof the same, not constant), 2 f + v, 3 v but v + 1 at row[c], 4 f but f + 1 at row[c] of the
+// proof whose pub[7] is `proof`
+struct SynthRowGen {
+    u32 kind[7];
+    u64 row[7], proof;
+    __host__ __device__ __forceinline__ void operator()(const AirConst& A, int, u64 i, u64 (&r)[7]) const {
+        for (int c = 0; c < 7; c++) {
+            const u64 v = A.pub[c], f = 3 * i + c, hit = i == row[c] ? 1 : 0;
+            const u32 k = kind[c];
+            r[c] = k == 0 ? v : k == 1 ? f : k == 2 ? f + v : k == 3 ? v + hit : f + (A.pub[7] == proof ? hit : 0);
+        }
+    }
+};
+
 // ---- the constraint sums of a proof with constant trace columns (bit c of const_mask: column c holds one
 // value v[c] in every row, hence at every point of its LDE). Constraint k is the same at every point when
 // every column it reads is constant, and so is the assertion term co[7 + c] (T_c(x) - v0_c) of a constant

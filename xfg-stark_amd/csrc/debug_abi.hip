@@ -324,6 +324,55 @@ int xfg_debug_col_classes(xfg_ctx* c, const uint64_t* trace, uint32_t count, uin
     });
 }
 
+int xfg_debug_trace_probe(xfg_ctx* c, uint32_t count, uint64_t n, const xfg_air_consts* airs, uint32_t generator,
+                          const xfg_probe_pattern* pattern, uint8_t* classes_out, uint64_t* vals_out,
+                          uint64_t* trace_out) {
+    if (!c) return XFG_INVALID_ARGUMENT;
+    c->err.clear();
+    bool ok = airs && classes_out && vals_out && trace_out && count != 0 && (uint64_t)count * 7 <= 0xFFFF &&
+              is_pow2(n) && n >= 8 && n <= (1ULL << 24) && generator <= 1 && (generator == 0 || pattern);
+    for (int k = 0; ok && generator == 1 && k < 7; k++) ok = pattern->kind[k] <= 4;
+    if (!ok) {
+        c->err = "xfg_debug_trace_probe: null or unsupported argument";
+        return XFG_INVALID_ARGUMENT;
+    }
+    return on_lane0(c, [&](Lane* L) -> int {
+        const size_t B = count, cols = B * 7;
+        std::vector<AirConst> ha(B);
+        for (size_t b = 0; b < B; b++) {
+            if (!air_canonical(&airs[b])) {
+                c->err = "AIR constant is not a canonical field element";
+                return XFG_INVALID_ARGUMENT;
+            }
+            ha[b] = air_of(&airs[b]);
+        }
+        SynthRowGen synth = {};
+        if (generator == 1) {
+            for (int k = 0; k < 7; k++) synth.kind[k] = pattern->kind[k], synth.row[k] = pattern->row[k];
+            synth.proof = pattern->proof;
+        }
+        const SynthRowGen* sg = generator == 1 ? &synth : nullptr;
+        const int logn = (int)ilog2(n);
+        L->trace.ensure(cols * n);
+        L->air.ensure(B);
+        L->const_col.ensure(const_flag_bytes(cols));
+        L->const_val.ensure(cols);
+        hipStream_t s = L->stream;
+        HIPCHK(hipMemcpy(L->air.p, ha.data(), B * sizeof(AirConst), hipMemcpyHostToDevice));
+        HIPCHK(hipMemsetAsync(L->trace.p, 0xFF, cols * n * 8, s));
+        HIPCHK(hipMemsetAsync(L->const_val.p, 0xFF, cols * 8, s));
+        // the front end of a generated unit as launch_trace_lde runs it
+        launch_trace_probe(L->air.p, (int)B, logn, L->const_col.p, L->const_val.p, s, sg);
+        launch_trace_gen(L->air.p, L->trace.p, L->const_col.p, logn, (int)B, s, sg);
+        HIPCHK(hipMemcpyAsync(classes_out, L->const_col.p, cols, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(vals_out, L->const_val.p, cols * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(trace_out, L->trace.p, cols * n * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (size_t k = 0; k < cols; k++) classes_out[k] = (uint8_t)col_class(classes_out[k]);
+        return XFG_OK;
+    });
+}
+
 int xfg_debug_field(xfg_ctx* c, uint32_t op, uint64_t count, const uint64_t* a, const uint64_t* b, uint64_t* out) {
     if (!c || !a || !b || !out || op > 12 || count == 0 || (op >= 9 && count % 2)) return XFG_INVALID_ARGUMENT;
     return on_lane0(c, [&](Lane* L) -> int {

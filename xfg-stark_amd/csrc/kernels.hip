@@ -39,26 +39,34 @@ __device__ __forceinline__ u64 tw_ipow(const Tables& T, int k, u64 e) {
 }
 
 // ============================================================================ AIR
-__global__ void trace_gen_kernel(const AirConst* air, u64* trace, int logn) {
+// One thread per row of a proof's trace, rows as Gen (air.hpp) returns them. Only the live columns are
+// stored: the proof's seven classified flags are read once, wave-uniform (the block's proof is blockIdx.y), and
+// the plane of a constant or shared column is left as it was -- its readers take a ColConst, not the plane
+template <class Gen>
+__global__ __launch_bounds__(256) void trace_gen_kernel(Gen gen, const AirConst* air, u64* trace,
+                                                        const unsigned char* flags, int logn) {
     const u64 n = 1ULL << logn;
     const u64 s = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     const int proof = blockIdx.y;
-    if (s >= n) return;
-    const AirConst& A = air[proof];
+    const u64 bytes = row_flag_bytes(flags, (u64)proof * 7);
+    unsigned live = 0;
+#pragma unroll
+    for (int c = 0; c < 7; c++) live |= ((bytes >> (8 * c)) & 0xFF ? 0u : 1u) << c;
+    live = __builtin_amdgcn_readfirstlane(live);
+    if (s >= n || !live) return;
+    u64 r[7];
+    gen(air[proof], logn, s, r);
     u64* tr = trace + (u64)proof * 7 * n;
-    // src/burn_mint_air.rs:442-476, state column = floor(4 step / n)
-    tr[0 * n + s] = A.pub[0];
-    tr[1 * n + s] = A.pub[1];
-    tr[2 * n + s] = A.pub[2];
-    tr[3 * n + s] = A.pub[3];
-    tr[4 * n + s] = (4 * s) >> logn;
-    tr[5 * n + s] = A.nullifier;
-    tr[6 * n + s] = A.commitment;
+#pragma unroll
+    for (int c = 0; c < 7; c++)
+        if ((live >> c) & 1) tr[c * n + s] = r[c];
 }
-void launch_trace_gen(const AirConst* air, u64* trace, int logn, int npoly, hipStream_t s) {
+void launch_trace_gen(const AirConst* air, u64* trace, const unsigned char* flags, int logn, int npoly, hipStream_t s,
+                      const SynthRowGen* synth) {
     u64 n = 1ULL << logn;
     dim3 g((unsigned)((n + 255) / 256), npoly);
-    hipLaunchKernelGGL(trace_gen_kernel, g, dim3(256), 0, s, air, trace, logn);
+    if (synth) hipLaunchKernelGGL(trace_gen_kernel<SynthRowGen>, g, dim3(256), 0, s, *synth, air, trace, flags, logn);
+    else hipLaunchKernelGGL(trace_gen_kernel<BurnRowGen>, g, dim3(256), 0, s, BurnRowGen{}, air, trace, flags, logn);
     XFG_CHECK_LAUNCH();
 }
 

@@ -76,6 +76,11 @@ constexpr size_t const_flag_bytes(size_t ncols) { return 2 * detect_same_off(nco
 __host__ __device__ constexpr int col_class(unsigned char f) { return (f & COL_CONST) ? 1 : ((f & COL_SHARED) ? 2 : 0); }
 void launch_const_detect(const u64* cols, int ncols, int logn, unsigned char* flags, hipStream_t s, int period = 0,
                          u64* vals = nullptr);
+// the same flags and vals for a unit of B generated traces of seven columns (period 7), from the rows as the
+// generator returns them and without a trace in memory: what launch_const_detect finds in the trace that
+// launch_trace_gen would write dense, byte for byte. synth: the synthetic generator (host; debug), else the burn AIR's
+void launch_trace_probe(const AirConst* air, int B, int logn, unsigned char* flags, u64* vals, hipStream_t s,
+                        const SynthRowGen* synth = nullptr);
 // what the NTTs would have produced for the flagged columns, v = src[col * src_stride]:
 // coef[col] = (v, 0, ..., 0) and lde[col][t][m] = v (coset-major planes); coef or lde may be nullptr.
 // Outside the prover's chain (its readers take a ColConst): xfg_debug_lde_skip and xfg_debug_interpolate_skip
@@ -105,15 +110,20 @@ struct RowConst {
         return (shared >> c) & 1 ? first : own;
     }
 };
+// the seven flag bytes of a proof, o = proof * 7, out of two or three aligned 32-bit loads: byte c = flags[o + c]
+__device__ __forceinline__ u64 row_flag_bytes(const unsigned char* flags, u64 o) {
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(flags) + (o >> 2);
+    const unsigned r = (unsigned)(o & 3);
+    u64 bytes = ((u64)w[0] | ((u64)w[1] << 32)) >> (8 * r);  // flags o .. o + 7 - r
+    if (r >= 2) bytes |= (u64)w[2] << (64 - 8 * r);           // o + 8 - r .. (inside the padded allocation)
+    return bytes;
+}
 // for a proof that is the same in every lane (a block per proof): the seven flags come out of two or
 // three aligned 32-bit loads and the values of 64-bit ones at wave-uniform addresses (scalar loads),
 // and mask and values are made wave-uniform for the branches that leave the flagged loads out
 __device__ __forceinline__ RowConst row_const_uniform(const ColConst& cc, u64 proof) {
     const u64 o = proof * 7;
-    const uint32_t* w = reinterpret_cast<const uint32_t*>(cc.flags) + (o >> 2);
-    const unsigned r = (unsigned)(o & 3);
-    u64 bytes = ((u64)w[0] | ((u64)w[1] << 32)) >> (8 * r);  // flags o .. o + 7 - r
-    if (r >= 2) bytes |= (u64)w[2] << (64 - 8 * r);           // o + 8 - r .. (inside the padded allocation)
+    const u64 bytes = row_flag_bytes(cc.flags, o);
     RowConst rc;
     rc.mask = rc.shared = 0;
 #pragma unroll
@@ -207,7 +217,10 @@ void launch_merkle_fri(const u64* vals, u64 val_stride, u64 comp_stride, bool co
                        const CoinStep& cs = CoinStep{});
 
 // ---- AIR ----
-void launch_trace_gen(const AirConst* air, u64* trace, int logn, int npoly, hipStream_t s);
+// the generated traces [npoly][7][n], live columns only: flags [npoly * 7] are the classified bytes
+// (launch_trace_probe), and the plane of a column flagged COL_CONST or COL_SHARED is not written
+void launch_trace_gen(const AirConst* air, u64* trace, const unsigned char* flags, int logn, int npoly, hipStream_t s,
+                      const SynthRowGen* synth = nullptr);
 // Trace::validate on the device (trace_check_kernel): keys[proof] = the smallest key of what the trace
 // [npoly][7][n] violates, TRACE_KEY_VALID (all ones) when nothing. A key is kind << 62 | step << 3 | index,
 // so that their order is the order of the report: a cell >= p first (index = column; such a cell is also

@@ -167,17 +167,25 @@ ColConst trace_const(const Lane* c, const ProofShape& sh) {
     return cc;
 }
 
-void launch_trace_lde(Lane* c, const Tables& T, int B, const ProofShape& sh, bool probe) {
+void launch_trace_lde(Lane* c, const Tables& T, int B, const ProofShape& sh, bool probe, bool generated) {
     hipStream_t s = c->stream;
     const unsigned char* skip = c->const_col.p;
     // xfg_debug_poison_lde: nothing an earlier unit left in the buffers can pass for a plane of this one
-    // (the LDE planes and the coefficients of constant and shared columns are never written)
+    // (the LDE planes and the coefficients of constant and shared columns are never written, nor are
+    // their planes of a generated trace: that one is poisoned here, ahead of its generator)
     if (c->poison_lde) {
         HIPCHK(hipMemsetAsync(c->lde.p, 0xFF, (size_t)B * 7 * sh.N * 8, s));
         HIPCHK(hipMemsetAsync(c->coef.p, 0xFF, (size_t)B * 7 * sh.n * 8, s));
+        if (generated) HIPCHK(hipMemsetAsync(c->trace.p, 0xFF, (size_t)B * 7 * sh.n * 8, s));
     }
-    // constant columns, and the columns of proofs 1 .. B - 1 that equal proof 0's: one pass over the trace
-    launch_const_detect(c->trace.p, B * 7, sh.logn, c->const_col.p, s, 7, c->const_val.p);
+    // constant columns, and the columns of proofs 1 .. B - 1 that equal proof 0's
+    if (generated) {
+        // found in the rows as they are generated; then the live columns alone go to c->trace
+        launch_trace_probe(c->air.p, B, sh.logn, c->const_col.p, c->const_val.p, s);
+        launch_trace_gen(c->air.p, c->trace.p, c->const_col.p, sh.logn, B, s);
+    } else {  // one pass over the trace
+        launch_const_detect(c->trace.p, B * 7, sh.logn, c->const_col.p, s, 7, c->const_val.p);
+    }
     launch_interpolate(c->trace.p, sh.n, c->coef.p, sh.n, c->scratch.p, B * 7, sh.logn, false, sh.n, T, s, skip);
     if (probe) {
         if (!c->lde_ev[0]) {
@@ -286,7 +294,7 @@ static ReplayView enqueue_commit_chain(Lane* c, const Tables& T, const u64* ce_d
     stage_mark(c, 0);
     const size_t tbytes = (size_t)7 * n * 8;  // one proof's trace
     switch (ts.kind) {
-        case TraceSrc::GENERATED: launch_trace_gen(c->air.p, c->trace.p, logn, B, s); break;
+        case TraceSrc::GENERATED: break;  // launch_trace_lde: classified from the generator, live columns written
         case TraceSrc::HOST_DIRECT:  // xfg_prove_trace: one trace, straight from the caller's memory
             HIPCHK(hipMemcpyAsync(c->trace.p, ts.p, B * tbytes, hipMemcpyHostToDevice, s));
             break;
@@ -308,7 +316,7 @@ static ReplayView enqueue_commit_chain(Lane* c, const Tables& T, const u64* ce_d
             break;
     }
     if (ts.checks()) launch_trace_check(c->trace.p, c->air.p, c->tkeys.p, logn, B, ts.validate, s);
-    launch_trace_lde(c, T, B, sh, c->lde_probe);
+    launch_trace_lde(c, T, B, sh, c->lde_probe, ts.kind == TraceSrc::GENERATED);
     stage_mark(c, 1);
     // ---- 2. trace root -> constraint composition coefficients (7 transition + 8 boundary)
     CoinStep cs;

@@ -979,7 +979,8 @@ static void ntt_run(NttArgs& a, int npoly, bool inv, hipStream_t s) {
 
 // ---------------------------------------------------------------- constant columns
 // A column that holds one value v in every row interpolates to the constant v, and its LDE is v at
-// every point: such columns take no NTT. const_detect_kernel finds them in whatever trace arrives,
+// every point: such columns take no NTT. const_detect_kernel finds them in whatever trace arrives
+// (trace_probe_kernel: in the rows of a trace the prover generates itself, as they are generated),
 // the NTT kernels return at once for them (NttArgs::skip). Their coefficient and LDE planes stay
 // unwritten in the prover: every reader of either takes the value from a ColConst (kernels.hpp);
 // const_fill_kernel serves xfg_debug_lde_skip and xfg_debug_interpolate_skip alone.
@@ -1050,6 +1051,54 @@ void launch_const_detect(const u64* cols, int ncols, int logn, unsigned char* fl
     } else {
         hipLaunchKernelGGL(const_detect_kernel<false>, g, b, 0, s, cols, n, flags, period, vals);
     }
+}
+// The detection for a unit of generated traces, on the rows as Gen (air.hpp) returns them: the trace is
+// not in memory, and the kernel's only loads are the AirConsts. The geometry is const_detect_kernel's with
+// the seven columns of a proof in one block: block (x, b) generates its CONST_DETECT_SPAN rows of proof b,
+// row 0 of proof b and (period: more than one proof, b > 0) the same rows of proof 0, and ORs the
+// differences per column; the two bytes per column, their presets, the stores of 0 and vals are as above.
+// What it says about a column is what the values say, never which generator ran
+template <class Gen>
+__global__ __launch_bounds__(256) void trace_probe_kernel(Gen gen, const AirConst* air, int logn, unsigned char* flags,
+                                                          int period, u64* vals) {
+    const int b = blockIdx.y;
+    const u64 n = 1ULL << logn;
+    const AirConst& A = air[b];
+    const u64 i0 = (u64)blockIdx.x * CONST_DETECT_SPAN, i1 = i0 + CONST_DETECT_SPAN < n ? i0 + CONST_DETECT_SPAN : n;
+    u64 first[7], diff[7] = {}, diff0[7] = {};
+    gen(A, logn, 0, first);
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (int c = 0; c < 7; c++) vals[b * 7 + c] = first[c];
+    const bool share = period && b > 0;  // block-uniform
+    for (u64 i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
+        u64 x[7];
+        gen(A, logn, i, x);
+#pragma unroll
+        for (int c = 0; c < 7; c++) diff[c] |= x[c] ^ first[c];
+        if (share) {
+            u64 y[7];
+            gen(air[0], logn, i, y);
+#pragma unroll
+            for (int c = 0; c < 7; c++) diff0[c] |= x[c] ^ y[c];
+        }
+    }
+    unsigned char* same = flags + detect_same_off((size_t)gridDim.y * 7);
+#pragma unroll
+    for (int c = 0; c < 7; c++) {
+        if (diff[c]) flags[b * 7 + c] = 0;
+        if (share && diff0[c]) same[b * 7 + c] = 0;
+    }
+}
+void launch_trace_probe(const AirConst* air, int B, int logn, unsigned char* flags, u64* vals, hipStream_t s,
+                        const SynthRowGen* synth) {
+    const u64 n = 1ULL << logn;
+    const int ncols = B * 7, period = B > 1 ? 7 : 0;  // one trace: nothing to share, no class kernel (launch_const_detect)
+    const dim3 gi((unsigned)((ncols + 255) / 256)), bi(256);
+    hipLaunchKernelGGL(const_flags_init_kernel, gi, bi, 0, s, flags, ncols, period);
+    const dim3 g((unsigned)((n + CONST_DETECT_SPAN - 1) / CONST_DETECT_SPAN), B), b((unsigned)std::min<u64>(256, n));
+    if (synth) hipLaunchKernelGGL(trace_probe_kernel<SynthRowGen>, g, b, 0, s, *synth, air, logn, flags, period, vals);
+    else hipLaunchKernelGGL(trace_probe_kernel<BurnRowGen>, g, b, 0, s, BurnRowGen{}, air, logn, flags, period, vals);
+    if (period) hipLaunchKernelGGL(const_class_kernel, gi, bi, 0, s, flags, ncols);
 }
 // outputs of the flagged columns, v = src[col * src_stride]: coef[col] = (v, 0, ..., 0) (n entries) and
 // lde[col][t][m] = v (N = beta n entries, the coset-major plane is simply full of v); either may be null.

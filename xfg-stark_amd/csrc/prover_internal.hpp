@@ -52,7 +52,8 @@ struct Lane {
     hipEvent_t lde_ev[2] = {};
     double lde_ms = 0;
     u64 lde_sets = 0, lde_polys = 0;
-    bool poison_lde = false;  // xfg_debug_poison_lde: launch_trace_lde sets c->lde to 0xFF bytes first
+    // xfg_debug_poison_lde: launch_trace_lde sets c->lde, c->coef and a generated unit's c->trace to 0xFF bytes first
+    bool poison_lde = false;
     DBuf<AirConst> air;
     DBuf<CeUniform> ce_uni;  // [B] launch_constraint_eval's per-proof uniform part (constant trace columns)
     DBuf<u64> coeffs, trace, coef, scratch, lde, ce, hcoef, hlde, zpts, partial, ood, carry, deep, f0, alpha7,
@@ -236,11 +237,14 @@ void size_trace_lde(Lane* c, size_t B, const ProofShape& sh);        // trace, c
 void size_constraint_eval(Lane* c, size_t B, const ProofShape& sh);  // air, coeffs, ce, ce_uni
 void size_ood_deep(Lane* c, size_t B, const ProofShape& sh);  // hcoef, zpts, partial, ood, dp, carry, deep
 // trace -> coefficients -> LDE (DefaultTraceLde::new); probe: the xfg_lde_probe events around the LDE.
-// Constant columns, and columns equal to proof 0's, are detected in the trace as it lies in c->trace
-// (whatever put it there) and not transformed: the flags stay in c->const_col, the values in
-// c->const_val, and their planes of c->coef and c->lde are left unwritten. Whatever reads either
-// afterwards takes trace_const along
-void launch_trace_lde(Lane* c, const Tables& T, int B, const ProofShape& sh, bool probe);
+// Constant columns, and columns equal to proof 0's, are detected from the values and not transformed: the
+// flags stay in c->const_col, the values in c->const_val, and their planes of c->coef and c->lde are left
+// unwritten. Whatever reads either afterwards takes trace_const along.
+// generated = false: the trace lies in c->trace (whatever put it there) and is read there, one pass
+// (launch_const_detect). generated = true: the unit's traces are those of the burn row generator on c->air
+// and are classified as it produces them (launch_trace_probe); then launch_trace_gen writes the live
+// columns alone to c->trace, so the trace planes of constant and shared columns hold nothing either
+void launch_trace_lde(Lane* c, const Tables& T, int B, const ProofShape& sh, bool probe, bool generated = false);
 ColConst trace_const(const Lane* c, const ProofShape& sh);
 // the proof-of-work search on the device for the B seeds the caller wrote to grind_seeds(c, B): launched on
 // the lane's gather stream (idle between a unit's chain and its gathers) and waited for. Returns the B

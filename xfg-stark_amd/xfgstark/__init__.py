@@ -132,6 +132,13 @@ if hasattr(_lib, "xfg_debug_col_classes"):  # absent from builds without shared 
     _lib.xfg_debug_ood_deep_const.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, _u64p, _u8p, _u64p, _u64p,
                                               _u64p, _u64p, C.POINTER(C.c_uint32), _u64p, C.c_uint64, _u64p, _u64p,
                                               _u64p, C.POINTER(C.c_uint32), _u64p, C.POINTER(C.c_int)]
+class _ProbePattern(C.Structure):
+    _fields_ = [("kind", C.c_uint32 * 7), ("reserved", C.c_uint32), ("row", C.c_uint64 * 7), ("proof", C.c_uint64)]
+
+
+if hasattr(_lib, "xfg_debug_trace_probe"):  # absent from builds that detect in the written trace (XFG_LIB A/B)
+    _lib.xfg_debug_trace_probe.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(_AirConsts), C.c_uint32,
+                                           C.POINTER(_ProbePattern), _u8p, _u64p, _u64p]
 if hasattr(_lib, "xfg_debug_fri_fold_f"):  # absent from builds older than folding factors 2, 4 and 16
     _lib.xfg_debug_fri_fold_f.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                           C.c_uint32, _u64p, _u64p, _u64p]
@@ -904,6 +911,28 @@ class XfgBurnMintProver:
         if st:
             raise self._err(st)
         return (out, vals) if values else out
+
+    def debug_trace_probe(self, airs, n, generator=0, pattern=None):
+        """the front end of a unit of generated traces (xfg_debug_trace_probe): airs = B air_consts() tuples;
+        generator 0 the burn AIR's rows, 1 the synthetic rows of pattern = (kind[7], row[7], proof) ->
+        (classes [B,7], values [B,7], trace buffer [B,7,n] as left: unwritten planes are 0xFF bytes)"""
+        import numpy as np
+        B = len(airs)
+        arr = (_AirConsts * B)(*[_air_struct(a) for a in airs])
+        pat = _ProbePattern()
+        if pattern is not None:
+            kind, row, proof = pattern
+            pat.kind = (C.c_uint32 * 7)(*kind)
+            pat.row = (C.c_uint64 * 7)(*row)
+            pat.proof = proof
+        cls = np.zeros((B, 7), dtype=np.uint8)
+        vals = np.zeros((B, 7), dtype=np.uint64)
+        tr = np.zeros((B, 7, n), dtype=np.uint64)
+        st = _lib.xfg_debug_trace_probe(self._ctx, B, n, arr, generator, C.byref(pat) if pattern is not None else None,
+                                        cls.ctypes.data_as(_u8p), vals.ctypes.data_as(_u64p), tr.ctypes.data_as(_u64p))
+        if st:
+            raise self._err(st)
+        return cls, vals, tr
 
     def debug_ood_deep_const(self, coef, flags, vals, hcoef, zpts, coeffs):
         """debug_ood_deep_e without coins on coefficients behind a column descriptor (xfg_debug_ood_deep_const):
