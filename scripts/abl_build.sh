@@ -5,7 +5,7 @@
 # skeleton and its arithmetic. Output is wrong by construction: timing only.
 set -e
 cd "$(dirname "$0")/.."
-make -s -C xfg-stark_amd build/kernels.hip.o build/merkle.hip.o build/grind.hip.o build/tables.hip.o build/lane_unit.hip.o build/prover.hip.o build/debug_abi.hip.o build/verify_batch_gpu.hip.o build/verify_kernels.hip.o build/verifier.cpp.o
+make -s -C xfg-stark_amd build/kernels.hip.o build/merkle.hip.o build/grind.hip.o build/columns.hip.o build/tables.hip.o build/lane_unit.hip.o build/prover.hip.o build/debug_abi.hip.o build/verify_batch_gpu.hip.o build/verify_kernels.hip.o build/verifier.cpp.o
 for v in nomath nostore; do
   sed -e 's/^\(\s*\)dft_reg<LOGR, INV>(v\[q\]);/\1ABL_M(dft_reg<LOGR, INV>(v[q]));/' \
       -e 's/for (int r = 1; r < R; r++) v\[q\]\[r\] = gl_mul(v\[q\]\[r\], TW2D/for (int r = 1; r < R \&\& ABL_MATH == 0; r++) v[q][r] = gl_mul(v[q][r], TW2D/' \
@@ -17,6 +17,6 @@ for v in nomath nostore; do
   sed -i "1i #define ABL_MATH $M\n#define ABL_STORE $S\n#define ABL_M(...) do { if (!ABL_MATH) { __VA_ARGS__; } } while (0)" ab/ntt_$v.hip
   grep -c "ABL_" ab/ntt_$v.hip
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -I xfg-stark_amd/csrc -c ab/ntt_$v.hip -o ab/ntt_$v.o
-  /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ab/lib_$v.so xfg-stark_amd/build/kernels.hip.o xfg-stark_amd/build/merkle.hip.o ab/ntt_$v.o xfg-stark_amd/build/grind.hip.o xfg-stark_amd/build/tables.hip.o xfg-stark_amd/build/lane_unit.hip.o xfg-stark_amd/build/prover.hip.o xfg-stark_amd/build/debug_abi.hip.o xfg-stark_amd/build/verify_batch_gpu.hip.o xfg-stark_amd/build/verify_kernels.hip.o xfg-stark_amd/build/verifier.cpp.o
+  /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ab/lib_$v.so xfg-stark_amd/build/kernels.hip.o xfg-stark_amd/build/merkle.hip.o ab/ntt_$v.o xfg-stark_amd/build/grind.hip.o xfg-stark_amd/build/columns.hip.o xfg-stark_amd/build/tables.hip.o xfg-stark_amd/build/lane_unit.hip.o xfg-stark_amd/build/prover.hip.o xfg-stark_amd/build/debug_abi.hip.o xfg-stark_amd/build/verify_batch_gpu.hip.o xfg-stark_amd/build/verify_kernels.hip.o xfg-stark_amd/build/verifier.cpp.o
 done
 ls -la ab/*.so

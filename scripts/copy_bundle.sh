@@ -22,8 +22,8 @@ cp $G/valu/valu_per_proof.json $P/valu_per_proof.json
 cp $G/single_summary.txt $P/single_proof.txt
 cp $G/single/single_kernel_stats.csv $P/single_kernel_stats.csv
 T=$(mktemp -d /tmp/xfg_isa.XXXX)
-for f in ntt kernels prover; do
+for f in ntt columns kernels prover; do
   /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only -S -o $T/$f.s xfg-stark_amd/csrc/$f.hip
 done
-python3 scripts/valu_ceiling.py $T/ntt.s $T/kernels.s $T/prover.s --ledger $P/valu_per_proof.json
+python3 scripts/valu_ceiling.py $T/ntt.s $T/columns.s $T/kernels.s $T/prover.s --ledger $P/valu_per_proof.json
 rm -rf $T

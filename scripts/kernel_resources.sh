@@ -1,6 +1,6 @@
 #!/bin/bash
 # CPU container: VGPR / SGPR / spill / scratch of the kernels whose demangled name matches PATTERN, from the
-# .amdhsa metadata of the device assembly of the given csrc units (default: kernels merkle ntt).
+# .amdhsa metadata of the device assembly of the given csrc units (default: kernels merkle ntt, and columns where the tree has it).
 #   scripts/kernel_resources.sh PATTERN [SRCROOT] [unit ...]
 # SRCROOT: a tree holding xfg-stark_amd/csrc (default: this one; a `git archive` of another revision for
 # the parent's side of a comparison, as profiles/r15/kernel_resources.txt)
@@ -9,7 +9,7 @@ PAT=${1:?pattern}
 ROOT=${2:-$(cd "$(dirname "$0")/.." && pwd)}
 shift || true
 shift || true
-UNITS=${*:-kernels merkle ntt}
+UNITS=${*:-kernels merkle ntt $([ -f "$ROOT/xfg-stark_amd/csrc/columns.hip" ] && echo columns)}
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 TMP=$(mktemp -d /tmp/xfg_res.XXXX)
 for u in $UNITS; do

@@ -13,5 +13,5 @@ for B in 1 3; do
 done
 python3 scripts/valu_ledger.py $OUT
 # the mix ceiling needs the ISA listings (CPU side, after copying the ledger into profiles/rNN/):
-#   hipcc -O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only -S -o X.s xfg-stark_amd/csrc/{ntt,kernels,prover}.hip
-#   python3 scripts/valu_ceiling.py ntt.s kernels.s prover.s --ledger profiles/rNN/valu_per_proof.json
+#   hipcc -O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only -S -o X.s xfg-stark_amd/csrc/{ntt,columns,kernels,prover}.hip
+#   python3 scripts/valu_ceiling.py ntt.s columns.s kernels.s prover.s --ledger profiles/rNN/valu_per_proof.json

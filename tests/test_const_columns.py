@@ -17,7 +17,7 @@ import plain_ref as R
 
 pytestmark = pytest.mark.gpu
 P = R.P
-DETECT_SPAN = 1024  # rows per detection block (CONST_DETECT_SPAN, csrc/kernels.hpp)
+DETECT_SPAN = 1024  # rows per detection block (CONST_DETECT_SPAN, csrc/columns.hpp)
 
 
 @pytest.fixture(scope="module")

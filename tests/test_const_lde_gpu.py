@@ -1,4 +1,4 @@
-"""GPU: the consumers of a trace LDE whose constant columns have no plane (csrc/kernels.hpp ColConst).
+"""GPU: the consumers of a trace LDE whose constant columns have no plane (csrc/columns.hpp ColConst).
 
 The prover no longer writes the LDE plane of a column it found constant: the leaf kernels, the opening
 kernel and the constraint evaluation take such a column's value from a descriptor. Kernel level:

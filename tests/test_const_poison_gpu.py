@@ -3,7 +3,7 @@ unit (xfg_debug_poison_lde), byte for byte against the CPU oracle.
 
 The LDE planes of constant columns are never written: the leaf kernels, the constraint evaluation, the
 opening kernel and the gather of the opened trace values each take such a column's value from the
-flags and coefficient 0 (csrc/kernels.hpp ColConst). Without the poison a plane that an earlier unit
+flags and coefficient 0 (csrc/columns.hpp ColConst). Without the poison a plane that an earlier unit
 left in the lane's buffer can hold the right value, and a reader that still goes to memory would pass.
 The trace kinds are those of tests/test_const_columns.py; this is the test that sees the gather."""
 import numpy as np

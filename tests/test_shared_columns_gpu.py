@@ -1,7 +1,7 @@
 """GPU: trace columns that a unit's proofs share with its first proof.
 
 A column of proof b > 0 that equals the same column of proof 0 element for element is not transformed: its
-coefficient and LDE planes are never written and every reader goes to proof 0's (csrc/kernels.hpp ColConst,
+coefficient and LDE planes are never written and every reader goes to proof 0's (csrc/columns.hpp ColConst,
 COL_SHARED). Constant columns keep their own class, and OOD and DEEP take both through the descriptor.
 
 Three layers:
@@ -24,7 +24,7 @@ from test_const_columns import _air_of, _trace
 
 pytestmark = pytest.mark.gpu
 P = R.P
-DETECT_SPAN = 1024  # rows per detection block (CONST_DETECT_SPAN, csrc/kernels.hpp)
+DETECT_SPAN = 1024  # rows per detection block (CONST_DETECT_SPAN, csrc/columns.hpp)
 
 
 @pytest.fixture(scope="module")

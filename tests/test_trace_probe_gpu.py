@@ -1,5 +1,5 @@
 """GPU: the columns of a generated trace are classified from the rows as the generator returns them, and
-only the live ones are written (csrc/ntt.hip trace_probe_kernel, csrc/kernels.hip trace_gen_kernel).
+only the live ones are written (csrc/columns.hip trace_probe_kernel, trace_gen_kernel).
 
 Through xfg_debug_trace_probe, which runs the front end of a generated unit as the chain does on a trace
 buffer of 0xFF bytes:
@@ -20,7 +20,7 @@ import oracle_lib as O
 import synthetic
 
 gpu = pytest.mark.gpu  # test_pattern_expectations alone needs no GPU
-DETECT_SPAN = 1024  # rows per detection block (CONST_DETECT_SPAN, csrc/kernels.hpp)
+DETECT_SPAN = 1024  # rows per detection block (CONST_DETECT_SPAN, csrc/columns.hpp)
 POISON = np.uint64(0xFFFFFFFFFFFFFFFF)
 CONST, ROWS, ROWS_PROOF, CONST_BUT, SHARED_BUT = range(5)  # xfg_probe_pattern kinds
 

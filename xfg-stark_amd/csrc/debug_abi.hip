@@ -363,7 +363,7 @@ int xfg_debug_trace_probe(xfg_ctx* c, uint32_t count, uint64_t n, const xfg_air_
         HIPCHK(hipMemsetAsync(L->const_val.p, 0xFF, cols * 8, s));
         // the front end of a generated unit as launch_trace_lde runs it
         launch_trace_probe(L->air.p, (int)B, logn, L->const_col.p, L->const_val.p, s, sg);
-        launch_trace_gen(L->air.p, L->trace.p, L->const_col.p, logn, (int)B, s, sg);
+        launch_trace_gen(L->air.p, (int)B, logn, L->const_col.p, L->trace.p, s, sg);
         HIPCHK(hipMemcpyAsync(classes_out, L->const_col.p, cols, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(vals_out, L->const_val.p, cols * 8, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(trace_out, L->trace.p, cols * n * 8, hipMemcpyDeviceToHost, s));

@@ -10,6 +10,7 @@ namespace xfg {
 
 typedef uint64_t u64;
 typedef uint32_t u32;
+typedef u64 u64x2 __attribute__((ext_vector_type(2)));  // one 16-byte store
 
 constexpr u64 P = 0xFFFFFFFF00000001ULL;
 constexpr u64 EPS = 0xFFFFFFFFULL;  // 2^64 mod p

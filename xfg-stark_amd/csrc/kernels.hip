@@ -21,57 +21,14 @@ namespace xfg {
 
 #define XFG_CHECK_LAUNCH() (void)hipGetLastError()
 
-__device__ __forceinline__ unsigned brev(unsigned x, int bits) { return __brev(x) >> (32 - bits); }
-
 __device__ __forceinline__ u64 shfl_xor_u64(u64 v, int m, int w) {
     u32 lo = __shfl_xor((u32)v, m, w), hi = __shfl_xor((u32)(v >> 32), m, w);
     return (u64)lo | ((u64)hi << 32);
 }
 
-// w_{2^k}^e from the master table (forward) / its inverse
-__device__ __forceinline__ u64 tw_pow(const Tables& T, int k, u64 e) {
-    u64 M = 1ULL << T.LM;
-    return T.tw[(e << (T.LM - k)) & (M - 1)];
-}
-__device__ __forceinline__ u64 tw_ipow(const Tables& T, int k, u64 e) {
-    u64 M = 1ULL << T.LM;
-    return T.tw[(M - ((e << (T.LM - k)) & (M - 1))) & (M - 1)];
-}
-
 // ============================================================================ AIR
-// One thread per row of a proof's trace, rows as Gen (air.hpp) returns them. Only the live columns are
-// stored: the proof's seven classified flags are read once, wave-uniform (the block's proof is blockIdx.y), and
-// the plane of a constant or shared column is left as it was -- its readers take a ColConst, not the plane
-template <class Gen>
-__global__ __launch_bounds__(256) void trace_gen_kernel(Gen gen, const AirConst* air, u64* trace,
-                                                        const unsigned char* flags, int logn) {
-    const u64 n = 1ULL << logn;
-    const u64 s = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    const int proof = blockIdx.y;
-    const u64 bytes = row_flag_bytes(flags, (u64)proof * 7);
-    unsigned live = 0;
-#pragma unroll
-    for (int c = 0; c < 7; c++) live |= ((bytes >> (8 * c)) & 0xFF ? 0u : 1u) << c;
-    live = __builtin_amdgcn_readfirstlane(live);
-    if (s >= n || !live) return;
-    u64 r[7];
-    gen(air[proof], logn, s, r);
-    u64* tr = trace + (u64)proof * 7 * n;
-#pragma unroll
-    for (int c = 0; c < 7; c++)
-        if ((live >> c) & 1) tr[c * n + s] = r[c];
-}
-void launch_trace_gen(const AirConst* air, u64* trace, const unsigned char* flags, int logn, int npoly, hipStream_t s,
-                      const SynthRowGen* synth) {
-    u64 n = 1ULL << logn;
-    dim3 g((unsigned)((n + 255) / 256), npoly);
-    if (synth) hipLaunchKernelGGL(trace_gen_kernel<SynthRowGen>, g, dim3(256), 0, s, *synth, air, trace, flags, logn);
-    else hipLaunchKernelGGL(trace_gen_kernel<BurnRowGen>, g, dim3(256), 0, s, BurnRowGen{}, air, trace, flags, logn);
-    XFG_CHECK_LAUNCH();
-}
-
 // The AIR itself (the constraints on one row, the step-0 values, which columns a constraint reads and the
-// split of the sums by constant columns) is air.hpp.
+// split of the sums by constant columns) is air.hpp; writing a generated trace is columns.hip.
 struct CeArgs {
     const u64* lde;
     const AirConst* air;
@@ -717,7 +674,7 @@ __global__ __launch_bounds__(256) void fri_fold_kernel(FoldArgs a) {
         }
     }
     // y = alpha * 7^-1 * w_D^-i ; Horner
-    const F y = fe_mulb(F::load(a.alpha7 + (u64)proof * D), tw_ipow(a.T, a.logD, i));
+    const F y = fe_mulb(F::load(a.alpha7 + (u64)proof * D), tw_get(a.T, a.logD, i, true));
     F r = v[NF - 1];
 #pragma unroll
     for (int j = NF - 2; j >= 0; j--) r = fe_add(fe_mul(r, y), v[j]);

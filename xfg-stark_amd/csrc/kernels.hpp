@@ -6,6 +6,7 @@
 #include "air.hpp"
 #include "blake3.hpp"
 #include "ntt_plan.hpp"
+#include "columns.hpp"
 
 namespace xfg {
 
@@ -20,7 +21,7 @@ struct DeepParams {
     u64 pad[2];
 };
 
-// precomputed four-step twiddles (ntt.hip build_fourstep): fwd[logn][logbeta] holds
+// precomputed four-step twiddles (tables.hip build_fourstep): fwd[logn][logbeta] holds
 // 7^j2 w_N^(j2 (t + beta k1)) at [t][k1][j2], inv[logn] holds w_n^-(j2 k1) / n at [k1][j2];
 // nullptr -> the kernels form them as running products. Which of the two a forward size gets:
 // table_kind (ntt_plan.hpp).
@@ -41,6 +42,11 @@ struct Tables {
     const u64* ipow7;  // 7^-j, j < 2^LM
     const FourStep* fs;  // host-side table registry (never dereferenced on the device)
 };
+// w_{2^k}^e from the master table, or its inverse
+__device__ __forceinline__ u64 tw_get(const Tables& T, int k, u64 e, bool inv) {
+    const u64 M = 1ULL << T.LM, idx = (e << (T.LM - k)) & (M - 1);
+    return T.tw[inv ? (M - idx) & (M - 1) : idx];
+}
 
 // ---- NTT (four-step, natural order in/out) ----
 // forward LDE: coef[poly][n] -> out[poly][beta][n] (coset-major: out[p][t][m] = P(7 w_N^(t + beta m)))
@@ -52,115 +58,9 @@ struct Tables {
 // T.tw must reach N entries and T.fs hold the tables of (logn, min(logbeta, 4)) (ensure_fourstep)
 void launch_lde(const u64* coef, u64 coef_stride, u64* out, u64* scratch, int npoly, int logn, int logbeta,
                 const Tables& T, hipStream_t s, const unsigned char* skip = nullptr);
-// generator of the four-step table for (logn, logbeta) (inverse: logbeta = -1; fourstep_size entries)
-void build_fourstep(u64* out, int logn, int logbeta, const Tables& T, hipStream_t s);
-// the pass tables alone (forward, for sizes without a four-step table; pass_tables_size entries)
-void build_pass_tables(u64* out, int logn, int logbeta, const Tables& T, hipStream_t s);
 // inverse: evals[poly][n] at 7^off7 * w_n^i -> coefficients (first `keep` written, stride out_stride)
 void launch_interpolate(const u64* evals, u64 in_stride, u64* out, u64 out_stride, u64* scratch, int npoly, int logn,
                         bool off7, u64 keep, const Tables& T, hipStream_t s, const unsigned char* skip = nullptr);
-// constant columns: flags[col] = COL_CONST where cols[col][0..n) holds one value in every row, else 0
-// (flags: ncols bytes, the allocation padded to whole 32-bit words; detection blocks cover
-// CONST_DETECT_SPAN rows each).
-// period > 0 (a unit of ncols / period traces of `period` columns each, more than one trace): the same
-// pass also compares column col >= period with column col % period of trace 0, element for element,
-// and flags[col] = COL_SHARED where they are equal and the column is not constant (a constant column
-// stays constant); trace 0's columns are never shared. The allocation then holds const_flag_bytes(ncols):
-// the pass keeps a second byte per column behind the flags.
-// vals (or nullptr): vals[col] = cols[col][0], the value of the column where it is constant
-constexpr int CONST_DETECT_SPAN = 1024, CONST_FILL_SPAN = 4096;
-constexpr unsigned char COL_CONST = 1, COL_SHARED = 2;
-__host__ __device__ constexpr size_t detect_same_off(size_t ncols) { return (ncols + 3) & ~(size_t)3; }
-constexpr size_t const_flag_bytes(size_t ncols) { return 2 * detect_same_off(ncols); }
-// a flag byte as a class: 0 live, 1 constant, 2 the same as the unit's first trace's column
-__host__ __device__ constexpr int col_class(unsigned char f) { return (f & COL_CONST) ? 1 : ((f & COL_SHARED) ? 2 : 0); }
-void launch_const_detect(const u64* cols, int ncols, int logn, unsigned char* flags, hipStream_t s, int period = 0,
-                         u64* vals = nullptr);
-// the same flags and vals for a unit of B generated traces of seven columns (period 7), from the rows as the
-// generator returns them and without a trace in memory: what launch_const_detect finds in the trace that
-// launch_trace_gen would write dense, byte for byte. synth: the synthetic generator (host; debug), else the burn AIR's
-void launch_trace_probe(const AirConst* air, int B, int logn, unsigned char* flags, u64* vals, hipStream_t s,
-                        const SynthRowGen* synth = nullptr);
-// what the NTTs would have produced for the flagged columns, v = src[col * src_stride]:
-// coef[col] = (v, 0, ..., 0) and lde[col][t][m] = v (coset-major planes); coef or lde may be nullptr.
-// Outside the prover's chain (its readers take a ColConst): xfg_debug_lde_skip and xfg_debug_interpolate_skip
-void launch_const_fill(const unsigned char* flags, const u64* src, u64 src_stride, u64* coef, u64* lde, int ncols,
-                       int logn, int logbeta, hipStream_t s);
-
-// The flagged columns as the consumers of the trace's planes take them (the LDE [B][7][beta][n] and the
-// coefficients [B][7][n]): neither plane of a flagged column is ever written (launch_trace_lde). Every
-// element of a constant column's LDE plane is the column's value; a shared column's planes are those of
-// the same column of proof 0, which lie in proof 0's slot of the same buffer.
-//   flags  [B * 7] the detection's bytes (COL_CONST, COL_SHARED; device, 4-byte aligned, the allocation
-//          padded to whole 32-bit words); nullptr: dense, every plane is read
-//   vals   the value of column c of proof b lies at vals[(b * 7 + c) * val_stride]
-struct ColConst {
-    const unsigned char* flags = nullptr;
-    const u64* vals = nullptr;
-    u64 val_stride = 0;
-};
-// one proof's flagged columns in registers: bit c of mask (constant) and v[c] where it is set; bit c of
-// shared (never set beside the same bit of mask): the column is read from proof 0's planes
-struct RowConst {
-    unsigned mask, shared;
-    u64 v[7];
-    // base[i] of the proof's own planes, or of proof 0's for a shared column: one select between the
-    // two bases (both wave-uniform in a kernel that runs a block per proof), not a pointer per column
-    __device__ __forceinline__ const u64* plane(int c, const u64* own, const u64* first) const {
-        return (shared >> c) & 1 ? first : own;
-    }
-};
-// the seven flag bytes of a proof, o = proof * 7, out of two or three aligned 32-bit loads: byte c = flags[o + c]
-__device__ __forceinline__ u64 row_flag_bytes(const unsigned char* flags, u64 o) {
-    const uint32_t* w = reinterpret_cast<const uint32_t*>(flags) + (o >> 2);
-    const unsigned r = (unsigned)(o & 3);
-    u64 bytes = ((u64)w[0] | ((u64)w[1] << 32)) >> (8 * r);  // flags o .. o + 7 - r
-    if (r >= 2) bytes |= (u64)w[2] << (64 - 8 * r);           // o + 8 - r .. (inside the padded allocation)
-    return bytes;
-}
-// for a proof that is the same in every lane (a block per proof): the seven flags come out of two or
-// three aligned 32-bit loads and the values of 64-bit ones at wave-uniform addresses (scalar loads),
-// and mask and values are made wave-uniform for the branches that leave the flagged loads out
-__device__ __forceinline__ RowConst row_const_uniform(const ColConst& cc, u64 proof) {
-    const u64 o = proof * 7;
-    const u64 bytes = row_flag_bytes(cc.flags, o);
-    RowConst rc;
-    rc.mask = rc.shared = 0;
-#pragma unroll
-    for (int c = 0; c < 7; c++) {
-        const unsigned f = (unsigned)(bytes >> (8 * c)) & 0xFF;
-        rc.mask |= (f & COL_CONST ? 1u : 0u) << c;
-        rc.shared |= ((f & (COL_CONST | COL_SHARED)) == COL_SHARED ? 1u : 0u) << c;
-    }
-    rc.mask = __builtin_amdgcn_readfirstlane(rc.mask);
-    rc.shared = __builtin_amdgcn_readfirstlane(rc.shared);
-#pragma unroll
-    for (int c = 0; c < 7; c++) {
-        rc.v[c] = 0;
-        if ((rc.mask >> c) & 1) {
-            const u64 v = cc.vals[(o + c) * cc.val_stride];
-            const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-            const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
-            rc.v[c] = (u64)lo | ((u64)hi << 32);
-        }
-    }
-    return rc;
-}
-// for a proof that differs from lane to lane (the openings): plain loads. The seven words at vals are
-// loaded whatever the flags say (an unflagged column's is its coefficient 0, never used), so that they
-// are in flight beside the flags and not behind them: a lone proof waits on this chain
-__device__ __forceinline__ RowConst row_const_lane(const ColConst& cc, u64 proof) {
-    RowConst rc;
-    rc.mask = rc.shared = 0;
-#pragma unroll
-    for (int c = 0; c < 7; c++) {
-        rc.v[c] = cc.vals[(proof * 7 + c) * cc.val_stride];
-        const unsigned f = cc.flags[proof * 7 + c];
-        rc.mask |= (f & COL_CONST ? 1u : 0u) << c;
-        rc.shared |= ((f & (COL_CONST | COL_SHARED)) == COL_SHARED ? 1u : 0u) << c;
-    }
-    return rc;
-}
 
 // ---- device-side Fiat-Shamir (winter-crypto DefaultRandomCoin<Blake3_256>, as host_common.hpp Coin).
 // Each transcript step runs in the kernel that produces its input, one proof per block; the host
@@ -217,10 +117,6 @@ void launch_merkle_fri(const u64* vals, u64 val_stride, u64 comp_stride, bool co
                        const CoinStep& cs = CoinStep{});
 
 // ---- AIR ----
-// the generated traces [npoly][7][n], live columns only: flags [npoly * 7] are the classified bytes
-// (launch_trace_probe), and the plane of a column flagged COL_CONST or COL_SHARED is not written
-void launch_trace_gen(const AirConst* air, u64* trace, const unsigned char* flags, int logn, int npoly, hipStream_t s,
-                      const SynthRowGen* synth = nullptr);
 // Trace::validate on the device (trace_check_kernel): keys[proof] = the smallest key of what the trace
 // [npoly][7][n] violates, TRACE_KEY_VALID (all ones) when nothing. A key is kind << 62 | step << 3 | index,
 // so that their order is the order of the report: a cell >= p first (index = column; such a cell is also

@@ -182,7 +182,7 @@ void launch_trace_lde(Lane* c, const Tables& T, int B, const ProofShape& sh, boo
     if (generated) {
         // found in the rows as they are generated; then the live columns alone go to c->trace
         launch_trace_probe(c->air.p, B, sh.logn, c->const_col.p, c->const_val.p, s);
-        launch_trace_gen(c->air.p, c->trace.p, c->const_col.p, sh.logn, B, s);
+        launch_trace_gen(c->air.p, B, sh.logn, c->const_col.p, c->trace.p, s);
     } else {  // one pass over the trace
         launch_const_detect(c->trace.p, B * 7, sh.logn, c->const_col.p, s, 7, c->const_val.p);
     }

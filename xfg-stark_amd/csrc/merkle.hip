@@ -90,7 +90,7 @@ __device__ __forceinline__ void quad_level(const Digest* src, bool act, int i, i
 
 // ============================================================================ LDE leaves
 // One leaf's elements: row[c] = column c of the LDE at coset t, row m. CC (a trace LDE with constant
-// columns, NC = 7; kernels.hpp ColConst): a column flagged in rc comes from rc and its load is not
+// columns, NC = 7; columns.hpp ColConst): a column flagged in rc comes from rc and its load is not
 // issued; a column shared in rc is read at the same place of proof 0's planes, `back` words before the
 // proof's own (one offset, selected per column: wave-uniform where a block serves one proof, per lane in
 // the openings). CC = false is the dense read and takes no RowConst (NoConst)

@@ -17,16 +17,11 @@
 // Forward LDE output is coset-major: out[p][t][m] = P(7 * w_N^(t + beta*m)), N = beta * n.
 // The coset shift (7 w_N^t)^j, j = C j1 + j2, is split into a pre-factor 7^(C j1) w_(beta R)^(t j1)
 // (LDS table per coset) and a post-factor 7^j2 w_N^(j2 t) folded into the four-step twiddle.
-#include <algorithm>
 #include <atomic>
-#include <cstdlib>
 #include <string>
-#include <type_traits>
-#include <utility>
 #include "hip_util.hpp"
 #include "kernels.hpp"
 #include "field_dft.hpp"
-#include "ntt_plan.hpp"
 
 namespace xfg {
 
@@ -60,7 +55,6 @@ __device__ __forceinline__ void buf_st(__amdgpu_buffer_rsrc_t r, u32 voff, u32 s
 // the odd lane both words of the odd ones: half as many store instructions, 16 B per lane. (A wave
 // ending a tile with 32 8-byte stores per lane is store-issue-bound: MI355X_MICROARCH.md, "store
 // tail".) Full tiles only: both lanes of a pair must hold a group.
-typedef u64 u64x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ u64 swap_lane_pair(u64 x) {
     const int lo = __builtin_amdgcn_mov_dpp((int)(u32)x, 0xB1, 0xF, 0xF, false);
     const int hi = __builtin_amdgcn_mov_dpp((int)(u32)(x >> 32), 0xB1, 0xF, 0xF, false);
@@ -105,13 +99,6 @@ __device__ __forceinline__ int phys(int i) { return i + (i >> P); }
 template <int P>
 __device__ __forceinline__ int phys2(int j, int o) {
     return (o & ((1 << P) - 1)) == 0 ? phys<P>(j) + o + (o >> P) : phys<P>(j + o);
-}
-
-__device__ __forceinline__ u64 tw_get(const Tables& T, int k, u64 e, bool inv) {
-    const u64 M = 1ULL << T.LM;
-    u64 idx = (e << (T.LM - k)) & (M - 1);
-    if (inv) idx = (M - idx) & (M - 1);
-    return T.tw[idx];
 }
 
 // ---------------------------------------------------------------- one Stockham step
@@ -295,7 +282,7 @@ struct NttArgs {
     int tq_b;       // forward: pass B applies the four-step twiddles as it loads (ntt_pass_a_cos)
     int preg;       // forward pass A: coset pre-factors read from the pass tables in L2, not LDS
     const unsigned char* skip;  // [poly]: non-zero -> the polynomial is not transformed (its blocks return
-                                // at once; launch_const_fill writes its outputs); nullptr: transform all
+                                // at once; a flagged column, columns.hpp); nullptr: transform all
     Tables T;
     __device__ PassTableLayout tab() const { return {logR, logC, logbeta}; }
     // wave-uniform (poly comes from the block index); tested before a block's first barrier and after
@@ -863,77 +850,6 @@ __global__ __launch_bounds__(1 << LOGT, MINW) void ntt_pass_b_pers(NttArgs a, in
     }
 }
 
-// ---------------------------------------------------------------- tables
-__global__ void fourstep_kernel(u64* out, int logn, int logbeta, int logC, u64 scale, Tables T) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    const u64 n = 1ULL << logn;
-    if (logbeta < 0) {
-        if (i >= n) return;
-        const u64 k1 = i >> logC, j2 = i & ((1ULL << logC) - 1);
-        out[i] = gl_mul(tw_get(T, logn, (j2 * k1) & (n - 1), true), scale);
-    } else {
-        const int logN = logn + logbeta;
-        if (i >= (1ULL << logN)) return;
-        const u64 t = i >> logn, k1 = (i & (n - 1)) >> logC, j2 = i & ((1ULL << logC) - 1);
-        out[i] = gl_mul(T.pow7[j2], tw_get(T, logN, (j2 * (t + (k1 << logbeta))) & ((1ULL << logN) - 1), false));
-    }
-}
-// the pass tables (PassTableLayout, ntt_plan.hpp): what every pass block would otherwise gather from
-// the master tables at its start
-__global__ void pass_tables_kernel(u64* out, PassTableLayout L, Tables T) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    const int logR = L.logR, logC = L.logC, logbeta = L.logbeta;
-    const u64 R = L.R(), C = L.C(), Z = 0;
-    if (i >= L.total()) return;
-    if (i < L.wC()) {
-        out[i] = tw_get(T, logR, i, !L.fwd());
-    } else if (i < L.pre(Z)) {
-        out[i] = tw_get(T, logC, i - L.wC(), !L.fwd());
-    } else if (i < L.comb(Z)) {
-        const u64 t = (i - L.pre(Z)) >> logR, j = (i - L.pre(Z)) & (R - 1);
-        out[i] = gl_mul(T.pow7[j << logC], tw_get(T, logR + logbeta, (t * j) & ((1ULL << (logR + logbeta)) - 1), false));
-    } else if (L.has_r1024() && i < L.r1024_seed(Z)) {
-        // ntt_pass_a_r1024: [t][r][k] = w_1024^(r k) g_t^r, g_t^r = 7^(C r) w_(beta R)^(t r)  (r, k < 32)
-        const u64 q = i - L.comb(Z);
-        const u64 t = q >> 10, r = (q >> 5) & 31, k = q & 31;
-        const u64 g = gl_mul(T.pow7[r << logC], tw_get(T, logR + logbeta, (t * r) & ((1ULL << (logR + logbeta)) - 1), false));
-        out[i] = gl_mul(tw_get(T, logR, r * k, false), g);
-    } else if (L.has_r1024()) {
-        // ntt_pass_a_r1024's four-step factors: [t][j2] 7^j2 w_N^(j2 t) (t < beta, j2 < C) and the
-        // t-independent four-step table [k1][j2] w_n^(j2 k1) (R x C)
-        const int logn = logR + logC, logN = logn + logbeta;
-        const u64 j2 = i & (C - 1);  // both regions start at multiples of C
-        if (i < L.r1024_t4()) {
-            const u64 t = (i - L.r1024_seed(Z)) >> logC;
-            out[i] = gl_mul(T.pow7[j2], tw_get(T, logN, (j2 * t) & ((1ULL << logN) - 1), false));
-        } else {
-            const u64 k1 = (i - L.r1024_t4()) >> logC;
-            out[i] = tw_get(T, logn, (j2 * k1) & ((1ULL << logn) - 1), false);
-        }
-    } else if (i < L.cos2_scal()) {
-        // ntt_pass_a_cos2: [t][r][k] = w_R^(r k) 7^(C r) w_(beta R)^(t r)
-        const u64 q = i - L.comb(Z);
-        const u64 t = q >> 8, r = (q >> 4) & 15, k = q & 15;
-        const u64 grp = gl_mul(T.pow7[r << logC], tw_get(T, logR + logbeta, (t * r) & ((1ULL << (logR + logbeta)) - 1), false));
-        out[i] = gl_mul(tw_get(T, logR, r * k, false), grp);
-    } else {
-        // ntt_pass_a_cos2: [c][r] = 7^(16 C r) w_(16 beta)^(c r)
-        const u64 q = i - L.cos2_scal();
-        const u64 c = q >> 4, r = q & 15;
-        out[i] = gl_mul(T.pow7[(16 * r) << logC], tw_get(T, 4 + logbeta, (c * r) & ((1ULL << (4 + logbeta)) - 1), false));
-    }
-}
-void build_pass_tables(u64* out, int logn, int logbeta, const Tables& T, hipStream_t s) {
-    const PassTableLayout L = pass_table_layout(logn, logbeta);
-    hipLaunchKernelGGL(pass_tables_kernel, dim3((unsigned)((L.total() + 255) / 256)), dim3(256), 0, s, out, L, T);
-}
-void build_fourstep(u64* out, int logn, int logbeta, const Tables& T, hipStream_t s) {
-    const u64 cnt = fourstep_main(logn, logbeta);
-    hipLaunchKernelGGL(fourstep_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, out, logn, logbeta,
-                       pass_table_layout(logn, logbeta).logC, gl_inv(1ULL << logn), T);
-    build_pass_tables(out + cnt, logn, logbeta, T, s);
-}
-
 // ---------------------------------------------------------------- dispatch
 // every kernel ntt_plan can name, with its key: XFG_NTT_KERNELS (ntt_plan.hpp) is the only list
 struct NttEntry {
@@ -975,165 +891,6 @@ static void ntt_run(NttArgs& a, int npoly, bool inv, hipStream_t s) {
     void* args[] = {&a, &p.ntx, &p.ntiles};  // the last two are ntt_pass_b_pers's alone
     ntt_launch(p.a, args, s);
     ntt_launch(p.b, args, s);
-}
-
-// ---------------------------------------------------------------- constant columns
-// A column that holds one value v in every row interpolates to the constant v, and its LDE is v at
-// every point: such columns take no NTT. const_detect_kernel finds them in whatever trace arrives
-// (trace_probe_kernel: in the rows of a trace the prover generates itself, as they are generated),
-// the NTT kernels return at once for them (NttArgs::skip). Their coefficient and LDE planes stay
-// unwritten in the prover: every reader of either takes the value from a ColConst (kernels.hpp);
-// const_fill_kernel serves xfg_debug_lde_skip and xfg_debug_interpolate_skip alone.
-//
-// Shared columns: a column of proof b > 0 of a unit that equals the same column of the unit's proof 0
-// element for element has proof 0's coefficients and proof 0's LDE: it takes no NTT either, and its
-// readers go to proof 0's planes (ColConst). The same detection pass finds them, in whatever traces
-// arrive; the representative is proof 0 and nothing more general, so a unit whose first trace differs
-// from the others shares nothing. A column that is constant stays constant (cheaper for every reader).
-// The pass keeps two bytes per column, both preset to 1 and both only ever overwritten with 0, so that
-// every writer of a byte stores the same value and nothing needs an atomic (one byte with two bits,
-// cleared by atomic ANDs, measured 127 us per 64-proof unit against 41 for the constancy pass alone and
-// 51 for this form, profiles/r15: the blocks of a proof's columns all hit the same one or two words):
-// flags[col], the constancy, and same[col] = flags[detect_same_off(ncols)
-// + col]. const_class_kernel then folds the second into the first as COL_SHARED
-__global__ void const_flags_init_kernel(unsigned char* flags, int count, int period) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    flags[i] = 1;
-    if (period) flags[detect_same_off(count) + i] = i >= period ? 1 : 0;  // trace 0's columns are never shared
-}
-// flags[col] (preset to 1) -> 0 where some element of cols[col][0..n) differs from element 0 and, SHARE,
-// same[col] -> 0 where some element differs from the same element of column col % period (trace 0's; the
-// columns below period are trace 0's own and are compared with nothing). One block per
-// CONST_DETECT_SPAN rows of a column (min(256, n) threads, coalesced strides); a thread that saw a
-// difference stores 0. The pass reads the trace once; trace 0's column (8 n bytes) is read again by
-// every other trace's blocks, from the cache.
-// vals[col] = element 0 (block 0 of the column; read only where the column turns out constant)
-template <bool SHARE>
-__global__ __launch_bounds__(256) void const_detect_kernel(const u64* cols, u64 n, unsigned char* flags, int period,
-                                                           u64* vals) {
-    const int col = blockIdx.y;
-    const u64* c = cols + (u64)col * n;
-    const u64 first = c[0];
-    const u64 i0 = (u64)blockIdx.x * CONST_DETECT_SPAN, i1 = i0 + CONST_DETECT_SPAN < n ? i0 + CONST_DETECT_SPAN : n;
-    if (vals && blockIdx.x == 0 && threadIdx.x == 0) vals[col] = first;
-    u64 diff = 0;
-    if (SHARE && col >= period) {  // block-uniform
-        const u64* c0 = cols + (u64)(col % period) * n;
-        u64 diff0 = 0;
-#pragma unroll 4
-        for (u64 i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
-            const u64 x = c[i];
-            diff |= x ^ first;
-            diff0 |= x ^ c0[i];
-        }
-        if (diff0) flags[detect_same_off(gridDim.y) + col] = 0;
-    } else {
-        for (u64 i = i0 + threadIdx.x; i < i1; i += blockDim.x) diff |= c[i] ^ first;
-    }
-    if (diff) flags[col] = 0;
-}
-// flags[col]: 1 -> COL_CONST, else COL_SHARED where same[col] is still set, else 0
-__global__ void const_class_kernel(unsigned char* flags, int count) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) flags[i] = flags[i] ? COL_CONST : (flags[detect_same_off(count) + i] ? COL_SHARED : 0);
-}
-void launch_const_detect(const u64* cols, int ncols, int logn, unsigned char* flags, hipStream_t s, int period,
-                         u64* vals) {
-    const u64 n = 1ULL << logn;
-    if (period <= 0 || ncols <= period) period = 0;  // one trace: nothing to share, nothing extra is run
-    const dim3 gi((unsigned)((ncols + 255) / 256)), bi(256);
-    hipLaunchKernelGGL(const_flags_init_kernel, gi, bi, 0, s, flags, ncols, period);
-    const dim3 g((unsigned)((n + CONST_DETECT_SPAN - 1) / CONST_DETECT_SPAN), ncols), b((unsigned)std::min<u64>(256, n));
-    if (period) {
-        hipLaunchKernelGGL(const_detect_kernel<true>, g, b, 0, s, cols, n, flags, period, vals);
-        hipLaunchKernelGGL(const_class_kernel, gi, bi, 0, s, flags, ncols);
-    } else {
-        hipLaunchKernelGGL(const_detect_kernel<false>, g, b, 0, s, cols, n, flags, period, vals);
-    }
-}
-// The detection for a unit of generated traces, on the rows as Gen (air.hpp) returns them: the trace is
-// not in memory, and the kernel's only loads are the AirConsts. The geometry is const_detect_kernel's with
-// the seven columns of a proof in one block: block (x, b) generates its CONST_DETECT_SPAN rows of proof b,
-// row 0 of proof b and (period: more than one proof, b > 0) the same rows of proof 0, and ORs the
-// differences per column; the two bytes per column, their presets, the stores of 0 and vals are as above.
-// What it says about a column is what the values say, never which generator ran
-template <class Gen>
-__global__ __launch_bounds__(256) void trace_probe_kernel(Gen gen, const AirConst* air, int logn, unsigned char* flags,
-                                                          int period, u64* vals) {
-    const int b = blockIdx.y;
-    const u64 n = 1ULL << logn;
-    const AirConst& A = air[b];
-    const u64 i0 = (u64)blockIdx.x * CONST_DETECT_SPAN, i1 = i0 + CONST_DETECT_SPAN < n ? i0 + CONST_DETECT_SPAN : n;
-    u64 first[7], diff[7] = {}, diff0[7] = {};
-    gen(A, logn, 0, first);
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (int c = 0; c < 7; c++) vals[b * 7 + c] = first[c];
-    const bool share = period && b > 0;  // block-uniform
-    for (u64 i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
-        u64 x[7];
-        gen(A, logn, i, x);
-#pragma unroll
-        for (int c = 0; c < 7; c++) diff[c] |= x[c] ^ first[c];
-        if (share) {
-            u64 y[7];
-            gen(air[0], logn, i, y);
-#pragma unroll
-            for (int c = 0; c < 7; c++) diff0[c] |= x[c] ^ y[c];
-        }
-    }
-    unsigned char* same = flags + detect_same_off((size_t)gridDim.y * 7);
-#pragma unroll
-    for (int c = 0; c < 7; c++) {
-        if (diff[c]) flags[b * 7 + c] = 0;
-        if (share && diff0[c]) same[b * 7 + c] = 0;
-    }
-}
-void launch_trace_probe(const AirConst* air, int B, int logn, unsigned char* flags, u64* vals, hipStream_t s,
-                        const SynthRowGen* synth) {
-    const u64 n = 1ULL << logn;
-    const int ncols = B * 7, period = B > 1 ? 7 : 0;  // one trace: nothing to share, no class kernel (launch_const_detect)
-    const dim3 gi((unsigned)((ncols + 255) / 256)), bi(256);
-    hipLaunchKernelGGL(const_flags_init_kernel, gi, bi, 0, s, flags, ncols, period);
-    const dim3 g((unsigned)((n + CONST_DETECT_SPAN - 1) / CONST_DETECT_SPAN), B), b((unsigned)std::min<u64>(256, n));
-    if (synth) hipLaunchKernelGGL(trace_probe_kernel<SynthRowGen>, g, b, 0, s, *synth, air, logn, flags, period, vals);
-    else hipLaunchKernelGGL(trace_probe_kernel<BurnRowGen>, g, b, 0, s, BurnRowGen{}, air, logn, flags, period, vals);
-    if (period) hipLaunchKernelGGL(const_class_kernel, gi, bi, 0, s, flags, ncols);
-}
-// outputs of the flagged columns, v = src[col * src_stride]: coef[col] = (v, 0, ..., 0) (n entries) and
-// lde[col][t][m] = v (N = beta n entries, the coset-major plane is simply full of v); either may be null.
-// Block x of a column writes entries [x, x + 1) * CONST_FILL_SPAN of the LDE plane and the same
-// fraction of the coefficients, in 16-byte stores (n and N are even, planes 16-byte aligned); blocks of
-// unflagged columns exit
-__global__ __launch_bounds__(256) void const_fill_kernel(const unsigned char* flags, const u64* src, u64 src_stride,
-                                                         u64* coef, u64* lde, u64 n, int logbeta) {
-    const int col = blockIdx.y;
-    if (!flags[col]) return;
-    const u64 v = src[(u64)col * src_stride];
-    const u64 i0 = (u64)blockIdx.x * CONST_FILL_SPAN;
-    if (lde) {
-        const u64 N = n << logbeta, i1 = i0 + CONST_FILL_SPAN < N ? i0 + CONST_FILL_SPAN : N;
-        u64* o = lde + (u64)col * N;
-        const u64x2 d = {v, v};
-        for (u64 i = i0 + 2 * threadIdx.x; i < i1; i += 2 * blockDim.x) *reinterpret_cast<u64x2*>(o + i) = d;
-    }
-    if (coef) {
-        // the block's share of the n coefficients (at least two per block: beta <= CONST_FILL_SPAN / 2)
-        const u64 span = lde ? (u64)CONST_FILL_SPAN >> logbeta : (u64)CONST_FILL_SPAN;
-        const u64 c0 = (u64)blockIdx.x * span, c1 = c0 + span < n ? c0 + span : n;
-        u64* o = coef + (u64)col * n;
-        for (u64 i = c0 + 2 * threadIdx.x; i < c1; i += 2 * blockDim.x) {
-            const u64x2 d = {i == 0 ? v : 0, 0};
-            *reinterpret_cast<u64x2*>(o + i) = d;
-        }
-    }
-}
-void launch_const_fill(const unsigned char* flags, const u64* src, u64 src_stride, u64* coef, u64* lde, int ncols,
-                       int logn, int logbeta, hipStream_t s) {
-    if (!coef && !lde) return;
-    const u64 n = 1ULL << logn, span = lde ? n << logbeta : n;
-    hipLaunchKernelGGL(const_fill_kernel, dim3((unsigned)((span + CONST_FILL_SPAN - 1) / CONST_FILL_SPAN), ncols),
-                       dim3(256), 0, s, flags, src, src_stride, coef, lde, n, lde ? logbeta : 0);
 }
 
 // ---------------------------------------------------------------- blowup 32, 64, 128: the twist

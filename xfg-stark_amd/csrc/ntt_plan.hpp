@@ -1,7 +1,7 @@
 // What the four-step NTT launches for a given shape, and where its tables and LDS regions lie: pure
 // functions, no HIP (tests/sanitize/ntt_plan.cpp compiles this header with a plain host compiler).
-// ntt.hip launches what ntt_plan() returns; its kernels and table generators take every offset from
-// the layout types here.
+// ntt.hip launches what ntt_plan() returns; its kernels and the table generators (tables.hip) take
+// every offset from the layout types here.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

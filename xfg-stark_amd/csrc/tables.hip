@@ -78,6 +78,77 @@ Tables tables_of(xfg_ctx* c) {
     T.fs = &c->tables.fs;
     return T;
 }
+__global__ void fourstep_kernel(u64* out, int logn, int logbeta, int logC, u64 scale, Tables T) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    const u64 n = 1ULL << logn;
+    if (logbeta < 0) {
+        if (i >= n) return;
+        const u64 k1 = i >> logC, j2 = i & ((1ULL << logC) - 1);
+        out[i] = gl_mul(tw_get(T, logn, (j2 * k1) & (n - 1), true), scale);
+    } else {
+        const int logN = logn + logbeta;
+        if (i >= (1ULL << logN)) return;
+        const u64 t = i >> logn, k1 = (i & (n - 1)) >> logC, j2 = i & ((1ULL << logC) - 1);
+        out[i] = gl_mul(T.pow7[j2], tw_get(T, logN, (j2 * (t + (k1 << logbeta))) & ((1ULL << logN) - 1), false));
+    }
+}
+// the pass tables (PassTableLayout, ntt_plan.hpp): what every pass block would otherwise gather from
+// the master tables at its start
+__global__ void pass_tables_kernel(u64* out, PassTableLayout L, Tables T) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    const int logR = L.logR, logC = L.logC, logbeta = L.logbeta;
+    const u64 R = L.R(), C = L.C(), Z = 0;
+    if (i >= L.total()) return;
+    if (i < L.wC()) {
+        out[i] = tw_get(T, logR, i, !L.fwd());
+    } else if (i < L.pre(Z)) {
+        out[i] = tw_get(T, logC, i - L.wC(), !L.fwd());
+    } else if (i < L.comb(Z)) {
+        const u64 t = (i - L.pre(Z)) >> logR, j = (i - L.pre(Z)) & (R - 1);
+        out[i] = gl_mul(T.pow7[j << logC], tw_get(T, logR + logbeta, (t * j) & ((1ULL << (logR + logbeta)) - 1), false));
+    } else if (L.has_r1024() && i < L.r1024_seed(Z)) {
+        // ntt_pass_a_r1024: [t][r][k] = w_1024^(r k) g_t^r, g_t^r = 7^(C r) w_(beta R)^(t r)  (r, k < 32)
+        const u64 q = i - L.comb(Z);
+        const u64 t = q >> 10, r = (q >> 5) & 31, k = q & 31;
+        const u64 g = gl_mul(T.pow7[r << logC], tw_get(T, logR + logbeta, (t * r) & ((1ULL << (logR + logbeta)) - 1), false));
+        out[i] = gl_mul(tw_get(T, logR, r * k, false), g);
+    } else if (L.has_r1024()) {
+        // ntt_pass_a_r1024's four-step factors: [t][j2] 7^j2 w_N^(j2 t) (t < beta, j2 < C) and the
+        // t-independent four-step table [k1][j2] w_n^(j2 k1) (R x C)
+        const int logn = logR + logC, logN = logn + logbeta;
+        const u64 j2 = i & (C - 1);  // both regions start at multiples of C
+        if (i < L.r1024_t4()) {
+            const u64 t = (i - L.r1024_seed(Z)) >> logC;
+            out[i] = gl_mul(T.pow7[j2], tw_get(T, logN, (j2 * t) & ((1ULL << logN) - 1), false));
+        } else {
+            const u64 k1 = (i - L.r1024_t4()) >> logC;
+            out[i] = tw_get(T, logn, (j2 * k1) & ((1ULL << logn) - 1), false);
+        }
+    } else if (i < L.cos2_scal()) {
+        // ntt_pass_a_cos2: [t][r][k] = w_R^(r k) 7^(C r) w_(beta R)^(t r)
+        const u64 q = i - L.comb(Z);
+        const u64 t = q >> 8, r = (q >> 4) & 15, k = q & 15;
+        const u64 grp = gl_mul(T.pow7[r << logC], tw_get(T, logR + logbeta, (t * r) & ((1ULL << (logR + logbeta)) - 1), false));
+        out[i] = gl_mul(tw_get(T, logR, r * k, false), grp);
+    } else {
+        // ntt_pass_a_cos2: [c][r] = 7^(16 C r) w_(16 beta)^(c r)
+        const u64 q = i - L.cos2_scal();
+        const u64 c = q >> 4, r = q & 15;
+        out[i] = gl_mul(T.pow7[(16 * r) << logC], tw_get(T, 4 + logbeta, (c * r) & ((1ULL << (4 + logbeta)) - 1), false));
+    }
+}
+// the pass tables alone (forward, for sizes without a four-step table; pass_tables_size entries)
+static void build_pass_tables(u64* out, int logn, int logbeta, const Tables& T, hipStream_t s) {
+    const PassTableLayout L = pass_table_layout(logn, logbeta);
+    hipLaunchKernelGGL(pass_tables_kernel, dim3((unsigned)((L.total() + 255) / 256)), dim3(256), 0, s, out, L, T);
+}
+// the four-step table with its pass tables behind it (fourstep_size entries)
+static void build_fourstep(u64* out, int logn, int logbeta, const Tables& T, hipStream_t s) {
+    const u64 cnt = fourstep_main(logn, logbeta);
+    hipLaunchKernelGGL(fourstep_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, out, logn, logbeta,
+                       pass_table_layout(logn, logbeta).logC, gl_inv(1ULL << logn), T);
+    build_pass_tables(out + cnt, logn, logbeta, T, s);
+}
 // four-step twiddle tables of the NTT sizes one (n, beta) proof uses: the forward LDE and the
 // inverse NTTs of sizes 8 .. 2n (trace, composition, FRI remainder). Sizes whose table would exceed
 // 2^FOURSTEP_MAX_LOG entries get the per-size pass tables instead (at 2^20 with the n-entry [k1][j2]
