@@ -28,6 +28,121 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, s), s
 
 
+def header_prototypes():
+    """every function the header declares: name -> (return type, [parameter declarations])"""
+    src = open(os.path.join(ROOT, "include", "xfg_stark.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    protos = {m.group(2): (" ".join(m.group(1).split()), [p.strip() for p in m.group(3).split(",")])
+              for m in re.finditer(r"\b((?:const\s+)?\w+[\s*]+)(xfg_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src)}
+    assert sorted(protos) == header_symbols()  # the expression misses no declaration
+    return protos
+
+
+SCALARS = {"uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "size_t": C.c_size_t, "int": C.c_int, "double": C.c_double}
+
+
+def is_pointer_kind(t):
+    return t in (C.c_void_p, C.c_char_p) or (isinstance(t, type) and issubclass(t, (C._Pointer, C.Array)))
+
+
+def prototype_mismatches(table, protos):
+    """what is wrong with the (name, restype, argtypes) rows of `table` against the header's prototypes"""
+    bad = [f"{name}: a row without a prototype in the header" for name, _, _ in table if name not in protos]
+    rows = {name: (restype, argtypes) for name, restype, argtypes in table}
+    if len(rows) != len(table):
+        bad.append("a function has two rows")
+    for name, (ret, params) in protos.items():
+        if name not in rows:
+            bad.append(f"{name}: no row in the table")
+            continue
+        restype, argtypes = rows[name]
+        want = C.c_void_p if "*" in ret else None if ret == "void" else SCALARS[ret]
+        if restype is not want:
+            bad.append(f"{name}: returns {ret}, the row says {restype}")
+        if len(argtypes) != len(params):
+            bad.append(f"{name}: {len(params)} parameters, the row has {len(argtypes)}")
+            continue
+        for i, (p, t) in enumerate(zip(params, argtypes)):
+            if "*" in p or "[" in p:
+                if not is_pointer_kind(t):
+                    bad.append(f"{name}: parameter {i} `{p}` is a pointer, the row says {t}")
+            else:
+                ctype = " ".join(w for w in p.split()[:-1] if w != "const")
+                if t is not SCALARS[ctype]:
+                    bad.append(f"{name}: parameter {i} `{p}` is {ctype}, the row says {t}")
+    return bad
+
+
+def test_prototype_table_matches_header():
+    """the one table of restype / argtypes the package applies to the library, against include/xfg_stark.h:
+    a row per declared function and no other, the same number of arguments, a pointer kind for every
+    parameter written with * or [], the exact width for every scalar, and the return type"""
+    from xfgstark import _abi
+    protos = header_prototypes()
+    assert len(protos) >= 49
+    assert prototype_mismatches(_abi.TABLE, protos) == []
+    assert _abi.MISSING == []  # the library built from this tree exports them all
+    for name, restype, argtypes in _abi.TABLE:  # and the table is what the loaded library carries
+        fn = getattr(_abi._lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+
+
+def test_prototype_check_sees_a_wrong_row():
+    """the check itself: a row one argument short, a uint64_t narrowed to c_uint32, a scalar where the header
+    has a pointer, a wrong return type, a missing and an unknown row are each reported"""
+    from xfgstark import _abi
+    protos = header_prototypes()
+    rows = {name: (restype, list(argtypes)) for name, restype, argtypes in _abi.TABLE}
+
+    def mismatches(name, restype=None, argtypes=None):
+        r, a = rows[name]
+        table = [row for row in _abi.TABLE if row[0] != name] + [(name, restype or r, argtypes or a)]
+        return prototype_mismatches(table, protos)
+
+    a = rows["xfg_batch_wait"][1]
+    assert mismatches("xfg_batch_wait", argtypes=a[:-1]) == ["xfg_batch_wait: 2 parameters, the row has 1"]
+    assert mismatches("xfg_batch_wait", argtypes=[a[0], C.c_uint32]) == [
+        "xfg_batch_wait: parameter 1 `uint64_t ticket` is uint64_t, the row says %s" % C.c_uint32]
+    assert len(mismatches("xfg_batch_wait", argtypes=[C.c_uint64, a[1]])) == 1
+    assert len(mismatches("xfg_proof_size_bound", restype=C.c_int)) == 1
+    assert prototype_mismatches(_abi.TABLE[1:], protos) == ["xfg_ctx_create: no row in the table"]
+    assert prototype_mismatches(_abi.TABLE + [("xfg_nothing", C.c_int, [])], protos) == [
+        "xfg_nothing: a row without a prototype in the header"]
+
+
+def test_bind_skips_and_lists_missing_symbols():
+    """a library older than a hook (XFG_LIB) still loads: bind() sets the prototypes of what is there and
+    returns the names of what is not, in the table's order"""
+    from xfgstark import _abi
+
+    class Fn:
+        restype = argtypes = "untouched"
+
+    class OlderBuild:
+        pass
+
+    absent = ["xfg_selftest_field", "xfg_debug_trace_probe", "xfg_debug_grind"]
+    lib = OlderBuild()
+    for name, _, _ in _abi.TABLE:
+        if name not in absent:
+            setattr(lib, name, Fn())
+    assert _abi.bind(lib) == absent
+    assert not any(hasattr(lib, name) for name in absent)
+    for name, restype, argtypes in _abi.TABLE:
+        if name not in absent:
+            assert getattr(lib, name).restype is restype and getattr(lib, name).argtypes is argtypes, name
+
+
+def test_import_needs_neither_numpy_nor_torch():
+    """importing the package stays cheap: numpy is imported when the first array is marshalled, torch never"""
+    import subprocess
+    import sys
+    code = ("import sys; sys.path.insert(0, %r); import xfgstark, xfgstark.package; "
+            "print(sorted(m for m in ('numpy', 'torch') if m in sys.modules))" % os.path.join(ROOT, "xfg-stark_amd"))
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, check=True).stdout
+    assert out.strip() == "[]"
+
+
 def test_library_is_gfx950_code_object():
     import subprocess
     import xfgstark
