@@ -3,8 +3,9 @@ each a directory of gfx950 assembly listings, one per translation unit (the Make
 --cuda-device-only -S). For every .amdhsa_kernel symbol, wherever in its directory it lies, it compares the
 instruction text between the symbol's label and its .Lfunc_end and the .amdhsa_* descriptor lines (VGPRs, SGPRs,
 LDS, scratch). Local labels .LBB<k>_<m> carry the function's index k within its file, which changes when a kernel
-moves: k is dropped. Comments are dropped too. Prints the counts and every differing or unmatched kernel by name;
-exit status 1 when there is one."""
+moves: k is dropped. A long branch's .Lpost_getpc<j> label counts the file's long branches, so j changes as
+well: inside a kernel the labels are renumbered from 0 in the order they first appear. Comments are dropped too.
+Prints the counts and every differing or unmatched kernel by name; exit status 1 when there is one."""
 import glob
 import os
 import re
@@ -37,7 +38,9 @@ def kernels(directory):
         for sym, d in desc.items():
             if sym in out:
                 raise SystemExit(f"{sym} defined twice in {directory}")
-            out[sym] = (body[sym], d, os.path.basename(path))
+            seen = {}
+            renumber = lambda m: ".Lpost_getpc_%d" % seen.setdefault(m.group(0), len(seen))
+            out[sym] = ([re.sub(r"\.Lpost_getpc\d+", renumber, t) for t in body[sym]], d, os.path.basename(path))
     return out
 
 

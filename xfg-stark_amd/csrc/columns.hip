@@ -20,6 +20,8 @@
 // 51 for this form, profiles/r15: the blocks of a proof's columns all hit the same one or two words):
 // flags[col], the constancy, and same[col] = flags[detect_same_off(ncols) + col]. const_class_kernel
 // then folds the second into the first as COL_SHARED
+#include "dispatch.hpp"
+#include "hip_util.hpp"
 #include "kernels.hpp"
 
 namespace xfg {
@@ -75,16 +77,17 @@ static void classify(unsigned char* flags, int ncols, int ny, int logn, int peri
     const u64 n = 1ULL << logn;
     if (period <= 0 || ncols <= period) period = 0;
     const dim3 gi((unsigned)((ncols + 255) / 256)), bi(256);
-    hipLaunchKernelGGL(const_flags_init_kernel, gi, bi, 0, s, flags, ncols, period);
+    XFG_LAUNCH(const_flags_init_kernel, gi, bi, 0, s, flags, ncols, period);
     const dim3 g((unsigned)((n + CONST_DETECT_SPAN - 1) / CONST_DETECT_SPAN), ny), b(n < 256 ? (unsigned)n : 256u);
     detect(g, b, period);
-    if (period) hipLaunchKernelGGL(const_class_kernel, gi, bi, 0, s, flags, ncols);
+    if (period) XFG_LAUNCH(const_class_kernel, gi, bi, 0, s, flags, ncols);
 }
 void launch_const_detect(const u64* cols, int ncols, int logn, unsigned char* flags, hipStream_t s, int period,
                          u64* vals) {
     classify(flags, ncols, ncols, logn, period, s, [&](dim3 g, dim3 b, int period) {
-        const auto k = period ? const_detect_kernel<true> : const_detect_kernel<false>;
-        hipLaunchKernelGGL(k, g, b, 0, s, cols, 1ULL << logn, flags, period, vals);
+        with_bool(period != 0, [&](auto SHARE) {
+            XFG_LAUNCH(const_detect_kernel<SHARE>, g, b, 0, s, cols, 1ULL << logn, flags, period, vals);
+        });
     });
 }
 // f(gen), gen the row generator of a unit's generated traces: the synthetic one where given (debug), else the burn AIR's
@@ -131,7 +134,7 @@ void launch_trace_probe(const AirConst* air, int B, int logn, unsigned char* fla
                         const SynthRowGen* synth) {
     classify(flags, B * 7, B, logn, 7, s, [&](dim3 g, dim3 b, int period) {
         with_row_gen(synth, [&](auto gen) {
-            hipLaunchKernelGGL(trace_probe_kernel<decltype(gen)>, g, b, 0, s, gen, air, logn, flags, period, vals);
+            XFG_LAUNCH(trace_probe_kernel<decltype(gen)>, g, b, 0, s, gen, air, logn, flags, period, vals);
         });
     });
 }
@@ -161,9 +164,8 @@ void launch_trace_gen(const AirConst* air, int B, int logn, const unsigned char*
                       const SynthRowGen* synth) {
     const dim3 g((unsigned)(((1ULL << logn) + 255) / 256), B);
     with_row_gen(synth, [&](auto gen) {
-        hipLaunchKernelGGL(trace_gen_kernel<decltype(gen)>, g, dim3(256), 0, s, gen, air, trace, flags, logn);
+        XFG_LAUNCH(trace_gen_kernel<decltype(gen)>, g, dim3(256), 0, s, gen, air, trace, flags, logn);
     });
-    (void)hipGetLastError();
 }
 // launch_const_fill: block x of a column writes entries [x, x + 1) * CONST_FILL_SPAN of the LDE plane and the
 // same fraction of the coefficients, in 16-byte stores (n and N = beta n are even, planes 16-byte aligned);
@@ -195,8 +197,8 @@ void launch_const_fill(const unsigned char* flags, const u64* src, u64 src_strid
                        int logn, int logbeta, hipStream_t s) {
     if (!coef && !lde) return;
     const u64 n = 1ULL << logn, span = lde ? n << logbeta : n;
-    hipLaunchKernelGGL(const_fill_kernel, dim3((unsigned)((span + CONST_FILL_SPAN - 1) / CONST_FILL_SPAN), ncols),
-                       dim3(256), 0, s, flags, src, src_stride, coef, lde, n, lde ? logbeta : 0);
+    XFG_LAUNCH(const_fill_kernel, dim3((unsigned)((span + CONST_FILL_SPAN - 1) / CONST_FILL_SPAN), ncols), dim3(256), 0, s,
+               flags, src, src_stride, coef, lde, n, lde ? logbeta : 0);
 }
 
 }  // namespace xfg

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "dev_coin.hpp"
+#include "dispatch.hpp"
 #include "field_dft.hpp"
 #include "prover_internal.hpp"
 
@@ -65,11 +66,10 @@ __global__ void field_pair_op_kernel(int op, const u64* a, const u64* b, u64* ou
 static void launch_field_op(int op, const u64* a, const u64* b, u64* out, u64 count, hipStream_t s) {
     if (op >= 9) {  // count is even (checked by the caller)
         const u64 pairs = count / 2;
-        hipLaunchKernelGGL(field_pair_op_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, s, op, a, b, out,
-                           pairs);
+        XFG_LAUNCH(field_pair_op_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, s, op, a, b, out, pairs);
         return;
     }
-    hipLaunchKernelGGL(field_op_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, op, a, b, out, count);
+    XFG_LAUNCH(field_op_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, op, a, b, out, count);
 }
 
 // transcript self test (xfg_debug_coin_draws): from coin c0, k <= 64 draws by one wave (out_wave) and
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(64) void coin_draw_test_kernel(DevCoin c0, int k, i
 }
 static void launch_coin_draw_test(const DevCoin& c0, int k, int ext, const u64* rej, u64* out_wave, u64* out_seq,
                                   u64* ctr, int* ok, hipStream_t s) {
-    hipLaunchKernelGGL(coin_draw_test_kernel, dim3(1), dim3(64), 0, s, c0, k, ext, rej, out_wave, out_seq, ctr, ok);
+    XFG_LAUNCH(coin_draw_test_kernel, dim3(1), dim3(64), 0, s, c0, k, ext, rej, out_wave, out_seq, ctr, ok);
 }
 
 // xfg_debug_lde / xfg_debug_lde_skip: skip (host, [npoly]) or nullptr
@@ -646,9 +646,6 @@ int xfg_debug_constraint_eval(xfg_ctx* c, uint32_t count, uint64_t n, uint32_t b
     });
 }
 
-// log2 of a folding factor the kernels have (2, 4, 8, 16), else 0
-static unsigned debug_logf(uint32_t fold) { return fold == 2 ? 1 : fold == 4 ? 2 : fold == 8 ? 3 : fold == 16 ? 4 : 0; }
-
 int xfg_debug_fri_fold(xfg_ctx* c, uint32_t count, uint32_t ext, uint32_t logn, uint32_t logbeta, int coset_major,
                        const uint64_t* vals, const uint64_t* alpha, uint64_t* out) {
     return xfg_debug_fri_fold_f(c, count, ext, logn, logbeta, coset_major, 8, vals, alpha, out);
@@ -658,7 +655,7 @@ int xfg_debug_fri_fold_f(xfg_ctx* c, uint32_t count, uint32_t ext, uint32_t logn
                          uint32_t fold, const uint64_t* vals, const uint64_t* alpha, uint64_t* out) {
     if (!c) return XFG_INVALID_ARGUMENT;
     c->err.clear();
-    const unsigned logf = debug_logf(fold);  // D >= 2 fold
+    const unsigned logf = fold_log2(fold);  // 0: no kernel; D >= 2 fold
     if (!vals || !alpha || !out || count == 0 || (ext != 1 && ext != 2) || logn > 28 || logbeta > 28 || !logf ||
         logn + logbeta < logf + 1 || logn + logbeta > 28) {
         c->err = "xfg_debug_fri_fold: null or unsupported argument";
@@ -775,7 +772,7 @@ int xfg_debug_merkle_fri_f(xfg_ctx* c, uint32_t count, uint32_t ext, uint32_t lo
                            uint32_t fold, const uint64_t* vals, uint8_t* nodes_out) {
     if (!c) return XFG_INVALID_ARGUMENT;
     c->err.clear();
-    const unsigned logf = debug_logf(fold);  // D >= 2 fold
+    const unsigned logf = fold_log2(fold);  // 0: no kernel; D >= 2 fold
     if (!vals || !nodes_out || count == 0 || count > 0xFFFF || (ext != 1 && ext != 2) || logn > 28 || logbeta > 28 ||
         !logf || logn + logbeta < logf + 1 || logn + logbeta > 28) {
         c->err = "xfg_debug_merkle_fri: null or unsupported argument";

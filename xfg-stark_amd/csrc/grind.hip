@@ -104,9 +104,8 @@ void launch_grind(const Digest* seeds, u64* state, u64* out, unsigned B, unsigne
     GrindArgs a{seeds, state, state + words, first, max_nonce, B, grind, chunk_log};
     HIPCHK(hipMemsetAsync(a.best, 0xFF, words * 8, s));
     HIPCHK(hipMemsetAsync(a.next_chunk, 0, words * 8, s));
-    hipLaunchKernelGGL(grind_kernel, dim3(blocks), dim3(grind_block_size(chunk_log)), 0, s, a);
-    hipLaunchKernelGGL(grind_collect_kernel, dim3((B + 255) / 256), dim3(256), 0, s, a.best, out, B);
-    (void)hipGetLastError();
+    XFG_LAUNCH(grind_kernel, dim3(blocks), dim3(grind_block_size(chunk_log)), 0, s, a);
+    XFG_LAUNCH(grind_collect_kernel, dim3((B + 255) / 256), dim3(256), 0, s, a.best, out, B);
 }
 
 }  // namespace xfg

@@ -1,5 +1,6 @@
-// HIP error handling, the XFG_TRACE switch and the owning device / pinned-host buffer types of the
-// prover's host code (tables.hip, lane_unit.hip, prover.hip, debug_abi.hip, verify_batch_gpu.hip).
+// HIP error handling and the one kernel launcher (every .hip file), the XFG_TRACE switch and the owning
+// device / pinned-host buffer types of the prover's host code (tables.hip, lane_unit.hip, prover.hip,
+// debug_abi.hip, verify_batch_gpu.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -19,6 +20,28 @@ struct HipError : std::runtime_error {
         if (e_ != hipSuccess)                                                                      \
             throw HipError(std::string("HIP error ") + hipGetErrorString(e_) + " at " #x);        \
     } while (0)
+
+// Every kernel launch of the library: XFG_LAUNCH(kernel, grid, block, dynamic LDS bytes, stream, args...).
+// The parameter types come from the kernel's own signature and each argument is converted to its parameter
+// as a direct call would convert it, so a wrong pointer type or argument count does not compile. A launch the
+// runtime refuses (a grid row past 65535, a block or an LDS request over the limit, no device) throws
+// HipError naming the kernel: it would otherwise leave no trace, not even at the next synchronisation.
+template <class T>
+struct SameType {
+    using type = T;
+};
+inline void launch_checked(const char* name, const void* fn, dim3 grid, dim3 block, void** args, size_t lds,
+                           hipStream_t s) {
+    const hipError_t e = hipLaunchKernel(fn, grid, block, args, lds, s);
+    if (e != hipSuccess) throw HipError(std::string("launch of ") + name + ": " + hipGetErrorString(e));
+}
+template <class... P>
+void launch_kernel(const char* name, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s,
+                   typename SameType<P>::type... p) {  // P is deduced from the kernel alone
+    void* args[sizeof...(P) + 1] = {(void*)&p..., nullptr};
+    launch_checked(name, (const void*)kernel, grid, block, args, lds, s);
+}
+#define XFG_LAUNCH(kernel, ...) ::xfg::launch_kernel(#kernel, kernel, __VA_ARGS__)
 
 // XFG_TRACE=1: host-side phase timestamps of every prove call (and any workspace reallocation,
 // which synchronises the device), printed to stderr

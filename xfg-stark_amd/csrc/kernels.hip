@@ -12,14 +12,13 @@
 // the device transcript itself is dev_coin.hpp (here: the DEEP draws, deep_coin_block).
 // All arithmetic is 64-bit Goldilocks integer work: HBM/VALU bound, no MFMA.
 #include "dev_coin.hpp"
+#include "dispatch.hpp"
 #include "field_dft.hpp"
 #include "hip_util.hpp"
 #include <algorithm>
 #include <stdexcept>
 
 namespace xfg {
-
-#define XFG_CHECK_LAUNCH() (void)hipGetLastError()
 
 __device__ __forceinline__ u64 shfl_xor_u64(u64 v, int m, int w) {
     u32 lo = __shfl_xor((u32)v, m, w), hi = __shfl_xor((u32)(v >> 32), m, w);
@@ -127,17 +126,14 @@ void launch_constraint_eval(const u64* lde, const AirConst* air, const u64* coef
     u64 nce = 2ULL << logn;
     int threads = nce < 256 ? (int)nce : 256;
     dim3 g((unsigned)(nce / threads), npoly);
-    if (cc.flags) {
-        const dim3 gu((unsigned)((npoly + 63) / 64));
-        if (ext == 2) hipLaunchKernelGGL(ce_uniform_kernel<2>, gu, dim3(64), 0, s, air, coeffs, cc, uni, npoly);
-        else hipLaunchKernelGGL(ce_uniform_kernel<1>, gu, dim3(64), 0, s, air, coeffs, cc, uni, npoly);
-        if (ext == 2) hipLaunchKernelGGL((constraint_eval_kernel<2, true>), g, dim3(threads), 0, s, a);
-        else hipLaunchKernelGGL((constraint_eval_kernel<1, true>), g, dim3(threads), 0, s, a);
-    } else {
-        if (ext == 2) hipLaunchKernelGGL((constraint_eval_kernel<2, false>), g, dim3(threads), 0, s, a);
-        else hipLaunchKernelGGL((constraint_eval_kernel<1, false>), g, dim3(threads), 0, s, a);
-    }
-    XFG_CHECK_LAUNCH();
+    with_ext(ext, [&](auto D) {
+        with_bool(cc.flags != nullptr, [&](auto CC) {
+            if constexpr (CC)
+                XFG_LAUNCH(ce_uniform_kernel<D>, dim3((unsigned)((npoly + 63) / 64)), dim3(64), 0, s, air, coeffs, cc, uni,
+                           npoly);
+            XFG_LAUNCH((constraint_eval_kernel<D, CC>), g, dim3(threads), 0, s, a);
+        });
+    });
 }
 
 // Trace::validate (winter-air 0.8) on the device: one thread per step reads its row (seven coalesced
@@ -205,9 +201,7 @@ void launch_trace_check(u64* trace, const AirConst* air, u64* keys, int logn, in
     const u64 n = 1ULL << logn;
     HIPCHK(hipMemsetAsync(keys, 0xFF, (size_t)npoly * 8, s));  // TRACE_KEY_VALID
     dim3 g((unsigned)((n + 255) / 256), npoly);
-    if (with_air) hipLaunchKernelGGL(trace_check_kernel<true>, g, dim3(256), 0, s, trace, air, keys, logn);
-    else hipLaunchKernelGGL(trace_check_kernel<false>, g, dim3(256), 0, s, trace, air, keys, logn);
-    XFG_CHECK_LAUNCH();
+    with_bool(with_air, [&](auto AIR) { XFG_LAUNCH(trace_check_kernel<AIR>, g, dim3(256), 0, s, trace, air, keys, logn); });
 }
 
 // ============================================================================ OOD
@@ -419,15 +413,12 @@ void launch_ood(const u64* coef, const u64* hcoef, const u64* zpts, u64* partial
     const u64 n = 1ULL << logn;
     const int T = ood_threads(n), nblk = (int)(n / ((u64)T * OOD_R));
     const dim3 g(nblk, npoly), b(T);
-    if (cc.flags) {
-        if (ext == 2) hipLaunchKernelGGL((ood_kernel<2, true>), g, b, 0, s, coef, hcoef, zpts, partial, logn, cc);
-        else hipLaunchKernelGGL((ood_kernel<1, true>), g, b, 0, s, coef, hcoef, zpts, partial, logn, cc);
-    } else {
-        if (ext == 2) hipLaunchKernelGGL((ood_kernel<2, false>), g, b, 0, s, coef, hcoef, zpts, partial, logn, cc);
-        else hipLaunchKernelGGL((ood_kernel<1, false>), g, b, 0, s, coef, hcoef, zpts, partial, logn, cc);
-    }
-    hipLaunchKernelGGL(ood_final_kernel, dim3(npoly), dim3(dc.coins ? 128 : 64), 0, s, partial, nblk, ext, ood, dc);
-    XFG_CHECK_LAUNCH();
+    with_ext(ext, [&](auto D) {
+        with_bool(cc.flags != nullptr, [&](auto CC) {
+            XFG_LAUNCH((ood_kernel<D, CC>), g, b, 0, s, coef, hcoef, zpts, partial, logn, cc);
+        });
+    });
+    XFG_LAUNCH(ood_final_kernel, dim3(npoly), dim3(dc.coins ? 128 : 64), 0, s, partial, nblk, ext, ood, dc);
 }
 u64 ood_partial_count(int logn) {
     const u64 n = 1ULL << logn;
@@ -619,16 +610,12 @@ void launch_deep(const u64* coef, const u64* hcoef, const DeepParams* dp, const 
     int ct = 64;
     while (ct < nblk) ct <<= 1;  // nblk <= 1024 (n <= 2^21, 2048 coefficients per block)
     const dim3 g(nblk, npoly), b(T);
-    if (ext == 2) hipLaunchKernelGGL(deep_carry_kernel<2>, dim3(npoly), dim3(ct), 0, s, partial, dp, carry, nblk, logch);
-    else hipLaunchKernelGGL(deep_carry_kernel<1>, dim3(npoly), dim3(ct), 0, s, partial, dp, carry, nblk, logch);
-    if (cc.flags) {
-        if (ext == 2) hipLaunchKernelGGL((deep_final_kernel<2, true>), g, b, 0, s, coef, hcoef, dp, carry, deep, logn, cc);
-        else hipLaunchKernelGGL((deep_final_kernel<1, true>), g, b, 0, s, coef, hcoef, dp, carry, deep, logn, cc);
-    } else {
-        if (ext == 2) hipLaunchKernelGGL((deep_final_kernel<2, false>), g, b, 0, s, coef, hcoef, dp, carry, deep, logn, cc);
-        else hipLaunchKernelGGL((deep_final_kernel<1, false>), g, b, 0, s, coef, hcoef, dp, carry, deep, logn, cc);
-    }
-    XFG_CHECK_LAUNCH();
+    with_ext(ext, [&](auto D) {
+        XFG_LAUNCH(deep_carry_kernel<D>, dim3(npoly), dim3(ct), 0, s, partial, dp, carry, nblk, logch);
+        with_bool(cc.flags != nullptr, [&](auto CC) {
+            XFG_LAUNCH((deep_final_kernel<D, CC>), g, b, 0, s, coef, hcoef, dp, carry, deep, logn, cc);
+        });
+    });
 }
 
 // ============================================================================ FRI fold
@@ -688,16 +675,6 @@ __global__ __launch_bounds__(256) void fri_fold_kernel(FoldArgs a) {
 #pragma unroll
     for (int c = 0; c < D; c++) a.out[((u64)proof * D + c) * a.out_stride + i] = r.c(c);
 }
-template <int D>
-static void fold_launch(int fold, dim3 g, dim3 b, hipStream_t s, const FoldArgs& a) {
-    switch (fold) {
-        case 2: hipLaunchKernelGGL((fri_fold_kernel<D, 1>), g, b, 0, s, a); break;
-        case 4: hipLaunchKernelGGL((fri_fold_kernel<D, 2>), g, b, 0, s, a); break;
-        case 8: hipLaunchKernelGGL((fri_fold_kernel<D, 3>), g, b, 0, s, a); break;
-        case 16: hipLaunchKernelGGL((fri_fold_kernel<D, 4>), g, b, 0, s, a); break;
-        default: throw std::invalid_argument("FRI fold: no kernel for this folding factor");
-    }
-}
 void launch_fri_fold(const u64* vals, u64 val_stride, u64 comp_stride, bool coset_major, int logn, int logbeta,
                      u64 rows, int logD, const u64* alpha7, u64* out, u64 out_stride, const Tables& T, int npoly,
                      int ext, int fold, hipStream_t s) {
@@ -708,9 +685,9 @@ void launch_fri_fold(const u64* vals, u64 val_stride, u64 comp_stride, bool cose
     a.T = T;
     int threads = rows < 256 ? (int)rows : 256;
     dim3 g((unsigned)((rows + threads - 1) / threads), npoly);
-    if (ext == 2) fold_launch<2>(fold, g, dim3(threads), s, a);
-    else fold_launch<1>(fold, g, dim3(threads), s, a);
-    XFG_CHECK_LAUNCH();
+    with_ext(ext, [&](auto D) {
+        with_fold(fold, [&](auto LOGF) { XFG_LAUNCH((fri_fold_kernel<D, LOGF>), g, dim3(threads), 0, s, a); });
+    });
 }
 
 // ============================================================================ gathers
@@ -741,8 +718,7 @@ __global__ void gather_set_kernel(GatherSet g, const u64* idx) {
 void launch_gather_set(const GatherSet& g, const u64* idx, hipStream_t s) {
     const u64 total = g.first[g.nseg];
     if (!total) return;
-    hipLaunchKernelGGL(gather_set_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, g, idx);
-    XFG_CHECK_LAUNCH();
+    XFG_LAUNCH(gather_set_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, g, idx);
 }
 
 // one segment per blockIdx.y, grid-stride over its words
@@ -758,8 +734,7 @@ void launch_pack(const PackSet& p, void* dst, hipStream_t s) {
     for (int k = 0; k < p.nseg; k++) most = std::max(most, p.words[k]);
     if (!most) return;
     const unsigned bx = (unsigned)std::min<u64>(32, (most + 255) / 256);
-    hipLaunchKernelGGL(pack_kernel, dim3(bx, p.nseg), dim3(256), 0, s, p, (u32*)dst);
-    XFG_CHECK_LAUNCH();
+    XFG_LAUNCH(pack_kernel, dim3(bx, p.nseg), dim3(256), 0, s, p, (u32*)dst);
 }
 
 }  // namespace xfg

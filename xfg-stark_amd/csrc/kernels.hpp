@@ -1,5 +1,7 @@
 // Launch wrappers for the burn-proof STARK kernels (gfx950). Every wrapper enqueues on the given
-// stream and never synchronises; batch dimension = number of independent proofs.
+// stream and never synchronises; batch dimension = number of independent proofs. A wrapper throws
+// std::invalid_argument for an ext outside {1, 2}, a fold outside {2, 4, 8, 16} or an LDE shape without a kernel
+// (dispatch.hpp), and HipError naming the kernel when the runtime refuses a launch (hip_util.hpp XFG_LAUNCH).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "gl.hpp"

@@ -15,13 +15,13 @@
 //   LDE leaves   n >= ROW2_MIN_N and npoly n / 256 < ROW2_MAX_BLOCKS: leaves_row2_kernel, else leaves_row_kernel
 //   middle       (count / 512) npoly < MID4_MAX_BLOCKS: tree_mid4_kernel, else tree_mid_kernel
 #include "dev_coin.hpp"
+#include "dispatch.hpp"
+#include "hip_util.hpp"
 #include <algorithm>
 #include <stdexcept>
 #include <type_traits>
 
 namespace xfg {
-
-#define XFG_CHECK_LAUNCH() (void)hipGetLastError()
 
 // ---- routing thresholds
 // leaves_row2_kernel (LEAF_LANES lanes per row) serves small launch sets, under one wave per SIMD of
@@ -290,58 +290,25 @@ __global__ __launch_bounds__(64) void open_rows_kernel(const u64* lde, const u64
     }
 }
 
-// The one (columns, log2 blowup) dispatch of the three kernel families above: f(NC, LOGB) with both as
-// integral constants, for nc in {7, 2, 1} and blowup 2..128. Any other pair has no kernel: refused,
-// never skipped (the ABI entries validate both before anything is launched).
-template <int V>
-using IntC = std::integral_constant<int, V>;
-template <int NC, class F>
-static bool with_logbeta(int logbeta, F f) {
-    switch (logbeta) {
-        case 1: f(IntC<NC>{}, IntC<1>{}); return true;
-        case 2: f(IntC<NC>{}, IntC<2>{}); return true;
-        case 3: f(IntC<NC>{}, IntC<3>{}); return true;
-        case 4: f(IntC<NC>{}, IntC<4>{}); return true;
-        case 5: f(IntC<NC>{}, IntC<5>{}); return true;
-        case 6: f(IntC<NC>{}, IntC<6>{}); return true;
-        case 7: f(IntC<NC>{}, IntC<7>{}); return true;
-        default: return false;
-    }
-}
+// The one dispatch of the three kernel families above: f(NC, LOGB, CC) as integral constants
+// (dispatch.hpp), for nc in {7, 2, 1} and blowup 2..128; with constant columns the CC instantiations,
+// which exist for the seven trace columns alone. Anything else has no kernel: refused, never skipped
+// (the ABI entries validate both before anything is launched).
 template <class F>
-static void with_nc_logbeta(int nc, int logbeta, F f) {
-    const bool found = nc == 7   ? with_logbeta<7>(logbeta, f)
-                       : nc == 2 ? with_logbeta<2>(logbeta, f)
-                       : nc == 1 ? with_logbeta<1>(logbeta, f)
-                                 : false;
-    if (!found) throw std::invalid_argument("Merkle kernels: no instantiation for this column count and blowup");
-}
-
-// with constant columns: the CC instantiations, which exist for the seven trace columns alone
-static void require_trace_width(int nc, const ColConst& cc) {
+static void with_lde_kernel(int nc, int logbeta, const ColConst& cc, F f) {
     if (cc.flags && nc != 7) throw std::invalid_argument("Merkle kernels: constant columns are those of a 7-column trace LDE");
-}
-template <class F>
-static void with_const_logbeta(int logbeta, F f) {
-    if (!with_logbeta<7>(logbeta, f))
-        throw std::invalid_argument("Merkle kernels: no instantiation for this column count and blowup");
+    if (cc.flags) with_logbeta<7>(logbeta, [&](auto NC, auto LB) { f(NC, LB, std::true_type{}); });
+    else with_nc_logbeta(nc, logbeta, [&](auto NC, auto LB) { f(NC, LB, std::false_type{}); });
 }
 
 void launch_open_rows(const u64* lde, int nc, const u64* entries, u64 count, Digest* out, int logn, int logbeta,
                       hipStream_t s, const ColConst& cc) {
     if (!count) return;
-    require_trace_width(nc, cc);
     const int logl = logbeta < 6 ? logbeta : 6;  // lanes per entry (open_lanes_log)
     dim3 g((unsigned)(((count << logl) + 63) / 64)), b(64);
-    if (cc.flags)
-        with_const_logbeta(logbeta, [&](auto NC, auto LB) {
-            hipLaunchKernelGGL((open_rows_kernel<decltype(NC)::value, decltype(LB)::value, true>), g, b, 0, s, lde, entries, count, out, logn, cc);
-        });
-    else
-        with_nc_logbeta(nc, logbeta, [&](auto NC, auto LB) {
-            hipLaunchKernelGGL((open_rows_kernel<decltype(NC)::value, decltype(LB)::value, false>), g, b, 0, s, lde, entries, count, out, logn, cc);
-        });
-    XFG_CHECK_LAUNCH();
+    with_lde_kernel(nc, logbeta, cc, [&](auto NC, auto LB, auto CC) {
+        XFG_LAUNCH((open_rows_kernel<NC, LB, CC>), g, b, 0, s, lde, entries, count, out, logn, cc);
+    });
 }
 
 // ============================================================================ transcript step
@@ -417,49 +384,29 @@ __global__ __launch_bounds__(256) void tree_mid4_kernel(Digest* nodes_all, u64 n
 static void finish_tree(Digest* nodes, u64 node_stride, u64 count, int npoly, hipStream_t s, const CoinStep& cs) {
     while (count > TREE_TOP_MAX) {
         if ((count / 512) * (u64)npoly < MID4_MAX_BLOCKS)
-            hipLaunchKernelGGL(tree_mid4_kernel, dim3((unsigned)(count / 128), npoly), dim3(256), 0, s, nodes,
-                               node_stride, count);
+            XFG_LAUNCH(tree_mid4_kernel, dim3((unsigned)(count / 128), npoly), dim3(256), 0, s, nodes, node_stride, count);
         else
-            hipLaunchKernelGGL(tree_mid_kernel, dim3((unsigned)(count / 512), npoly), dim3(256), 0, s, nodes,
-                               node_stride, count);
+            XFG_LAUNCH(tree_mid_kernel, dim3((unsigned)(count / 512), npoly), dim3(256), 0, s, nodes, node_stride, count);
         count /= TREE_MID_SHRINK;
     }
     if (count > 1 || cs.kind != CoinStep::NONE) {
         int threads = (int)(2 * count);  // four lanes per node of the widest level
         threads = threads < 64 ? 64 : threads;
-        hipLaunchKernelGGL(tree_top_kernel, dim3(npoly), dim3(threads), 0, s, nodes, node_stride, count, cs);
+        XFG_LAUNCH(tree_top_kernel, dim3(npoly), dim3(threads), 0, s, nodes, node_stride, count, cs);
     }
-    XFG_CHECK_LAUNCH();
 }
 
 void launch_merkle_lde(const u64* lde, int nc, Digest* nodes, int npoly, int logn, int logbeta, hipStream_t s,
                        const CoinStep& cs, const ColConst& cc) {
     const u64 n = 1ULL << logn, node_stride = 2 * n;
-    require_trace_width(nc, cc);
-    if (n >= ROW2_MIN_N && (u64)npoly * (n / 256) < ROW2_MAX_BLOCKS) {  // under one wave per SIMD
-        const int logl = logbeta < LEAF_LANES_LOG ? logbeta : LEAF_LANES_LOG;
-        dim3 g((unsigned)(n >> (8 - logl)), npoly), b(256);
-        if (cc.flags)
-            with_const_logbeta(logbeta, [&](auto NC, auto LB) {
-                hipLaunchKernelGGL((leaves_row2_kernel<decltype(NC)::value, decltype(LB)::value, true>), g, b, 0, s, lde, nodes, node_stride, logn, cc);
-            });
-        else
-            with_nc_logbeta(nc, logbeta, [&](auto NC, auto LB) {
-                hipLaunchKernelGGL((leaves_row2_kernel<decltype(NC)::value, decltype(LB)::value, false>), g, b, 0, s, lde, nodes, node_stride, logn, cc);
-            });
-    } else {
-        const unsigned T = (unsigned)std::min<u64>(256, n);
-        dim3 g((unsigned)(n / T), npoly), b(T);
-        if (cc.flags)
-            with_const_logbeta(logbeta, [&](auto NC, auto LB) {
-                hipLaunchKernelGGL((leaves_row_kernel<decltype(NC)::value, decltype(LB)::value, true>), g, b, 0, s, lde, nodes, node_stride, logn, cc);
-            });
-        else
-            with_nc_logbeta(nc, logbeta, [&](auto NC, auto LB) {
-                hipLaunchKernelGGL((leaves_row_kernel<decltype(NC)::value, decltype(LB)::value, false>), g, b, 0, s, lde, nodes, node_stride, logn, cc);
-            });
-    }
-    XFG_CHECK_LAUNCH();
+    const bool row2 = n >= ROW2_MIN_N && (u64)npoly * (n / 256) < ROW2_MAX_BLOCKS;  // under one wave per SIMD
+    const int logl = logbeta < LEAF_LANES_LOG ? logbeta : LEAF_LANES_LOG;
+    const unsigned T = (unsigned)std::min<u64>(256, n);
+    const dim3 g(row2 ? (unsigned)(n >> (8 - logl)) : (unsigned)(n / T), npoly), b(row2 ? 256 : T);
+    with_lde_kernel(nc, logbeta, cc, [&](auto NC, auto LB, auto CC) {
+        if (row2) XFG_LAUNCH((leaves_row2_kernel<NC, LB, CC>), g, b, 0, s, lde, nodes, node_stride, logn, cc);
+        else XFG_LAUNCH((leaves_row_kernel<NC, LB, CC>), g, b, 0, s, lde, nodes, node_stride, logn, cc);
+    });
     finish_tree(nodes, node_stride, n / 4, npoly, s, cs);  // both leaf kernels: the row level and two more
 }
 
@@ -487,34 +434,17 @@ __global__ __launch_bounds__(256) void fri_leaves_kernel(const u64* vals, u64 va
     nodes[rows + i] = d;
     block_tree_up(d, nodes, rows, lds, wmin);
 }
-// f(D, LOGF) as integral constants for ext in {1, 2} and folding factor 2, 4, 8, 16; any other pair has
-// no kernel: refused, never skipped
-template <class F>
-static void with_ext_fold(int ext, int fold, F f) {
-    const int logf = fold == 2 ? 1 : fold == 4 ? 2 : fold == 8 ? 3 : fold == 16 ? 4 : 0;
-    if ((ext != 1 && ext != 2) || !logf)
-        throw std::invalid_argument("FRI leaf kernel: no instantiation for this extension degree and folding factor");
-    auto by_fold = [&](auto DC) {
-        switch (logf) {
-            case 1: f(DC, IntC<1>{}); break;
-            case 2: f(DC, IntC<2>{}); break;
-            case 3: f(DC, IntC<3>{}); break;
-            default: f(DC, IntC<4>{}); break;
-        }
-    };
-    if (ext == 2) by_fold(IntC<2>{});
-    else by_fold(IntC<1>{});
-}
 void launch_merkle_fri(const u64* vals, u64 val_stride, u64 comp_stride, bool coset_major, int logn, int logbeta,
                        u64 rows, Digest* nodes, int npoly, int ext, int fold, hipStream_t s, const CoinStep& cs) {
     const u64 T = std::min<u64>(256, rows), node_stride = 2 * rows;
     const int wmin = (int)std::min<u64>(T, UP_WMIN);
     dim3 g((unsigned)(rows / T), npoly);
-    with_ext_fold(ext, fold, [&](auto DC, auto LF) {
-        hipLaunchKernelGGL((fri_leaves_kernel<decltype(DC)::value, decltype(LF)::value>), g, dim3((unsigned)T), 0, s, vals,
-                           val_stride, comp_stride, coset_major ? 1 : 0, logn, logbeta, rows, nodes, node_stride, wmin);
+    with_ext(ext, [&](auto D) {  // ext in {1, 2}, fold in {2, 4, 8, 16}: anything else is refused
+        with_fold(fold, [&](auto LOGF) {
+            XFG_LAUNCH((fri_leaves_kernel<D, LOGF>), g, dim3((unsigned)T), 0, s, vals, val_stride, comp_stride,
+                       coset_major ? 1 : 0, logn, logbeta, rows, nodes, node_stride, wmin);
+        });
     });
-    XFG_CHECK_LAUNCH();
     finish_tree(nodes, node_stride, rows / T * wmin, npoly, s, cs);
 }
 

@@ -855,9 +855,10 @@ __global__ __launch_bounds__(1 << LOGT, MINW) void ntt_pass_b_pers(NttArgs a, in
 struct NttEntry {
     NttKey key;
     const void* fn;
+    const char* name;
     std::atomic<bool> big_lds;  // the opt-in for more than 64 KiB of dynamic LDS has been made (and has returned)
 };
-#define XFG_NTT_ENTRY(K, SYM, S, INV, T, E) {{NttKernel::K, S, T, E, INV}, (const void*)SYM},
+#define XFG_NTT_ENTRY(K, SYM, S, INV, T, E) {{NttKernel::K, S, T, E, INV}, (const void*)SYM, #SYM},
 static NttEntry ntt_entries[] = {XFG_NTT_KERNELS(XFG_NTT_ENTRY)};
 #undef XFG_NTT_ENTRY
 
@@ -870,7 +871,7 @@ static void ntt_launch(const NttPass& p, void** args, hipStream_t s) {
             HIPCHK(hipFuncSetAttribute(e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             e.big_lds.store(true, std::memory_order_release);
         }
-        HIPCHK(hipLaunchKernel(e.fn, dim3(p.gx, p.gy), dim3(p.block), args, p.lds, s));
+        launch_checked(e.name, e.fn, dim3(p.gx, p.gy), dim3(p.block), args, p.lds, s);
         return;
     }
     throw std::runtime_error("NTT: planned kernel is not in the kernel list");
@@ -918,8 +919,8 @@ void launch_lde(const u64* coef, u64 coef_stride, u64* out, u64* scratch, int np
     u64* twisted = scratch + lp.twist_off;
     if (lp.groups > 1) {
         if (T.LM < logn + logbeta) throw std::runtime_error("forward LDE: the root-of-unity table is smaller than the LDE domain");
-        hipLaunchKernelGGL(lde_twist_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)npoly, (unsigned)(lp.groups - 1)), dim3(256),
-                           0, s, coef, coef_stride, twisted, logn, logn + logbeta, skip, T);
+        XFG_LAUNCH(lde_twist_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)npoly, (unsigned)(lp.groups - 1)), dim3(256), 0,
+                   s, coef, coef_stride, twisted, logn, logn + logbeta, skip, T);
     }
     const TableKind k = T.fs ? table_kind(logn, lb) : TableKind::none;
     for (int u = 0; u < lp.groups; u++) {

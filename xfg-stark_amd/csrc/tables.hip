@@ -140,13 +140,13 @@ __global__ void pass_tables_kernel(u64* out, PassTableLayout L, Tables T) {
 // the pass tables alone (forward, for sizes without a four-step table; pass_tables_size entries)
 static void build_pass_tables(u64* out, int logn, int logbeta, const Tables& T, hipStream_t s) {
     const PassTableLayout L = pass_table_layout(logn, logbeta);
-    hipLaunchKernelGGL(pass_tables_kernel, dim3((unsigned)((L.total() + 255) / 256)), dim3(256), 0, s, out, L, T);
+    XFG_LAUNCH(pass_tables_kernel, dim3((unsigned)((L.total() + 255) / 256)), dim3(256), 0, s, out, L, T);
 }
 // the four-step table with its pass tables behind it (fourstep_size entries)
 static void build_fourstep(u64* out, int logn, int logbeta, const Tables& T, hipStream_t s) {
     const u64 cnt = fourstep_main(logn, logbeta);
-    hipLaunchKernelGGL(fourstep_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, out, logn, logbeta,
-                       pass_table_layout(logn, logbeta).logC, gl_inv(1ULL << logn), T);
+    XFG_LAUNCH(fourstep_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, out, logn, logbeta,
+               pass_table_layout(logn, logbeta).logC, gl_inv(1ULL << logn), T);
     build_pass_tables(out + cnt, logn, logbeta, T, s);
 }
 // four-step twiddle tables of the NTT sizes one (n, beta) proof uses: the forward LDE and the

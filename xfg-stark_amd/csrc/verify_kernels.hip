@@ -3,8 +3,8 @@
 // out as flat task lists (verifier.cpp plan_proof); see xfg_verify_batch_gpu in verify_batch_gpu.hip.
 // Replaces the serial BatchBurnMintVerifier loops of the reference (src/burn_mint_verifier.rs:
 // 326-338, 386-408), each of which runs winterfell::verify on the CPU.
-#include <stdexcept>
-
+#include "dispatch.hpp"
+#include "hip_util.hpp"
 #include "verifier.hpp"
 
 namespace xfg {
@@ -149,16 +149,9 @@ static unsigned blocks_for(u64 n, unsigned t) { return (unsigned)((n + t - 1) / 
 
 void launch_verify(const uint8_t* blob, const VTree* trees, u64 ntrees, const VTreeLeaf* tleaves, const VVec* vecs,
                    const VFieldProof* fp, const VFieldQuery* fq, u64 nq, int fold, u64* flags, hipStream_t s) {
-    if (ntrees) hipLaunchKernelGGL(vtree_kernel, dim3((unsigned)ntrees), dim3(256), 0, s, blob, trees, tleaves, vecs, flags);
+    if (ntrees) XFG_LAUNCH(vtree_kernel, dim3((unsigned)ntrees), dim3(256), 0, s, blob, trees, tleaves, vecs, flags);
     const dim3 g(blocks_for(nq, 64)), b(64);
-    if (nq) switch (fold) {
-        case 2: hipLaunchKernelGGL(vfield_kernel<1>, g, b, 0, s, blob, fp, fq, nq, flags); break;
-        case 4: hipLaunchKernelGGL(vfield_kernel<2>, g, b, 0, s, blob, fp, fq, nq, flags); break;
-        case 8: hipLaunchKernelGGL(vfield_kernel<3>, g, b, 0, s, blob, fp, fq, nq, flags); break;
-        case 16: hipLaunchKernelGGL(vfield_kernel<4>, g, b, 0, s, blob, fp, fq, nq, flags); break;
-        default: throw std::invalid_argument("batch verifier: no kernel for this folding factor");
-    }
-    (void)hipGetLastError();
+    if (nq) with_fold(fold, [&](auto LOGF) { XFG_LAUNCH(vfield_kernel<LOGF>, g, b, 0, s, blob, fp, fq, nq, flags); });
 }
 
 }  // namespace xfg
