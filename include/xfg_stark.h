@@ -185,6 +185,36 @@ int xfg_prove_trace_batch_submit(xfg_ctx* ctx, uint32_t count, const uint64_t* t
                                  uint8_t* const* outs, size_t* out_lens, int* statuses, xfg_trace_fault* faults,
                                  uint64_t* ticket);
 
+/* ---- the same three entries for traces in any strided layout, row-major included ----
+ * where cell (trace i, column c, step s) lies: traces[i*trace_stride + c*col_stride + s*row_stride], in
+ * 8-byte words. Any values, 0 included (a broadcast view); the cells may overlap, they are only read.
+ * dense column-major = {7n, n, 1}; row-major = {7n, 1, 7}; rows padded to 8 words = {8n, 1, 8} */
+typedef struct { uint64_t trace_stride, col_stride, row_stride; } xfg_trace_layout;
+
+/* Each returns what its namesake without _strided returns on the dense array M[i][c][s] = the cell the layout
+ * names (there is no width argument: a layout names seven columns): return value, statuses, out_lens, faults,
+ * proof bytes and the xfg_last_error text; `found` of a fault is read from the caller's buffer through the
+ * layout. Flags, limits and the pending-batch rule are those of the namesake. layout == NULL, or the dense
+ * layout spelled out, is the namesake itself.
+ * Device traces in another layout are not copied: one pass over the caller's buffer checks them and
+ * classifies their columns, a second writes the columns that need a transform into the lane's workspace.
+ * Host traces in another layout are checked through the strides and gathered into the lanes' pinned staging.
+ * Refused with XFG_INVALID_ARGUMENT, nothing launched: what the namesake refuses; an extent -- the words from
+ * the first cell to the last, (count-1)*trace_stride + 6*col_stride + (n-1)*row_stride + 1 -- that overflows
+ * 64 bits or is above 2^58; for device traces an extent past the end of the allocation */
+int xfg_check_traces_strided(xfg_ctx* ctx, uint32_t count, const uint64_t* traces, uint64_t n,
+                             const xfg_trace_layout* layout, const xfg_air_consts* airs, uint32_t flags,
+                             xfg_trace_fault* faults);
+int xfg_prove_trace_batch_strided(xfg_ctx* ctx, uint32_t count, const uint64_t* traces, uint64_t n,
+                                  const xfg_trace_layout* layout, const xfg_air_consts* airs, const xfg_options* opts,
+                                  uint32_t flags, uint8_t* const* outs, size_t* out_lens, int* statuses,
+                                  xfg_trace_fault* faults);
+/* waited for with xfg_batch_wait(ticket) */
+int xfg_prove_trace_batch_strided_submit(xfg_ctx* ctx, uint32_t count, const uint64_t* traces, uint64_t n,
+                                         const xfg_trace_layout* layout, const xfg_air_consts* airs,
+                                         const xfg_options* opts, uint32_t flags, uint8_t* const* outs,
+                                         size_t* out_lens, int* statuses, xfg_trace_fault* faults, uint64_t* ticket);
+
 /* allocate every device / pinned-host workspace and load all code objects for batches of
  * `count` proofs of this shape (setup, not a prove; later calls never allocate) */
 int xfg_prepare(xfg_ctx* ctx, uint32_t count, uint64_t trace_length, const xfg_options* opts);
@@ -292,6 +322,21 @@ typedef struct xfg_probe_pattern {
 int xfg_debug_trace_probe(xfg_ctx* ctx, uint32_t count, uint64_t n, const xfg_air_consts* airs, uint32_t generator,
                           const xfg_probe_pattern* pattern, uint8_t* classes_out, uint64_t* vals_out,
                           uint64_t* trace_out);
+/* the front end of a unit of `count` device traces in a strided layout as the prover's chain runs it, without
+ * the transforms: buf (host memory, buf_words words) is uploaded as it is into a device buffer of exactly that
+ * size, the lane's trace buffer [count][7][n] is set to 0xFF bytes, and the two ingest launches run on lane 0:
+ * one pass over the buffer for the check's words and the column classes, one that writes the canonical live
+ * columns. The hook always takes these kernels, for the dense layout and layout == NULL (dense) too.
+ * validate != 0: the AIR's assertions and constraints are checked besides the canonicity of the cells.
+ * classes_out and vals_out [count][7] as for xfg_debug_col_classes (on the canonical cells); faults_out [count]
+ * as xfg_check_traces_strided fills them (`found` read from buf through the layout); trace_out [count][7][n]: the
+ * buffer as left, the planes of constant (1) and shared (2) columns still 0xFF bytes.
+ * Refused with XFG_INVALID_ARGUMENT: a null pointer (layout excepted), count 0 or count * 7 > 65535, n no power
+ * of two in [8, 2^24], an AIR constant that is not canonical, an extent that overflows, is above 2^58 or
+ * above buf_words */
+int xfg_debug_trace_ingest(xfg_ctx* ctx, uint32_t count, uint64_t n, const uint64_t* buf, uint64_t buf_words,
+                           const xfg_trace_layout* layout, const xfg_air_consts* airs, int validate,
+                           uint8_t* classes_out, uint64_t* vals_out, xfg_trace_fault* faults_out, uint64_t* trace_out);
 /* xfg_debug_lde / xfg_debug_interpolate with a caller-supplied flag vector skip [npoly]: polynomials
  * with a non-zero flag take no transform and are filled in as constants (coefficient / evaluation 0 of
  * the input is the value), as the prover does for the columns it detects. The caller vouches that a

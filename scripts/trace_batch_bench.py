@@ -7,13 +7,19 @@ bench.py keeps them:
   c  prove_traces from a device tensor
   cv c with validate=True (XFG_TRACE_VALIDATE)
   d  prove_batch on the same inputs (traces generated on the device): the ceiling
+  e1 the traces held on the device as rows [64][2^16][7]: permute(0, 2, 1).contiguous() inside the timed loop
+     (a second copy of the traces, a temporary of 64 x 7 x 2^16 x 8 bytes per batch), then submit_traces: what
+     a producer of rows has to do with a library that takes the dense layout only
+  e2 the same rows passed as the view rows.permute(0, 2, 1): read where they lie (xfg_prove_trace_batch_strided);
+     left out when the library loaded through XFG_LIB has no such entry
 
 The modes alternate `rounds` times in one process on one card; one JSON line per mode and round, then a
 summary line per mode (median, min, max proofs/s). Then, in timing mode (one 64-proof unit, HIP events
 around the stages), the first stage -- upload, check, interpolation and LDE of the trace -- of c and of
 cv: their difference is the check kernel's time for 64 traces.
 
-usage: python3 scripts/trace_batch_bench.py [batches per round, default 24] [rounds, 3] [depth, 6]"""
+usage: python3 scripts/trace_batch_bench.py [batches per round, default 24] [rounds, 3] [depth, 6]
+                                            [modes, comma-separated first letters, default all: a,b,c,cv,d,e1,e2]"""
 import collections
 import json
 import os
@@ -65,11 +71,14 @@ def main():
     batches = int(sys.argv[1]) if len(sys.argv) > 1 else 24
     rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 3
     depth = int(sys.argv[3]) if len(sys.argv) > 3 else 6
+    only = sys.argv[4].split(",") if len(sys.argv) > 4 else None
+    strided = "xfg_prove_trace_batch_strided_submit" not in xfgstark._abi.MISSING
     pr = xfgstark.XfgBurnMintProver()
     inputs = [synthetic.burn_inputs(i) for i in range(COUNT)]
     airs = [xfgstark.air_consts(**kw) for kw in inputs]
     host = build_traces(airs)
     dev = torch.from_numpy(host.view(np.int64)).to("cuda:0")
+    rows = dev.permute(0, 2, 1).contiguous()  # [64][2^16][7], as a step function writes them
     torch.cuda.synchronize()
     assert pr.check_traces(dev, airs) == [None] * COUNT
     pr.prepare(COUNT, N, buffers=depth + 1)
@@ -86,18 +95,31 @@ def main():
         ("c_device_tensor", lambda: pipelined(lambda: pr.submit_traces(dev, airs), batches, depth)),
         ("cv_device_validate", lambda: pipelined(lambda: pr.submit_traces(dev, airs, validate=True), batches, depth)),
         ("d_prove_batch", lambda: pipelined(lambda: pr.submit_batch(inputs, N), batches, depth)),
+        ("e1_rows_permute_copy", lambda: pipelined(lambda: pr.submit_traces(rows.permute(0, 2, 1).contiguous(), airs),
+                                                   batches, depth)),
+        ("e2_rows_view", lambda: pipelined(lambda: pr.submit_traces(rows.permute(0, 2, 1), airs), batches, depth)),
     ])
+    if not strided:
+        del modes["e2_rows_view"]
+    if only:
+        modes = collections.OrderedDict((k, v) for k, v in modes.items() if k.split("_")[0] in only)
     # the same proofs whichever way the traces arrive
     want = [p.to_bytes() for p in pr.prove_batch(inputs, N)]
     for how in (host, dev):
         for validate in (False, True):
             assert [p.to_bytes() for p in pr.prove_traces(how, airs, validate=validate)] == want
+    assert [p.to_bytes() for p in pr.prove_traces(rows.permute(0, 2, 1).contiguous(), airs)] == want
+    if strided:
+        for validate in (False, True):
+            assert [p.to_bytes() for p in pr.prove_traces(rows.permute(0, 2, 1), airs, validate=validate)] == want
     pr.prepare(COUNT, N)  # the context has seen host traces: the lanes' pinned staging is sized now
     for name, run in modes.items():  # warm every path once
         run() if name.startswith("a_") else pipelined(
             {"b": lambda: pr.submit_traces(host, airs), "c": lambda: pr.submit_traces(dev, airs),
              "cv": lambda: pr.submit_traces(dev, airs, validate=True),
-             "d": lambda: pr.submit_batch(inputs, N)}[name.split("_")[0]], depth + 1, depth)
+             "d": lambda: pr.submit_batch(inputs, N),
+             "e1": lambda: pr.submit_traces(rows.permute(0, 2, 1).contiguous(), airs),
+             "e2": lambda: pr.submit_traces(rows.permute(0, 2, 1), airs)}[name.split("_")[0]], depth + 1, depth)
     rates = collections.defaultdict(list)
     for r in range(rounds):
         for name, run in modes.items():
@@ -109,9 +131,13 @@ def main():
                           "max": round(max(v), 1), "batches": 1 if name.startswith("a_") else batches,
                           "depth": depth}), flush=True)
     bytes_per_batch = host.nbytes
-    print(json.dumps({"trace_bytes_per_batch": bytes_per_batch,
-                      "b_upload_GBps": round(statistics.median(rates["b_host_array"]) / COUNT * bytes_per_batch / 1e9, 2)}),
-          flush=True)
+    if "b_host_array" in rates:
+        print(json.dumps({"trace_bytes_per_batch": bytes_per_batch,
+                          "b_upload_GBps": round(statistics.median(rates["b_host_array"]) / COUNT * bytes_per_batch / 1e9, 2)}),
+              flush=True)
+    if only and not {"c", "cv"} <= set(only):
+        pr.close()
+        return
     # the check kernel's own time: stage 0 of one 64-proof unit with and without the check
     pr.set_timing(True)
     stage = {"c": [], "cv": []}

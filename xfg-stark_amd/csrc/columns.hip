@@ -1,4 +1,5 @@
-// The classes of a trace's columns: finding them, writing a generated trace's live ones (launches: columns.hpp).
+// The classes of a trace's columns: finding them, writing the live ones of a generated trace and of a trace that
+// lies in the caller's device memory in a strided layout (launches: columns.hpp).
 //
 // Constant columns: a column that holds one value v in every row interpolates to the constant v, and its
 // LDE is v at every point: such columns take no NTT. const_detect_kernel finds them in whatever trace arrives
@@ -165,6 +166,161 @@ void launch_trace_gen(const AirConst* air, int B, int logn, const unsigned char*
     const dim3 g((unsigned)(((1ULL << logn) + 255) / 256), B);
     with_row_gen(synth, [&](auto gen) {
         XFG_LAUNCH(trace_gen_kernel<decltype(gen)>, g, dim3(256), 0, s, gen, air, trace, flags, logn);
+    });
+}
+// ---- traces in the caller's device memory, in any layout (StridedRows, columns.hpp): read where they lie.
+// Two launches stand where the copy into c->trace, trace_check_kernel and const_detect_kernel stood.
+// Geometry of both: one thread per step, block (x, b) the steps [256 x, 256 x + 256) of proof b, like
+// trace_check_kernel. Two load shapes, chosen on the host and block-uniform:
+//   TILE = false  each thread loads its cells through the strides: right for every layout, coalesced when
+//                 row_stride is 1
+//   TILE = true   col_stride 1 and 7 <= row_stride <= 16: the block's rows are one contiguous run of words,
+//                 which the block loads with coalesced 8-byte loads (lane i at word i of the run; a base
+//                 that is only 8-byte aligned is as good as any) and of which it keeps the seven cells of
+//                 every row in LDS, 7 words apart whatever the pitch in memory: the pad words of a padded
+//                 row never reach a register that is used. A thread then reads its row with 8-byte LDS
+//                 reads; 7 is odd, so the 32 rows of a half wave fall on 32 different bank pairs
+//                 ((7 t) mod 32 is a permutation of the 64-bit banks). The run ends at the seventh cell of
+//                 the last row it needs, not at that row's pitch: the pad words behind the last row of a
+//                 buffer are outside the extent the library has checked.
+//                 LDS: (256 + 1) rows x 7 words = 14,392 bytes per block
+constexpr int INGEST_BLOCK = 256, INGEST_TILE_WORDS = (INGEST_BLOCK + 1) * 7;
+__device__ __forceinline__ u64 canonical_cell(u64 v, unsigned& bad, int c) {
+    if (v >= P) {
+        bad |= 1u << c;
+        v -= P;
+    }
+    return v;
+}
+// x = the seven cells of step s of `proof`, canonical, of which the generic form loads the columns of `live`
+// alone; returns bit c set where cell c was >= p. NEXT: nxt4 = the canonical cell [4][s + 1] below the last
+// step (the tile then holds one row more than the block has steps, except behind the last step), else 0.
+// Every thread of the block calls it, the threads past the last step too (they get zeros): the tile form
+// has two barriers, the first for the readers of what the tile held before
+template <bool TILE, bool NEXT>
+__device__ __forceinline__ unsigned ingest_row(const StridedRows& src, u64* tile, int proof, u64 s, u64 n, u64 (&x)[7],
+                                               u64& nxt4, unsigned live = 0x7F) {
+    u64 nx = 0;
+#pragma unroll
+    for (int c = 0; c < 7; c++) x[c] = 0;
+    if constexpr (TILE) {
+        const u64 s0 = (u64)blockIdx.x * INGEST_BLOCK, left = n - s0;  // the grid has no block past the last step
+        const unsigned rows = left > INGEST_BLOCK ? INGEST_BLOCK + (NEXT ? 1u : 0u) : (unsigned)left;
+        const unsigned rs = (unsigned)src.at.row_stride, len = (rows - 1) * rs + 7;
+        const u64* run = src.base + src.at.at((u64)proof, 0, s0);
+        // word w of the run is cell k = w mod rs of row r = w / rs; a thread's words are 256 apart
+        const unsigned dq = INGEST_BLOCK / rs, dr = INGEST_BLOCK % rs;
+        unsigned r = threadIdx.x / rs, k = threadIdx.x % rs;
+        __syncthreads();
+        for (unsigned w = threadIdx.x; w < len; w += INGEST_BLOCK) {
+            if (k < 7) tile[r * 7 + k] = run[w];
+            r += dq;
+            k += dr;
+            if (k >= rs) {
+                k -= rs;
+                r++;
+            }
+        }
+        __syncthreads();
+        if (s < n) {
+#pragma unroll
+            for (int c = 0; c < 7; c++) x[c] = tile[threadIdx.x * 7 + c];
+            if (NEXT && s + 1 < n) nx = tile[(threadIdx.x + 1) * 7 + 4];
+        }
+    } else if (s < n) {
+        const u64* row = src.base + src.at.at((u64)proof, 0, s);
+#pragma unroll
+        for (int c = 0; c < 7; c++)
+            if ((live >> c) & 1) x[c] = row[(u64)c * src.at.col_stride];
+        if (NEXT && s + 1 < n) nx = row[4 * src.at.col_stride + src.at.row_stride];
+    }
+    unsigned bad = 0, unused = 0;
+#pragma unroll
+    for (int c = 0; c < 7; c++) x[c] = canonical_cell(x[c], bad, c);
+    nxt4 = canonical_cell(nx, unused, 0);
+    return bad;
+}
+// One pass over the source. keys[proof]: trace_check_kernel's word, from the same per-row function
+// (trace_row_key, kernels.hpp) and the same reduction. flags / same / vals: const_detect_kernel's, on the
+// canonical values: the two bytes per column were preset by const_flags_init_kernel, a wave that saw a
+// difference in a column stores one 0 to the column's byte (the differences are reduced over the wave
+// first), and const_class_kernel folds them (classify). For the shared columns a block of proof b > 0 loads
+// the same rows of proof 0 too, from the cache, as const_detect_kernel<true> does
+template <bool AIR, bool TILE>
+__global__ __launch_bounds__(INGEST_BLOCK) void trace_ingest_probe_kernel(StridedRows src, const AirConst* air, u64* keys,
+                                                                          int logn, unsigned char* flags, int period,
+                                                                          u64* vals) {
+    __shared__ u64 tile[TILE ? INGEST_TILE_WORDS : 1];
+    const u64 n = 1ULL << logn;
+    const u64 s = (u64)blockIdx.x * INGEST_BLOCK + threadIdx.x;
+    const int proof = blockIdx.y;
+    u64 x[7], nxt4;
+    const unsigned bad = ingest_row<TILE, AIR>(src, tile, proof, s, n, x, nxt4);
+    u64 key = TRACE_KEY_VALID;
+    if (s < n) key = trace_row_key<AIR>(air[proof], x, bad, nxt4, s, n);
+    trace_key_commit(key, keys + proof);
+
+    const bool lane0 = (threadIdx.x & 63) == 0;
+    unsigned unused = 0;
+#pragma unroll
+    for (int c = 0; c < 7; c++) {
+        const u64 first = canonical_cell(src.base[src.at.at((u64)proof, (u64)c, 0)], unused, c);  // a uniform address
+        if (blockIdx.x == 0 && threadIdx.x == 0) vals[proof * 7 + c] = first;
+        if (__any(s < n && x[c] != first) && lane0) flags[proof * 7 + c] = 0;
+    }
+    if (period && proof > 0) {  // block-uniform
+        u64 y[7], none;
+        ingest_row<TILE, false>(src, tile, 0, s, n, y, none);
+        unsigned char* same = flags + detect_same_off((size_t)gridDim.y * 7);
+#pragma unroll
+        for (int c = 0; c < 7; c++)
+            if (__any(s < n && x[c] != y[c]) && lane0) same[proof * 7 + c] = 0;
+    }
+}
+void launch_trace_ingest_probe(const StridedRows& src, const AirConst* air, int B, int logn, bool with_air, u64* keys,
+                               unsigned char* flags, u64* vals, hipStream_t s) {
+    HIPCHK(hipMemsetAsync(keys, 0xFF, (size_t)B * 8, s));  // TRACE_KEY_VALID
+    const dim3 g((unsigned)(((1ULL << logn) + INGEST_BLOCK - 1) / INGEST_BLOCK), B);
+    // classify's presets and fold; the launch between them has the check's geometry, a thread per step
+    classify(flags, B * 7, B, logn, 7, s, [&](dim3, dim3, int period) {
+        with_bool(with_air, [&](auto AIR) {
+            with_bool(src.tiled(), [&](auto TILE) {
+                XFG_LAUNCH((trace_ingest_probe_kernel<AIR, TILE>), g, dim3(INGEST_BLOCK), 0, s, src, air, keys, logn, flags,
+                           period, vals);
+            });
+        });
+    });
+}
+// The canonical cells of the live columns into trace [B][7][n], thread s of a block writing tr[c n + s]:
+// coalesced. The seven classified flags of the proof are read once, wave-uniform, and the plane of a constant
+// or shared column is left as it was, as by trace_gen_kernel; a proof with no live column returns at once
+// (the whole block: the flags are the proof's, so no thread is left at a barrier)
+template <bool TILE>
+__global__ __launch_bounds__(INGEST_BLOCK) void trace_ingest_write_kernel(StridedRows src, u64* trace,
+                                                                          const unsigned char* flags, int logn) {
+    __shared__ u64 tile[TILE ? INGEST_TILE_WORDS : 1];
+    const u64 n = 1ULL << logn;
+    const u64 s = (u64)blockIdx.x * INGEST_BLOCK + threadIdx.x;
+    const int proof = blockIdx.y;
+    const u64 bytes = row_flag_bytes(flags, (u64)proof * 7);
+    unsigned live = 0;
+#pragma unroll
+    for (int c = 0; c < 7; c++) live |= ((bytes >> (8 * c)) & 0xFF ? 0u : 1u) << c;
+    live = __builtin_amdgcn_readfirstlane(live);
+    if (!live) return;
+    u64 x[7], none;
+    ingest_row<TILE, false>(src, tile, proof, s, n, x, none, live);
+    if (s >= n) return;
+    u64* tr = trace + (u64)proof * 7 * n;
+#pragma unroll
+    for (int c = 0; c < 7; c++)
+        if ((live >> c) & 1) tr[c * n + s] = x[c];
+}
+void launch_trace_ingest_write(const StridedRows& src, int B, int logn, const unsigned char* flags, u64* trace,
+                               hipStream_t s) {
+    const dim3 g((unsigned)(((1ULL << logn) + INGEST_BLOCK - 1) / INGEST_BLOCK), B);
+    with_bool(src.tiled(), [&](auto TILE) {
+        XFG_LAUNCH(trace_ingest_write_kernel<TILE>, g, dim3(INGEST_BLOCK), 0, s, src, trace, flags, logn);
     });
 }
 // launch_const_fill: block x of a column writes entries [x, x + 1) * CONST_FILL_SPAN of the LDE plane and the

@@ -2,6 +2,7 @@
 // flagged column as the consumers of the trace's planes read it (ColConst, RowConst). Included by kernels.hpp.
 #pragma once
 #include "air.hpp"
+#include "trace_layout.hpp"
 
 namespace xfg {
 
@@ -31,6 +32,27 @@ void launch_trace_probe(const AirConst* air, int B, int logn, unsigned char* fla
 // (launch_trace_probe), and the plane of a column flagged COL_CONST or COL_SHARED is not written
 void launch_trace_gen(const AirConst* air, int B, int logn, const unsigned char* flags, u64* trace, hipStream_t s,
                       const SynthRowGen* synth = nullptr);
+// ---- a unit of B traces that lie in the caller's device memory in any layout (trace_layout.hpp): read in
+// place, never copied. base is the unit's cell (0, 0, 0); the kernels only read it.
+struct StridedRows {
+    const u64* base;
+    TraceLayout at;
+    // rows of one block are one contiguous run of words: the block stages the run in LDS with coalesced loads
+    // (the tile form of the two kernels) instead of loading seven cells row_stride words apart per thread
+    bool tiled() const { return at.col_stride == 1 && at.row_stride >= 7 && at.row_stride <= INGEST_TILE_MAX_PITCH; }
+    static constexpr u64 INGEST_TILE_MAX_PITCH = 16;
+};
+// One pass over the source for what the copy, launch_trace_check and launch_const_detect produce of a trace
+// in the lane's buffer: keys [B] as launch_trace_check leaves them (with_air as there; set by a memset on s
+// first), flags [B * 7] and vals [B * 7] as launch_const_detect(period 7) leaves them, both found on the
+// canonical values of the cells (a cell >= p counts as its value - p, which is what the check would have put
+// into the lane's copy). B <= 65535
+void launch_trace_ingest_probe(const StridedRows& src, const AirConst* air, int B, int logn, bool with_air, u64* keys,
+                               unsigned char* flags, u64* vals, hipStream_t s);
+// the canonical cells of the live columns into trace [B][7][n]; the plane of a column flagged COL_CONST or
+// COL_SHARED is not written (flags: the classified bytes of launch_trace_ingest_probe), as by launch_trace_gen
+void launch_trace_ingest_write(const StridedRows& src, int B, int logn, const unsigned char* flags, u64* trace,
+                               hipStream_t s);
 // what the NTTs would have produced for the flagged columns, v = src[col * src_stride]:
 // coef[col] = (v, 0, ..., 0) and lde[col][t][m] = v (coset-major planes); coef or lde may be nullptr.
 // Outside the prover's chain (its readers take a ColConst): xfg_debug_lde_skip and xfg_debug_interpolate_skip

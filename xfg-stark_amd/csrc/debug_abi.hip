@@ -373,6 +373,65 @@ int xfg_debug_trace_probe(xfg_ctx* c, uint32_t count, uint64_t n, const xfg_air_
     });
 }
 
+int xfg_debug_trace_ingest(xfg_ctx* c, uint32_t count, uint64_t n, const uint64_t* buf, uint64_t buf_words,
+                           const xfg_trace_layout* layout, const xfg_air_consts* airs, int validate,
+                           uint8_t* classes_out, uint64_t* vals_out, xfg_trace_fault* faults_out, uint64_t* trace_out) {
+    if (!c) return XFG_INVALID_ARGUMENT;
+    c->err.clear();
+    const bool ok = buf && airs && classes_out && vals_out && faults_out && trace_out && count != 0 &&
+                    (uint64_t)count * 7 <= 0xFFFF && is_pow2(n) && n >= 8 && n <= (1ULL << 24);
+    const TraceLayout at = !ok || !layout ? dense_layout(n)
+                                          : TraceLayout{layout->trace_stride, layout->col_stride, layout->row_stride};
+    u64 extent = 0;
+    if (!ok || !trace_extent(at, count, n, &extent) || extent > buf_words) {
+        c->err = "xfg_debug_trace_ingest: null or unsupported argument, or an extent outside the buffer";
+        return XFG_INVALID_ARGUMENT;
+    }
+    return on_lane0(c, [&](Lane* L) -> int {
+        const size_t B = count, cols = B * 7;
+        std::vector<AirConst> ha(B);
+        for (size_t b = 0; b < B; b++) {
+            if (!air_canonical(&airs[b])) {
+                c->err = "AIR constant is not a canonical field element";
+                return XFG_INVALID_ARGUMENT;
+            }
+            ha[b] = air_of(&airs[b]);
+        }
+        const int logn = (int)ilog2(n);
+        // buf_words and no headroom (DBuf adds some): what is read past the buffer is not the hook's memory
+        struct DevFree {
+            void operator()(u64* p) const { (void)hipFree(p); }
+        };
+        u64* raw = nullptr;
+        HIPCHK(hipMalloc((void**)&raw, buf_words * 8));
+        const std::unique_ptr<u64, DevFree> src(raw);
+        L->trace.ensure(cols * n);
+        L->air.ensure(B);
+        L->tkeys.ensure(B);
+        L->const_col.ensure(const_flag_bytes(cols));
+        L->const_val.ensure(cols);
+        hipStream_t s = L->stream;
+        HIPCHK(hipMemcpy(src.get(), buf, buf_words * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(L->air.p, ha.data(), B * sizeof(AirConst), hipMemcpyHostToDevice));
+        HIPCHK(hipMemsetAsync(L->trace.p, 0xFF, cols * n * 8, s));
+        HIPCHK(hipMemsetAsync(L->const_val.p, 0xFF, cols * 8, s));
+        // the front end of a unit of device traces in a strided layout as launch_trace_lde runs it
+        const StridedRows rows{src.get(), at};
+        launch_trace_ingest_probe(rows, L->air.p, (int)B, logn, validate != 0, L->tkeys.p, L->const_col.p, L->const_val.p, s);
+        launch_trace_ingest_write(rows, (int)B, logn, L->const_col.p, L->trace.p, s);
+        std::vector<u64> keys(B);
+        HIPCHK(hipMemcpyAsync(keys.data(), L->tkeys.p, B * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(classes_out, L->const_col.p, cols, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(vals_out, L->const_val.p, cols * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(trace_out, L->trace.p, cols * n * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (size_t k = 0; k < cols; k++) classes_out[k] = (uint8_t)col_class(classes_out[k]);
+        for (size_t b = 0; b < B; b++)
+            faults_out[b] = decode_trace_key(keys[b], ha[b], [&](uint32_t col, u64 step) { return buf[at.at(b, col, step)]; });
+        return XFG_OK;
+    });
+}
+
 int xfg_debug_field(xfg_ctx* c, uint32_t op, uint64_t count, const uint64_t* a, const uint64_t* b, uint64_t* out) {
     if (!c || !a || !b || !out || op > 12 || count == 0 || (op >= 9 && count % 2)) return XFG_INVALID_ARGUMENT;
     return on_lane0(c, [&](Lane* L) -> int {

@@ -161,41 +161,19 @@ __global__ __launch_bounds__(256) void trace_check_kernel(u64* trace, const AirC
         for (int c = 0; c < 7; c++) cur[c] = tr[(u64)c * n + s];
         u64 nxt4 = 0;
         if (AIR && s + 1 < n) nxt4 = tr[4 * n + s + 1];
+        unsigned bad = 0;
 #pragma unroll
-        for (int c = 6; c >= 0; c--) {
+        for (int c = 0; c < 7; c++) {
             if (cur[c] >= P) {
-                key = trace_key(TRACE_KEY_NONCANONICAL, s, (unsigned)c);
+                bad |= 1u << c;
                 cur[c] -= P;
                 tr[(u64)c * n + s] = cur[c];
             }
         }
-        if (AIR && key == TRACE_KEY_VALID) {
-            const AirConst& A = air[proof];
-            if (s + 1 < n) {
-                if (nxt4 >= P) nxt4 -= P;
-                u64 r[7];
-                air_transition(A, cur, nxt4, r);
-#pragma unroll
-                for (int c = 6; c >= 0; c--)
-                    if (r[c] != 0) key = trace_key(TRACE_KEY_TRANSITION, s, (unsigned)c);
-            } else if (cur[4] != AIR_LAST_STATE) {
-                key = trace_key(TRACE_KEY_ASSERTION, s, 7);
-            }
-            if (s == 0) {  // after the rest: an assertion precedes every transition, and number 7 when n = 1
-                u64 v0[7];
-                air_step0_values(A, v0);
-#pragma unroll
-                for (int c = 6; c >= 0; c--)
-                    if (cur[c] != v0[c]) key = trace_key(TRACE_KEY_ASSERTION, 0, (unsigned)c);
-            }
-        }
+        if (nxt4 >= P) nxt4 -= P;
+        key = trace_row_key<AIR>(air[proof], cur, bad, nxt4, s, n);
     }
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {
-        const u64 o = shfl_xor_u64(key, m, 64);
-        key = o < key ? o : key;
-    }
-    if ((threadIdx.x & 63) == 0 && key != TRACE_KEY_VALID) atomicMin((unsigned long long*)(keys + proof), (unsigned long long)key);
+    trace_key_commit(key, keys + proof);
 }
 void launch_trace_check(u64* trace, const AirConst* air, u64* keys, int logn, int npoly, bool with_air, hipStream_t s) {
     const u64 n = 1ULL << logn;

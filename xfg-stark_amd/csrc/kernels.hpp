@@ -8,6 +8,7 @@
 #include "air.hpp"
 #include "blake3.hpp"
 #include "ntt_plan.hpp"
+#include "trace_layout.hpp"
 #include "columns.hpp"
 
 namespace xfg {
@@ -126,12 +127,50 @@ void launch_merkle_fri(const u64* vals, u64 val_stride, u64 comp_stride, bool co
 // (0..6 = columns 0..6 at step 0, 7 = column 4 at step n - 1; step-major order is number order), then
 // the transition constraints by step and number 0..6 (steps 0..n-2). with_air = false: the canonicity
 // test alone. Sets keys with a memset on s first; npoly <= 65535
-constexpr u64 TRACE_KEY_VALID = ~0ULL;
-enum : unsigned { TRACE_KEY_NONCANONICAL = 0, TRACE_KEY_ASSERTION = 1, TRACE_KEY_TRANSITION = 2 };
-__host__ __device__ constexpr u64 trace_key(unsigned kind, u64 step, unsigned index) {
-    return ((u64)kind << 62) | (step << 3) | index;
-}
+// (TRACE_KEY_VALID, the kinds and trace_key itself: trace_layout.hpp, which the host shares)
+static_assert(TRACE_FIELD_P == P, "trace_layout.hpp restates the field's prime");
 void launch_trace_check(u64* trace, const AirConst* air, u64* keys, int logn, int npoly, bool with_air, hipStream_t s);
+// The check on one row, the one statement of the reporting order: the key of what step s of a trace of n steps
+// violates first, TRACE_KEY_VALID when nothing. cur: the row's seven cells, canonical; bad: bit c set where
+// cell c was >= p as it was loaded (reported before anything else, the lowest column first); nxt4: the
+// canonical cell [4][s + 1], read below the last step only. AIR = false: the canonicity test alone.
+// Called by trace_check_kernel (a trace in the lane's buffer) and trace_ingest_probe_kernel (columns.hip: the
+// caller's buffer in any layout)
+template <bool AIR>
+__device__ __forceinline__ u64 trace_row_key(const AirConst& A, const u64 (&cur)[7], unsigned bad, u64 nxt4, u64 s, u64 n) {
+    if (bad) return trace_key(TRACE_KEY_NONCANONICAL, s, (unsigned)__builtin_ctz(bad));
+    u64 key = TRACE_KEY_VALID;
+    if constexpr (AIR) {
+        if (s + 1 < n) {
+            u64 r[7];
+            air_transition(A, cur, nxt4, r);
+#pragma unroll
+            for (int c = 6; c >= 0; c--)
+                if (r[c] != 0) key = trace_key(TRACE_KEY_TRANSITION, s, (unsigned)c);
+        } else if (cur[4] != AIR_LAST_STATE) {
+            key = trace_key(TRACE_KEY_ASSERTION, s, 7);
+        }
+        if (s == 0) {  // after the rest: an assertion precedes every transition, and number 7 when n = 1
+            u64 v0[7];
+            air_step0_values(A, v0);
+#pragma unroll
+            for (int c = 6; c >= 0; c--)
+                if (cur[c] != v0[c]) key = trace_key(TRACE_KEY_ASSERTION, 0, (unsigned)c);
+        }
+    }
+    return key;
+}
+// the rows' keys reduced to a minimum over the wave with shuffles (every lane of the wave takes part); only a
+// wave that found something issues an atomicMin on the proof's word, so a valid trace issues none
+__device__ __forceinline__ void trace_key_commit(u64 key, u64* word) {
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) {
+        const u32 lo = __shfl_xor((u32)key, m, 64), hi = __shfl_xor((u32)(key >> 32), m, 64);
+        const u64 o = (u64)lo | ((u64)hi << 32);
+        key = o < key ? o : key;
+    }
+    if ((threadIdx.x & 63) == 0 && key != TRACE_KEY_VALID) atomicMin((unsigned long long*)word, (unsigned long long)key);
+}
 // composition evaluations over the CE domain 7*<w_2n> (natural order) from the trace LDE
 // div = constraint divisor table [3][2][n] from ce_divisor_table()
 // ext = extension degree D: coeffs [B][15][D], ce planes [B][D][2n]; cc: as for launch_merkle_lde

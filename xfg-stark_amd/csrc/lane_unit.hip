@@ -167,22 +167,29 @@ ColConst trace_const(const Lane* c, const ProofShape& sh) {
     return cc;
 }
 
-void launch_trace_lde(Lane* c, const Tables& T, int B, const ProofShape& sh, bool probe, bool generated) {
+void launch_trace_lde(Lane* c, const Tables& T, int B, const ProofShape& sh, bool probe, bool generated,
+                      const StridedRows* ingest, bool ingest_validate) {
     hipStream_t s = c->stream;
     const unsigned char* skip = c->const_col.p;
     // xfg_debug_poison_lde: nothing an earlier unit left in the buffers can pass for a plane of this one
     // (the LDE planes and the coefficients of constant and shared columns are never written, nor are
-    // their planes of a generated trace: that one is poisoned here, ahead of its generator)
+    // their planes of a generated or an ingested trace: that one is poisoned here, ahead of its writer)
     if (c->poison_lde) {
         HIPCHK(hipMemsetAsync(c->lde.p, 0xFF, (size_t)B * 7 * sh.N * 8, s));
         HIPCHK(hipMemsetAsync(c->coef.p, 0xFF, (size_t)B * 7 * sh.n * 8, s));
-        if (generated) HIPCHK(hipMemsetAsync(c->trace.p, 0xFF, (size_t)B * 7 * sh.n * 8, s));
+        if (generated || ingest) HIPCHK(hipMemsetAsync(c->trace.p, 0xFF, (size_t)B * 7 * sh.n * 8, s));
     }
     // constant columns, and the columns of proofs 1 .. B - 1 that equal proof 0's
     if (generated) {
         // found in the rows as they are generated; then the live columns alone go to c->trace
         launch_trace_probe(c->air.p, B, sh.logn, c->const_col.p, c->const_val.p, s);
         launch_trace_gen(c->air.p, B, sh.logn, c->const_col.p, c->trace.p, s);
+    } else if (ingest) {
+        // found, with the check's words, in the caller's buffer where it lies; then the live columns alone go
+        // to c->trace
+        launch_trace_ingest_probe(*ingest, c->air.p, B, sh.logn, ingest_validate, c->tkeys.p, c->const_col.p,
+                                  c->const_val.p, s);
+        launch_trace_ingest_write(*ingest, B, sh.logn, c->const_col.p, c->trace.p, s);
     } else {  // one pass over the trace
         launch_const_detect(c->trace.p, B * 7, sh.logn, c->const_col.p, s, 7, c->const_val.p);
     }
@@ -304,19 +311,30 @@ static ReplayView enqueue_commit_chain(Lane* c, const Tables& T, const u64* ce_d
             u64* st = c->h_trace.p;
             const u64* src = ts.p;
             const int* refused = ts.refused;
-            host_pool().parallel_for(B, [st, src, refused, n, tbytes](int b) {
-                if (refused[b]) memset(st + (size_t)b * 7 * n, 0, tbytes);
-                else memcpy(st + (size_t)b * 7 * n, src + (size_t)b * 7 * n, tbytes);
-            });
+            if (ts.strided) {  // traces in another layout are gathered where dense ones are copied
+                const TraceLayout L = ts.layout;
+                host_pool().parallel_for(B, [st, src, refused, n, tbytes, L](int b) {
+                    if (refused[b]) memset(st + (size_t)b * 7 * n, 0, tbytes);
+                    else gather_trace(src + (size_t)b * L.trace_stride, L, n, st + (size_t)b * 7 * n);
+                });
+            } else {
+                host_pool().parallel_for(B, [st, src, refused, n, tbytes](int b) {
+                    if (refused[b]) memset(st + (size_t)b * 7 * n, 0, tbytes);
+                    else memcpy(st + (size_t)b * 7 * n, src + (size_t)b * 7 * n, tbytes);
+                });
+            }
             HIPCHK(hipMemcpyAsync(c->trace.p, st, B * tbytes, hipMemcpyHostToDevice, s));
             break;
         }
         case TraceSrc::DEVICE:
             HIPCHK(hipMemcpyAsync(c->trace.p, ts.p, B * tbytes, hipMemcpyDeviceToDevice, s));
             break;
+        case TraceSrc::DEVICE_STRIDED: break;  // launch_trace_lde: read where they lie, checked and classified in one pass
     }
-    if (ts.checks()) launch_trace_check(c->trace.p, c->air.p, c->tkeys.p, logn, B, ts.validate, s);
-    launch_trace_lde(c, T, B, sh, c->lde_probe, ts.kind == TraceSrc::GENERATED);
+    const bool ingested = ts.kind == TraceSrc::DEVICE_STRIDED;
+    const StridedRows rows{ts.p, ts.layout};
+    if (ts.checks() && !ingested) launch_trace_check(c->trace.p, c->air.p, c->tkeys.p, logn, B, ts.validate, s);
+    launch_trace_lde(c, T, B, sh, c->lde_probe, ts.kind == TraceSrc::GENERATED, ingested ? &rows : nullptr, ts.validate);
     stage_mark(c, 1);
     // ---- 2. trace root -> constraint composition coefficients (7 transition + 8 boundary)
     CoinStep cs;

@@ -62,7 +62,7 @@ static void worker_main(xfg_ctx* c, int l) {
         L->timing = timing;
         // the unit's own slice of the batch's traces, refusals and key words (halved units too)
         TraceSrc ts = b->trace;
-        if (ts.p) ts.p += (size_t)b0 * 7 * b->n;
+        if (ts.p) ts.p += (size_t)b0 * (ts.strided ? ts.layout.trace_stride : 7 * b->n);
         if (!b->refused.empty()) ts.refused = b->refused.data() + b0;
         if (!b->keys.empty()) ts.keys = b->keys.data() + b0;
         prove_lane(L, b->T, b->ce_div, b->jobs.data() + b0, b1 - b0, ts, b->n, b->o);
@@ -123,32 +123,6 @@ static void note_status(xfg_ctx* c, const Batch& b, size_t k) {
                                          : "Prover error: proof generation failed (degenerate transcript or DEEP degree)";
 }
 
-// the trace check's word (trace_key, kernels.hpp) as the C ABI reports it; cell(column, step) fetches
-// that cell of the proof's trace as the caller holds it
-template <class Cell>
-static xfg_trace_fault decode_trace_key(u64 key, const AirConst& A, Cell cell) {
-    xfg_trace_fault f{};
-    if (key == TRACE_KEY_VALID) return f;
-    const unsigned kind = (unsigned)(key >> 62), idx = (unsigned)(key & 7);
-    f.step = (key << 2) >> 5;
-    if (kind == TRACE_KEY_TRANSITION) {
-        f.kind = 2;
-        f.index = idx;
-        return f;
-    }
-    if (kind == TRACE_KEY_ASSERTION) {
-        const u64 asserted[8] = {A.pub[0], A.pub[1], A.pub[2], A.pub[3], 0, A.nullifier, A.commitment, AIR_LAST_STATE};
-        f.kind = 1;
-        f.index = idx;
-        f.column = idx < 7 ? idx : 4;
-        f.expected = asserted[idx];
-    } else {
-        f.kind = 3;
-        f.column = idx;
-    }
-    f.found = cell(f.column, f.step);
-    return f;
-}
 // Trace::validate's panic messages (winter-air 0.8)
 static std::string trace_fault_text(const xfg_trace_fault& f) {
     if (f.kind == 1)
@@ -359,13 +333,12 @@ int xfg_batch_wait(xfg_ctx* c, uint64_t ticket) {
         // caller-supplied traces: what the check found, decoded (the cell of a failed assertion is read
         // from the caller's buffer, which stays theirs until here)
         if (!b->keys.empty()) {
-            const bool dev = b->trace.kind == TraceSrc::DEVICE;
+            const bool dev = b->trace.on_device();
             if (dev) HIPCHK(hipSetDevice(c->device));
+            const TraceLayout L = b->trace.layout;  // the cell's address comes from the batch's layout
             for (size_t k = 0; k < b->jobs.size(); k++) {
-                const u64* tr = b->trace.p + k * 7 * b->n;
-                const u64 n = b->n;
                 const xfg_trace_fault f = decode_trace_key(b->keys[k], b->jobs[k].air, [&](uint32_t col, u64 step) {
-                    return fetch_cell(tr, dev, (size_t)col * n + step);
+                    return fetch_cell(b->trace.p, dev, (size_t)L.at(k, col, step));
                 });
                 if (b->faults) b->faults[b->which[k]] = f;
                 if (f.kind) c->err = trace_fault_text(f);
@@ -416,10 +389,20 @@ static u64 host_noncanonical_key(const u64* tr, u64 n) {
     return key;
 }
 
-int xfg_prove_trace_batch_submit(xfg_ctx* c, uint32_t count, const uint64_t* traces, uint32_t width, uint64_t n,
-                                 const xfg_air_consts* airs, const xfg_options* opts, uint32_t flags,
-                                 uint8_t* const* outs, size_t* out_lens, int* statuses, xfg_trace_fault* faults,
-                                 uint64_t* ticket) {
+// the layout an entry was given as the library takes it: null (dense, the existing code path) for NULL and
+// for the dense layout spelled out, else the caller's strides
+static const TraceLayout* resolve_layout(const xfg_trace_layout* layout, u64 n, TraceLayout& store) {
+    if (!layout) return nullptr;
+    store = TraceLayout{layout->trace_stride, layout->col_stride, layout->row_stride};
+    return is_dense(store, n) ? nullptr : &store;
+}
+static const char* const EXTENT_REFUSAL = "trace layout: the extent of the traces overflows or is above 2^58 words";
+
+// xfg_prove_trace_batch_submit (L null: the dense layout) and xfg_prove_trace_batch_strided_submit
+static int submit_trace_batch(xfg_ctx* c, uint32_t count, const uint64_t* traces, uint32_t width, uint64_t n,
+                              const TraceLayout* L, const xfg_air_consts* airs, const xfg_options* opts, uint32_t flags,
+                              uint8_t* const* outs, size_t* out_lens, int* statuses, xfg_trace_fault* faults,
+                              uint64_t* ticket) {
     if (!c) return XFG_INVALID_ARGUMENT;
     c->err.clear();
     if (!traces || !airs || !opts || !out_lens || !statuses || !ticket || count == 0) {
@@ -443,9 +426,14 @@ int xfg_prove_trace_batch_submit(xfg_ctx* c, uint32_t count, const uint64_t* tra
             return XFG_INVALID_ARGUMENT;
         }
     const bool dev = (flags & XFG_TRACE_ON_DEVICE) != 0;
+    u64 extent = (u64)count * 7 * n;  // words from the first cell to the last
+    if (L && !trace_extent(*L, count, n, &extent)) {
+        c->err = EXTENT_REFUSAL;
+        return XFG_INVALID_ARGUMENT;
+    }
     return guarded(c, [&]() -> int {
         HIPCHK(hipSetDevice(c->device));
-        if (const char* m = dev ? device_traces_problem(c, traces, (size_t)count * 7 * n * 8) : nullptr) {
+        if (const char* m = dev ? device_traces_problem(c, traces, (size_t)extent * 8) : nullptr) {
             c->err = m;
             return XFG_INVALID_ARGUMENT;
         }
@@ -462,7 +450,13 @@ int xfg_prove_trace_batch_submit(xfg_ctx* c, uint32_t count, const uint64_t* tra
         if (!dev) {
             // all_canonical per proof on the host pool (the submitting thread starts every batch's latency)
             u64* keys = bp->keys.data();
-            host_pool().parallel_for((int)count, [&](int i) { keys[i] = host_noncanonical_key(traces + (size_t)i * 7 * n, n); });
+            if (L) {  // through the strides
+                host_pool().parallel_for((int)count, [&](int i) {
+                    keys[i] = host_noncanonical_key(traces + (size_t)i * L->trace_stride, *L, n);
+                });
+            } else {
+                host_pool().parallel_for((int)count, [&](int i) { keys[i] = host_noncanonical_key(traces + (size_t)i * 7 * n, n); });
+            }
             for (uint32_t i = 0; i < count; i++)
                 if (keys[i] != TRACE_KEY_VALID) {
                     bp->refused[i] = statuses[i] = XFG_INVALID_ARGUMENT;
@@ -470,14 +464,24 @@ int xfg_prove_trace_batch_submit(xfg_ctx* c, uint32_t count, const uint64_t* tra
                 }
             c->stage_traces = true;
         }
-        bp->trace.kind = dev ? TraceSrc::DEVICE : TraceSrc::HOST_STAGED;
+        bp->trace.kind = dev ? (L ? TraceSrc::DEVICE_STRIDED : TraceSrc::DEVICE) : TraceSrc::HOST_STAGED;
         bp->trace.p = traces;
+        bp->trace.layout = L ? *L : dense_layout(n);
+        bp->trace.strided = L != nullptr;
         bp->trace.validate = (flags & XFG_TRACE_VALIDATE) != 0;
         bp->faults = faults;
         *ticket = submit_batch(c, std::move(bp), n, o, count, outs, out_lens, statuses,
                                split_units(c, (int)count, o.beta));
         return XFG_OK;
     });
+}
+
+int xfg_prove_trace_batch_submit(xfg_ctx* c, uint32_t count, const uint64_t* traces, uint32_t width, uint64_t n,
+                                 const xfg_air_consts* airs, const xfg_options* opts, uint32_t flags,
+                                 uint8_t* const* outs, size_t* out_lens, int* statuses, xfg_trace_fault* faults,
+                                 uint64_t* ticket) {
+    return submit_trace_batch(c, count, traces, width, n, nullptr, airs, opts, flags, outs, out_lens, statuses, faults,
+                              ticket);
 }
 
 int xfg_prove_trace_batch(xfg_ctx* c, uint32_t count, const uint64_t* traces, uint32_t width, uint64_t n,
@@ -490,8 +494,29 @@ int xfg_prove_trace_batch(xfg_ctx* c, uint32_t count, const uint64_t* traces, ui
     return xfg_batch_wait(c, t);
 }
 
-int xfg_check_traces(xfg_ctx* c, uint32_t count, const uint64_t* traces, uint64_t n, const xfg_air_consts* airs,
-                     uint32_t flags, xfg_trace_fault* faults) {
+int xfg_prove_trace_batch_strided_submit(xfg_ctx* c, uint32_t count, const uint64_t* traces, uint64_t n,
+                                         const xfg_trace_layout* layout, const xfg_air_consts* airs,
+                                         const xfg_options* opts, uint32_t flags, uint8_t* const* outs, size_t* out_lens,
+                                         int* statuses, xfg_trace_fault* faults, uint64_t* ticket) {
+    TraceLayout store{};
+    const TraceLayout* L = resolve_layout(layout, n, store);
+    return submit_trace_batch(c, count, traces, 7, n, L, airs, opts, flags, outs, out_lens, statuses, faults, ticket);
+}
+
+int xfg_prove_trace_batch_strided(xfg_ctx* c, uint32_t count, const uint64_t* traces, uint64_t n,
+                                  const xfg_trace_layout* layout, const xfg_air_consts* airs, const xfg_options* opts,
+                                  uint32_t flags, uint8_t* const* outs, size_t* out_lens, int* statuses,
+                                  xfg_trace_fault* faults) {
+    uint64_t t = 0;
+    int r = xfg_prove_trace_batch_strided_submit(c, count, traces, n, layout, airs, opts, flags, outs, out_lens, statuses,
+                                                 faults, &t);
+    if (r) return r;
+    return xfg_batch_wait(c, t);
+}
+
+// xfg_check_traces (L null: the dense layout) and xfg_check_traces_strided
+static int check_traces(xfg_ctx* c, uint32_t count, const uint64_t* traces, uint64_t n, const TraceLayout* L,
+                        const xfg_air_consts* airs, uint32_t flags, xfg_trace_fault* faults) {
     if (!c) return XFG_INVALID_ARGUMENT;
     c->err.clear();
     if (!traces || !airs || !faults || count == 0) {
@@ -509,34 +534,68 @@ int xfg_check_traces(xfg_ctx* c, uint32_t count, const uint64_t* traces, uint64_
             return XFG_INVALID_ARGUMENT;
         }
     const bool dev = (flags & XFG_TRACE_ON_DEVICE) != 0;
-    return on_lane0(c, [&](Lane* L) -> int {
-        const size_t cells = (size_t)count * 7 * n;
-        if (const char* m = dev ? device_traces_problem(c, traces, cells * 8) : nullptr) {
+    const size_t cells = (size_t)count * 7 * n;
+    u64 extent = cells;
+    if (L && !trace_extent(*L, count, n, &extent)) {
+        c->err = EXTENT_REFUSAL;
+        return XFG_INVALID_ARGUMENT;
+    }
+    const TraceLayout at = L ? *L : dense_layout(n);
+    return on_lane0(c, [&](Lane* lane) -> int {
+        if (const char* m = dev ? device_traces_problem(c, traces, (size_t)extent * 8) : nullptr) {
             c->err = m;
             return XFG_INVALID_ARGUMENT;
         }
-        L->trace.ensure(cells);
-        L->air.ensure(count);
-        L->tkeys.ensure(count);
+        lane->air.ensure(count);
+        lane->tkeys.ensure(count);
         std::vector<AirConst> ha(count);
         for (uint32_t i = 0; i < count; i++) ha[i] = air_of(&airs[i]);
-        HIPCHK(hipMemcpy(L->air.p, ha.data(), count * sizeof(AirConst), hipMemcpyHostToDevice));
-        // the kernel works on the lane's copy (it canonicalises what it reports as >= p)
-        HIPCHK(hipMemcpyAsync(L->trace.p, traces, cells * 8, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                              L->stream));
-        launch_trace_check(L->trace.p, L->air.p, L->tkeys.p, (int)ilog2(n), (int)count, true, L->stream);
+        HIPCHK(hipMemcpy(lane->air.p, ha.data(), count * sizeof(AirConst), hipMemcpyHostToDevice));
+        if (L && dev) {
+            // no copy: the ingest's first pass, constraints included, straight on the caller's buffer (only read);
+            // its column classes go to the lane's buffers and are not used here
+            lane->const_col.ensure(const_flag_bytes((size_t)count * 7));
+            lane->const_val.ensure((size_t)count * 7);
+            launch_trace_ingest_probe(StridedRows{traces, at}, lane->air.p, (int)count, (int)ilog2(n), true, lane->tkeys.p,
+                                      lane->const_col.p, lane->const_val.p, lane->stream);
+        } else {
+            lane->trace.ensure(cells);
+            // the kernel works on the lane's copy (it canonicalises what it reports as >= p)
+            if (L) {  // host traces in another layout: gathered, one trace per task, then the dense path
+                std::vector<u64> dense(cells);
+                host_pool().parallel_for((int)count, [&](int i) {
+                    gather_trace(traces + (size_t)i * at.trace_stride, at, n, dense.data() + (size_t)i * 7 * n);
+                });
+                HIPCHK(hipMemcpy(lane->trace.p, dense.data(), cells * 8, hipMemcpyHostToDevice));
+            } else {
+                HIPCHK(hipMemcpyAsync(lane->trace.p, traces, cells * 8,
+                                      dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, lane->stream));
+            }
+            launch_trace_check(lane->trace.p, lane->air.p, lane->tkeys.p, (int)ilog2(n), (int)count, true, lane->stream);
+        }
         std::vector<u64> keys(count);
-        HIPCHK(hipMemcpyAsync(keys.data(), L->tkeys.p, count * 8, hipMemcpyDeviceToHost, L->stream));
-        HIPCHK(hipStreamSynchronize(L->stream));
+        HIPCHK(hipMemcpyAsync(keys.data(), lane->tkeys.p, count * 8, hipMemcpyDeviceToHost, lane->stream));
+        HIPCHK(hipStreamSynchronize(lane->stream));
         for (uint32_t i = 0; i < count; i++) {
-            const u64* tr = traces + (size_t)i * 7 * n;
             faults[i] = decode_trace_key(keys[i], ha[i], [&](uint32_t col, u64 step) {
-                return fetch_cell(tr, dev, (size_t)col * n + step);
+                return fetch_cell(traces, dev, (size_t)at.at(i, col, step));
             });
             if (faults[i].kind) c->err = trace_fault_text(faults[i]);
         }
         return XFG_OK;
     });
+}
+
+int xfg_check_traces(xfg_ctx* c, uint32_t count, const uint64_t* traces, uint64_t n, const xfg_air_consts* airs,
+                     uint32_t flags, xfg_trace_fault* faults) {
+    return check_traces(c, count, traces, n, nullptr, airs, flags, faults);
+}
+
+int xfg_check_traces_strided(xfg_ctx* c, uint32_t count, const uint64_t* traces, uint64_t n,
+                             const xfg_trace_layout* layout, const xfg_air_consts* airs, uint32_t flags,
+                             xfg_trace_fault* faults) {
+    TraceLayout store{};
+    return check_traces(c, count, traces, n, resolve_layout(layout, n, store), airs, flags, faults);
 }
 
 int xfg_prepare(xfg_ctx* c, uint32_t count, uint64_t trace_length, const xfg_options* opts) {

@@ -114,16 +114,24 @@ struct Lane {
 
 // where a unit's traces come from, and what is checked on the way. p: the unit's own slice [B][7][n]
 // (null: generated on the device from the AIR constants)
+// DEVICE_STRIDED: device traces in a layout other than the dense one; they are never copied, the unit's
+// front end reads them where they lie (launch_trace_lde). HOST_STAGED with `strided` set: host traces in such
+// a layout, gathered into the lane's staging where dense ones are copied into it
 struct TraceSrc {
-    enum Kind { GENERATED, HOST_DIRECT, HOST_STAGED, DEVICE };
+    enum Kind { GENERATED, HOST_DIRECT, HOST_STAGED, DEVICE, DEVICE_STRIDED };
     Kind kind = GENERATED;
     const u64* p = nullptr;
+    // where the cells lie from p on (batches of caller-supplied traces: the dense layout unless `strided`); a
+    // unit's slice starts trace_stride words per proof further on
+    TraceLayout layout{0, 0, 0};
+    bool strided = false;
+    bool on_device() const { return kind == DEVICE || kind == DEVICE_STRIDED; }
     bool validate = false;        // XFG_TRACE_VALIDATE: the AIR check behind the upload
     bool size_staging = false;    // grow the lane's pinned trace staging with its other buffers
     const int* refused = nullptr;  // [B] non-zero: refused at submission, the slot is proven over zeros
     u64* keys = nullptr;          // [B] out: the check kernel's words (when checks())
     // device traces are always tested for canonical cells; host traces were on the host
-    bool checks() const { return validate || kind == DEVICE; }
+    bool checks() const { return validate || on_device(); }
 };
 
 // a submitted batch: jobs [0, B) proven in units of XFG_UNIT proofs by the lane workers; proof
@@ -244,7 +252,12 @@ void size_ood_deep(Lane* c, size_t B, const ProofShape& sh);  // hcoef, zpts, pa
 // (launch_const_detect). generated = true: the unit's traces are those of the burn row generator on c->air
 // and are classified as it produces them (launch_trace_probe); then launch_trace_gen writes the live
 // columns alone to c->trace, so the trace planes of constant and shared columns hold nothing either
-void launch_trace_lde(Lane* c, const Tables& T, int B, const ProofShape& sh, bool probe, bool generated = false);
+// ingest (generated = false): the unit's traces lie in the caller's device memory behind *ingest and are not in
+// c->trace: one pass finds the check's words (c->tkeys, AIR constraints included when ingest_validate), the
+// flags and the values (launch_trace_ingest_probe on c->air), a second writes the canonical live columns to
+// c->trace (launch_trace_ingest_write); the planes of the others hold nothing, as for a generated unit
+void launch_trace_lde(Lane* c, const Tables& T, int B, const ProofShape& sh, bool probe, bool generated = false,
+                      const StridedRows* ingest = nullptr, bool ingest_validate = false);
 ColConst trace_const(const Lane* c, const ProofShape& sh);
 // the proof-of-work search on the device for the B seeds the caller wrote to grind_seeds(c, B): launched on
 // the lane's gather stream (idle between a unit's chain and its gathers) and waited for. Returns the B
@@ -261,6 +274,33 @@ static inline bool all_canonical(const uint64_t* v, size_t k) {
 }
 static inline bool air_canonical(const xfg_air_consts* a) {
     return all_canonical(a->pub_inputs, 12) && a->nullifier < P && a->commitment < P;
+}
+
+// the trace check's word (trace_key, trace_layout.hpp) as the C ABI reports it; cell(column, step) fetches
+// that cell of the proof's trace as the caller holds it
+template <class Cell>
+static xfg_trace_fault decode_trace_key(u64 key, const AirConst& A, Cell cell) {
+    xfg_trace_fault f{};
+    if (key == TRACE_KEY_VALID) return f;
+    const unsigned kind = (unsigned)(key >> 62), idx = (unsigned)(key & 7);
+    f.step = (key << 2) >> 5;
+    if (kind == TRACE_KEY_TRANSITION) {
+        f.kind = 2;
+        f.index = idx;
+        return f;
+    }
+    if (kind == TRACE_KEY_ASSERTION) {
+        const u64 asserted[8] = {A.pub[0], A.pub[1], A.pub[2], A.pub[3], 0, A.nullifier, A.commitment, AIR_LAST_STATE};
+        f.kind = 1;
+        f.index = idx;
+        f.column = idx < 7 ? idx : 4;
+        f.expected = asserted[idx];
+    } else {
+        f.kind = 3;
+        f.column = idx;
+    }
+    f.found = cell(f.column, f.step);
+    return f;
 }
 
 template <class F>

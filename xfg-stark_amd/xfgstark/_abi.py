@@ -59,6 +59,10 @@ class _TraceFault(C.Structure):
                 ("expected", C.c_uint64), ("found", C.c_uint64)]
 
 
+class _TraceLayout(C.Structure):
+    _fields_ = [("trace_stride", C.c_uint64), ("col_stride", C.c_uint64), ("row_stride", C.c_uint64)]
+
+
 class _ProbePattern(C.Structure):
     _fields_ = [("kind", C.c_uint32 * 7), ("reserved", C.c_uint32), ("row", C.c_uint64 * 7), ("proof", C.c_uint64)]
 
@@ -74,6 +78,8 @@ _opts, _burn, _airs, _faults = C.POINTER(_Options), C.POINTER(_BurnInputs), C.PO
 # the submit entries take their synchronous form's arguments and a ticket
 _PROVE_BATCH = [_ctx, _u32, _burn, _u64, _opts, _bufs, _szp, _intp]
 _TRACE_BATCH = [_ctx, _u32, C.c_void_p, _u32, _u64, _airs, _opts, _u32, _bufs, _szp, _intp, _faults]
+_layout = C.POINTER(_TraceLayout)
+_TRACE_BATCH_STRIDED = [_ctx, _u32, C.c_void_p, _u64, _layout, _airs, _opts, _u32, _bufs, _szp, _intp, _faults]
 _FRI = [_ctx, _u32, _u32, _u32, _u32, _int]  # count, ext, logn, logbeta, coset_major
 _OOD_TAIL = [_u64p, _u64p, _u64p, _u32p, _u64p, _u64, _u64p, _u64p, _u64p, _u32p, _u64p, _intp]  # from hcoef on
 
@@ -92,6 +98,9 @@ TABLE = [
     ("xfg_check_traces", _int, [_ctx, _u32, C.c_void_p, _u64, _airs, _u32, _faults]),
     ("xfg_prove_trace_batch", _int, _TRACE_BATCH),
     ("xfg_prove_trace_batch_submit", _int, _TRACE_BATCH + [_u64p]),
+    ("xfg_check_traces_strided", _int, [_ctx, _u32, C.c_void_p, _u64, _layout, _airs, _u32, _faults]),
+    ("xfg_prove_trace_batch_strided", _int, _TRACE_BATCH_STRIDED),
+    ("xfg_prove_trace_batch_strided_submit", _int, _TRACE_BATCH_STRIDED + [_u64p]),
     ("xfg_prepare", _int, [_ctx, _u32, _u64, _opts]),
     ("xfg_burn_air_consts", _int, [_burn, _airs]),
     ("xfg_proof_parse", _int, [_u8p, _sz, C.POINTER(_ProofInfo), _str, _sz]),
@@ -109,6 +118,7 @@ TABLE = [
     ("xfg_debug_const_columns", _int, [_ctx, _u64p, _u32, _u32, _u64, _u8p]),
     ("xfg_debug_col_classes", _int, [_ctx, _u64p, _u32, _u64, _u8p, _u64p]),
     ("xfg_debug_trace_probe", _int, [_ctx, _u32, _u64, _airs, _u32, C.POINTER(_ProbePattern), _u8p, _u64p, _u64p]),
+    ("xfg_debug_trace_ingest", _int, [_ctx, _u32, _u64, _u64p, _u64, _layout, _airs, _int, _u8p, _u64p, _faults, _u64p]),
     ("xfg_debug_lde_skip", _int, [_ctx, _u64p, _u32, _u64, _u32, _u8p, _u64p]),
     ("xfg_debug_interpolate_skip", _int, [_ctx, _u64p, _u32, _u64, _int, _u8p, _u64p]),
     ("xfg_debug_interpolate_keep", _int, [_ctx, _u64p, _u32, _u64, _u64, _int, _u64p]),

@@ -5,9 +5,9 @@ import operator
 import sys
 
 from ._abi import (STATUS, TRACE_ON_DEVICE, TRACE_VALIDATE, XfgStarkError, _AirConsts, _BurnInputs, _lib, _Options,
-                   _ProofInfo, _TraceFault, _u8p)
+                   _ProofInfo, _TraceFault, _TraceLayout, _u8p)
 from ._hooks import KernelHooks
-from ._marshal import air_array, air_struct, array, bytes_ptr, new_buffer, out_slots, ptr
+from ._marshal import air_array, air_struct, array, bytes_ptr, new_buffer, out_slots, ptr, trace_array
 
 
 class TraceFault:
@@ -546,43 +546,64 @@ class XfgBurnMintProver(KernelHooks):
         return self._submit(_lib.xfg_prove_batch_submit, (k, arr, trace_length, C.byref(o)), k, cap,
                             record=addr, owner=owner)
 
-    def _trace_args(self, traces, airs):
-        """the C arguments of a batch of traces: (object to keep alive, pointer, count, n, airs array, flags)"""
+    def _trace_view(self, traces, airs):
+        """the C arguments of a batch of traces of logical shape [count][7][n]: (objects to keep alive, pointer,
+        count, width, n, airs array, flags, layout). layout: None for contiguous data, which goes to the entries
+        without a layout as it always has; else the (trace, column, row) strides in 8-byte words of a strided
+        tensor or array, which goes to the _strided entries as it lies"""
         if hasattr(traces, "data_ptr"):  # a torch.Tensor (torch itself is not imported here)
             t = traces
             if t.device.type != "cuda" or (t.device.index or 0) != self._device:
                 raise XfgStarkError(9, f"traces tensor is on {t.device}, the prover on device {self._device}")
-            if str(t.dtype) not in ("torch.int64", "torch.uint64") or not t.is_contiguous():
-                raise XfgStarkError(9, "traces tensor must be contiguous with dtype int64 or uint64")
+            if str(t.dtype) not in ("torch.int64", "torch.uint64"):
+                raise XfgStarkError(9, "traces tensor must have dtype int64 or uint64")
             shape, keep, flags = tuple(t.shape), t, TRACE_ON_DEVICE
+            layout = None if t.is_contiguous() or len(shape) != 3 else tuple(t.stride())
             if len(shape) == 3 and t.numel():
                 import torch
-                torch.cuda.current_stream(t.device).synchronize()  # the data is complete before the lanes copy it
+                torch.cuda.current_stream(t.device).synchronize()  # the data is complete before the lanes read it
             where = t.data_ptr()
         else:
-            a = array(traces)
+            a, layout = trace_array(traces)
             shape, keep, flags, where = a.shape, a, 0, a.ctypes.data
         if len(shape) != 3:
             raise XfgStarkError(9, "traces: [count][7][n]")
         count, width, n = shape
+        if layout is not None and (width != 7 or min(layout) < 0):  # a layout names seven columns
+            raise XfgStarkError(9, "XfgBurnMintAir traces have 7 columns" if width != 7
+                                else "traces: a view with a negative stride is not supported")
         if len(airs) != count:
             raise XfgStarkError(9, f"{count} traces, {len(airs)} AIR constants")
         air_np, air_p = air_array(airs)
-        return (keep, air_np), where or None, count, width, n, air_p, flags
+        return (keep, air_np), where or None, count, width, n, air_p, flags, layout
+
+    def _trace_args(self, traces, airs):
+        """_trace_view without the layout: (objects to keep alive, pointer, count, width, n, airs array, flags)"""
+        return self._trace_view(traces, airs)[:7]
 
     def submit_traces(self, traces, airs, validate=False):
-        """asynchronous prove_traces (xfg_prove_trace_batch_submit) -> PendingBatch; the traces (array or
-        tensor) are referenced by it until it has been waited for, and must not be written before then"""
-        keep, where, count, width, n, air_p, flags = self._trace_args(traces, airs)
+        """asynchronous prove_traces (xfg_prove_trace_batch_submit, or _strided_submit for a strided view) ->
+        PendingBatch; the traces (array or tensor) are referenced by it until it has been waited for, and must
+        not be written before then"""
+        keep, where, count, width, n, air_p, flags, layout = self._trace_view(traces, airs)
         o, cap = self._options._c_and_bound(n) if count else (self._options._c(), 0)
         faults = (_TraceFault * count)()
         flags |= TRACE_VALIDATE if validate else 0
-        return self._submit(_lib.xfg_prove_trace_batch_submit, (count, where, width, n, air_p, C.byref(o), flags),
-                            count, cap, tail=(faults,), buf=self._take_buffer(cap * count), owner=keep, faults=faults)
+        if layout is None:
+            fn, head = _lib.xfg_prove_trace_batch_submit, (count, where, width, n, air_p, C.byref(o), flags)
+        else:
+            at = _TraceLayout(*layout)
+            keep = keep + (at,)
+            fn, head = _lib.xfg_prove_trace_batch_strided_submit, (count, where, n, C.byref(at), air_p, C.byref(o), flags)
+        return self._submit(fn, head, count, cap, tail=(faults,), buf=self._take_buffer(cap * count), owner=keep,
+                            faults=faults)
 
     def prove_traces(self, traces, airs, validate=False):
-        """ExecutionTrace-level proving of a batch: traces = numpy uint64 array [count][7][n] or a
-        contiguous int64 / uint64 torch.Tensor of that shape on the prover's device, airs = count x
+        """ExecutionTrace-level proving of a batch: traces = numpy uint64 array or int64 / uint64 torch.Tensor
+        on the prover's device, of logical shape [count][7][n] with any non-negative strides: row-major data
+        [count][n][7] is rows.permute(0, 2, 1) (numpy: rows.transpose(0, 2, 1)), rows padded to 8 words are
+        rows[..., :7].permute(0, 2, 1). A strided view is read where it lies, without a copy (a host array
+        whose strides are not multiples of 8 bytes is copied first). airs = count x
         (pub_inputs[12], nullifier, commitment) -> list of StarkProof | XfgStarkError (per proof).
         validate: Trace::validate on the device first; a trace that violates the AIR gives an
         XfgStarkError of status 11 (INVALID_TRACE) whose .fault is the TraceFault and whose text is
@@ -593,12 +614,16 @@ class XfgBurnMintProver(KernelHooks):
         return self.submit_traces(traces, airs, validate).result()
 
     def check_traces(self, traces, airs):
-        """Trace::validate on the device alone (xfg_check_traces): -> list of TraceFault | None"""
-        keep, where, count, width, n, air_p, flags = self._trace_args(traces, airs)
+        """Trace::validate on the device alone (xfg_check_traces, or xfg_check_traces_strided for a strided
+        view: traces as for prove_traces): -> list of TraceFault | None"""
+        keep, where, count, width, n, air_p, flags, layout = self._trace_view(traces, airs)
         if width != 7:
             raise XfgStarkError(9, "XfgBurnMintAir traces have 7 columns")
         faults = (_TraceFault * max(count, 1))()
-        self._call(_lib.xfg_check_traces, count, where, n, air_p, flags, faults)
+        if layout is None:
+            self._call(_lib.xfg_check_traces, count, where, n, air_p, flags, faults)
+        else:
+            self._call(_lib.xfg_check_traces_strided, count, where, n, C.byref(_TraceLayout(*layout)), air_p, flags, faults)
         return [TraceFault._from_c(faults[i]) for i in range(count)]
 
     def _take_buffer(self, size):

@@ -3,7 +3,7 @@ kernels, host arrays out. The layouts, and the 0xFF bytes the entries put where 
 left, are described in include/xfg_stark.h."""
 import ctypes as C
 
-from ._abi import XfgStarkError, _lib, _ProbePattern, _u8p, _u32p
+from ._abi import XfgStarkError, _lib, _ProbePattern, _TraceFault, _TraceLayout, _u8p, _u32p
 from ._marshal import air_array, array, ptr, words, zeros
 
 
@@ -57,6 +57,22 @@ class KernelHooks:
         cls, vals, tr = zeros((B, 7), "uint8"), zeros((B, 7)), zeros((B, 7, n))
         self._call(_lib.xfg_debug_trace_probe, B, n, air_p, generator, pat, ptr(cls, _u8p), ptr(vals), ptr(tr))
         return cls, vals, tr
+
+    def debug_trace_ingest(self, buf, layout, count, n, airs, validate=False):
+        """the front end of a unit of device traces in a strided layout (xfg_debug_trace_ingest): buf = a flat
+        uint64 array, uploaded as it is; layout = (trace, column, row) strides in words, None for dense; airs =
+        count air_consts() tuples -> (classes [count,7], values [count,7], faults: list of the xfg_trace_fault
+        fields (kind, index, column, step, expected, found) or None, trace buffer [count,7,n] as left: unwritten
+        planes are 0xFF bytes)"""
+        b = array(buf).reshape(-1)
+        keep, air_p = air_array(airs)
+        at = None if layout is None else C.byref(_TraceLayout(*layout))
+        cls, vals, tr = zeros((count, 7), "uint8"), zeros((count, 7)), zeros((count, 7, n))
+        faults = (_TraceFault * max(count, 1))()
+        self._call(_lib.xfg_debug_trace_ingest, count, n, ptr(b), b.size, at, air_p, 1 if validate else 0,
+                   ptr(cls, _u8p), ptr(vals), faults, ptr(tr))
+        fields = [name for name, _ in _TraceFault._fields_]
+        return cls, vals, [tuple(getattr(f, k) for k in fields) if f.kind else None for f in faults[:count]], tr
 
     def debug_ood_deep_const(self, coef, flags, vals, hcoef, zpts, coeffs):
         """debug_ood_deep_e without coins on coefficients behind a column descriptor (xfg_debug_ood_deep_const):

@@ -19,6 +19,20 @@ def array(x, dtype="uint64", shape=None, what=None):
     return a
 
 
+def trace_array(x):
+    """a batch of host traces [count][7][n] -> (array, layout). A uint64 ndarray that is not C-contiguous and
+    whose strides are non-negative multiples of 8 bytes goes to the library as it lies, without a copy: layout =
+    its (trace, column, row) strides in 8-byte words. Anything else is copied into a C-contiguous array, layout
+    None. A negative stride raises XfgStarkError(9): the library's strides are unsigned"""
+    n_ = np()
+    if isinstance(x, n_.ndarray) and x.dtype == n_.uint64 and x.ndim == 3:
+        if any(s < 0 for s in x.strides):
+            raise XfgStarkError(9, "traces: a view with a negative stride is not supported")
+        if not x.flags.c_contiguous and x.flags.aligned and all(s % 8 == 0 for s in x.strides):
+            return x, tuple(s // 8 for s in x.strides)
+    return array(x), None
+
+
 def zeros(shape, dtype="uint64"):
     return np().zeros(shape, dtype=dtype)
 
