@@ -12,6 +12,9 @@ bench.py keeps them:
      a producer of rows has to do with a library that takes the dense layout only
   e2 the same rows passed as the view rows.permute(0, 2, 1): read where they lie (xfg_prove_trace_batch_strided);
      left out when the library loaded through XFG_LIB has no such entry
+  k  check_traces on the 64 device-resident traces of c, a host clock around `batches` calls one after the other
+     (the call synchronises): traces/s
+  kh k on the host array of b, at most 24 calls
 
 The modes alternate `rounds` times in one process on one card; one JSON line per mode and round, then a
 summary line per mode (median, min, max proofs/s). Then, in timing mode (one 64-proof unit, HIP events
@@ -19,7 +22,7 @@ around the stages), the first stage -- upload, check, interpolation and LDE of t
 cv: their difference is the check kernel's time for 64 traces.
 
 usage: python3 scripts/trace_batch_bench.py [batches per round, default 24] [rounds, 3] [depth, 6]
-                                            [modes, comma-separated first letters, default all: a,b,c,cv,d,e1,e2]"""
+                                            [modes, comma-separated first letters, default all: a,b,c,cv,d,e1,e2,k,kh]"""
 import collections
 import json
 import os
@@ -89,6 +92,14 @@ def main():
             pr.prove_trace(host[i], *airs[i])
         return COUNT / (time.perf_counter() - t0)
 
+    calls = {"a_prove_trace_loop": 1, "kh_check_host": min(batches, 24)}  # submissions per round; else `batches`
+
+    def check_loop(traces, reps):
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            assert pr.check_traces(traces, airs) == [None] * COUNT
+        return reps * COUNT / (time.perf_counter() - t0)
+
     modes = collections.OrderedDict([
         ("a_prove_trace_loop", lambda: single_loop()),
         ("b_host_array", lambda: pipelined(lambda: pr.submit_traces(host, airs), batches, depth)),
@@ -98,6 +109,8 @@ def main():
         ("e1_rows_permute_copy", lambda: pipelined(lambda: pr.submit_traces(rows.permute(0, 2, 1).contiguous(), airs),
                                                    batches, depth)),
         ("e2_rows_view", lambda: pipelined(lambda: pr.submit_traces(rows.permute(0, 2, 1), airs), batches, depth)),
+        ("k_check_device", lambda: check_loop(dev, batches)),
+        ("kh_check_host", lambda: check_loop(host, calls["kh_check_host"])),
     ])
     if not strided:
         del modes["e2_rows_view"]
@@ -114,7 +127,7 @@ def main():
             assert [p.to_bytes() for p in pr.prove_traces(rows.permute(0, 2, 1), airs, validate=validate)] == want
     pr.prepare(COUNT, N)  # the context has seen host traces: the lanes' pinned staging is sized now
     for name, run in modes.items():  # warm every path once
-        run() if name.startswith("a_") else pipelined(
+        run() if name.startswith(("a_", "k")) else pipelined(
             {"b": lambda: pr.submit_traces(host, airs), "c": lambda: pr.submit_traces(dev, airs),
              "cv": lambda: pr.submit_traces(dev, airs, validate=True),
              "d": lambda: pr.submit_batch(inputs, N),
@@ -128,7 +141,7 @@ def main():
             print(json.dumps({"round": r, "mode": name, "proofs_per_s": round(v, 1)}), flush=True)
     for name, v in rates.items():
         print(json.dumps({"mode": name, "median": round(statistics.median(v), 1), "min": round(min(v), 1),
-                          "max": round(max(v), 1), "batches": 1 if name.startswith("a_") else batches,
+                          "max": round(max(v), 1), "batches": calls.get(name, batches),
                           "depth": depth}), flush=True)
     bytes_per_batch = host.nbytes
     if "b_host_array" in rates:

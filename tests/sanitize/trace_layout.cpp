@@ -34,7 +34,8 @@ static std::vector<Case> cases(u64 n, u64 count) {
 }
 static u64 cell_value(u64 i, u64 c, u64 s) { return (i << 40) | (c << 32) | (s + 1); }  // canonical, all distinct
 
-// the dense key of prover.hip's host check, restated: the smallest key over the columns' first offenders
+// the key of a dense trace, restated independently of trace_layout.hpp: the smallest key over the columns' first
+// offenders
 static u64 dense_key(const std::vector<u64>& tr, u64 n) {
     u64 key = TRACE_KEY_VALID;
     for (unsigned c = 0; c < 7; c++)

@@ -186,6 +186,41 @@ def test_view_bytes_match_oracle(prover, name, where, count, n, blowup, ext, q):
         TB._restore(prover)
 
 
+@pytest.mark.parametrize("where", ["host", "device"])
+def test_dense_layout_spelled_out_is_the_dense_run(prover, where):
+    """{7n, n, 1} at the raw strided entries (the package sends a contiguous array to the entries without a
+    layout): the oracle's bytes, the faults of check_traces on the dense array, and a device buffer only read"""
+    import xfgstark
+    lib = xfgstark._lib
+    count, n, blowup, ext, q = SHAPES[0]
+    traces, airs, wants = _batch(count, n, blowup, ext, q)
+    dense = np.ascontiguousarray(traces)
+    held = TB._input(dense, where)
+    ptr, flags = (dense.ctypes.data, 0) if where == "host" else (held.data_ptr(), xfgstark.TRACE_ON_DEVICE)
+    air_np, air_p = xfgstark._marshal.air_array(airs)
+    at = xfgstark._TraceLayout(7 * n, n, 1)
+    want_faults = [TB._fault_tuple(f) for f in prover.check_traces(held, airs)]
+    assert any(want_faults)  # the random traces violate the AIR: the faults compared below are not all None
+    faults = (xfgstark._TraceFault * count)()
+    assert lib.xfg_check_traces_strided(prover._ctx, count, ptr, n, C.byref(at), air_p, flags, faults) == 0
+    assert [TB._fault_tuple(xfgstark.TraceFault._from_c(faults[i])) for i in range(count)] == want_faults
+    TB._with_options(prover, blowup, ext, q)
+    try:
+        o, cap = prover._options._c_and_bound(n)
+        bufs = [C.create_string_buffer(cap) for _ in range(count)]
+        outs = (xfgstark._u8p * count)(*[C.cast(b, xfgstark._u8p) for b in bufs])
+        lens, sts = (C.c_size_t * count)(*[cap] * count), (C.c_int * count)()
+        assert lib.xfg_prove_trace_batch_strided(prover._ctx, count, ptr, n, C.byref(at), air_p, C.byref(o), flags, outs,
+                                                 lens, sts, None) == 0
+    finally:
+        TB._restore(prover)
+    assert list(sts) == [0] * count
+    for i in range(count):
+        assert C.string_at(bufs[i], lens[i]) == wants[i], i
+    if where == "device":
+        assert np.array_equal(held.cpu().numpy().view(np.uint64), dense)
+
+
 def test_two_submissions_back_to_back(prover):
     """submit_traces twice, from a row-major view and from a dense tensor, then both waits"""
     traces, airs, wants = _batch(70, 64, 8, 1, 42)

@@ -4,7 +4,7 @@ the batches they run on.
 TEST INFRASTRUCTURE ONLY. A layout says where cell (trace i, column c, step s) lies in one flat buffer of
 8-byte words: offset + i * trace_stride + c * col_stride + s * row_stride (xfg_trace_layout).
 
-    dense        {7n, n, 1}              the hook only: the entries take the existing path for it
+    dense        {7n, n, 1}              the hook; the entries copy it as they do without a layout (one raw test)
     rows7        {7n, 1, 7}              row-major; the tile form of the ingest kernels, pitch 7
     rows8        {8n, 1, 8}              rows padded to 8 words; the 8th word of every row is 2^64 - 1
     rows12+3     {12n, 1, 12}, offset 3  seven columns of a wider table; the base is only 8-byte aligned

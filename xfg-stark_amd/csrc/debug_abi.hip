@@ -314,8 +314,7 @@ int xfg_debug_col_classes(xfg_ctx* c, const uint64_t* trace, uint32_t count, uin
         L->const_val.ensure(cols);
         HIPCHK(hipMemcpy(L->trace.p, trace, cols * n * 8, hipMemcpyHostToDevice));
         HIPCHK(hipMemsetAsync(L->const_val.p, 0xFF, cols * 8, L->stream));
-        // the unit's detection as launch_trace_lde runs it
-        launch_const_detect(L->trace.p, (int)cols, (int)ilog2(n), L->const_col.p, L->stream, 7, L->const_val.p);
+        launch_trace_front(L, (int)count, (int)ilog2(n), TraceFront{TraceFront::IN_LANE, TraceFront::NONE, nullptr, {}});
         HIPCHK(hipMemcpyAsync(classes_out, L->const_col.p, cols, hipMemcpyDeviceToHost, L->stream));
         if (vals_out) HIPCHK(hipMemcpyAsync(vals_out, L->const_val.p, cols * 8, hipMemcpyDeviceToHost, L->stream));
         HIPCHK(hipStreamSynchronize(L->stream));
@@ -338,14 +337,8 @@ int xfg_debug_trace_probe(xfg_ctx* c, uint32_t count, uint64_t n, const xfg_air_
     }
     return on_lane0(c, [&](Lane* L) -> int {
         const size_t B = count, cols = B * 7;
-        std::vector<AirConst> ha(B);
-        for (size_t b = 0; b < B; b++) {
-            if (!air_canonical(&airs[b])) {
-                c->err = "AIR constant is not a canonical field element";
-                return XFG_INVALID_ARGUMENT;
-            }
-            ha[b] = air_of(&airs[b]);
-        }
+        std::vector<AirConst> ha;
+        if (!airs_of(c, airs, B, ha, L)) return XFG_INVALID_ARGUMENT;
         SynthRowGen synth = {};
         if (generator == 1) {
             for (int k = 0; k < 7; k++) synth.kind[k] = pattern->kind[k], synth.row[k] = pattern->row[k];
@@ -354,16 +347,12 @@ int xfg_debug_trace_probe(xfg_ctx* c, uint32_t count, uint64_t n, const xfg_air_
         const SynthRowGen* sg = generator == 1 ? &synth : nullptr;
         const int logn = (int)ilog2(n);
         L->trace.ensure(cols * n);
-        L->air.ensure(B);
         L->const_col.ensure(const_flag_bytes(cols));
         L->const_val.ensure(cols);
         hipStream_t s = L->stream;
-        HIPCHK(hipMemcpy(L->air.p, ha.data(), B * sizeof(AirConst), hipMemcpyHostToDevice));
         HIPCHK(hipMemsetAsync(L->trace.p, 0xFF, cols * n * 8, s));
         HIPCHK(hipMemsetAsync(L->const_val.p, 0xFF, cols * 8, s));
-        // the front end of a generated unit as launch_trace_lde runs it
-        launch_trace_probe(L->air.p, (int)B, logn, L->const_col.p, L->const_val.p, s, sg);
-        launch_trace_gen(L->air.p, (int)B, logn, L->const_col.p, L->trace.p, s, sg);
+        launch_trace_front(L, (int)B, logn, TraceFront{TraceFront::GENERATED, TraceFront::NONE, sg, {}});
         HIPCHK(hipMemcpyAsync(classes_out, L->const_col.p, cols, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(vals_out, L->const_val.p, cols * 8, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(trace_out, L->trace.p, cols * n * 8, hipMemcpyDeviceToHost, s));
@@ -380,8 +369,7 @@ int xfg_debug_trace_ingest(xfg_ctx* c, uint32_t count, uint64_t n, const uint64_
     c->err.clear();
     const bool ok = buf && airs && classes_out && vals_out && faults_out && trace_out && count != 0 &&
                     (uint64_t)count * 7 <= 0xFFFF && is_pow2(n) && n >= 8 && n <= (1ULL << 24);
-    const TraceLayout at = !ok || !layout ? dense_layout(n)
-                                          : TraceLayout{layout->trace_stride, layout->col_stride, layout->row_stride};
+    const TraceLayout at = layout_of(ok ? layout : nullptr, n);
     u64 extent = 0;
     if (!ok || !trace_extent(at, count, n, &extent) || extent > buf_words) {
         c->err = "xfg_debug_trace_ingest: null or unsupported argument, or an extent outside the buffer";
@@ -389,14 +377,8 @@ int xfg_debug_trace_ingest(xfg_ctx* c, uint32_t count, uint64_t n, const uint64_
     }
     return on_lane0(c, [&](Lane* L) -> int {
         const size_t B = count, cols = B * 7;
-        std::vector<AirConst> ha(B);
-        for (size_t b = 0; b < B; b++) {
-            if (!air_canonical(&airs[b])) {
-                c->err = "AIR constant is not a canonical field element";
-                return XFG_INVALID_ARGUMENT;
-            }
-            ha[b] = air_of(&airs[b]);
-        }
+        std::vector<AirConst> ha;
+        if (!airs_of(c, airs, B, ha, L)) return XFG_INVALID_ARGUMENT;
         const int logn = (int)ilog2(n);
         // buf_words and no headroom (DBuf adds some): what is read past the buffer is not the hook's memory
         struct DevFree {
@@ -406,19 +388,15 @@ int xfg_debug_trace_ingest(xfg_ctx* c, uint32_t count, uint64_t n, const uint64_
         HIPCHK(hipMalloc((void**)&raw, buf_words * 8));
         const std::unique_ptr<u64, DevFree> src(raw);
         L->trace.ensure(cols * n);
-        L->air.ensure(B);
         L->tkeys.ensure(B);
         L->const_col.ensure(const_flag_bytes(cols));
         L->const_val.ensure(cols);
         hipStream_t s = L->stream;
         HIPCHK(hipMemcpy(src.get(), buf, buf_words * 8, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(L->air.p, ha.data(), B * sizeof(AirConst), hipMemcpyHostToDevice));
         HIPCHK(hipMemsetAsync(L->trace.p, 0xFF, cols * n * 8, s));
         HIPCHK(hipMemsetAsync(L->const_val.p, 0xFF, cols * 8, s));
-        // the front end of a unit of device traces in a strided layout as launch_trace_lde runs it
-        const StridedRows rows{src.get(), at};
-        launch_trace_ingest_probe(rows, L->air.p, (int)B, logn, validate != 0, L->tkeys.p, L->const_col.p, L->const_val.p, s);
-        launch_trace_ingest_write(rows, (int)B, logn, L->const_col.p, L->trace.p, s);
+        launch_trace_front(L, (int)B, logn, TraceFront{TraceFront::IN_PLACE, validate ? TraceFront::AIR : TraceFront::CANONICAL,
+                                                      nullptr, StridedRows{src.get(), at}});
         std::vector<u64> keys(B);
         HIPCHK(hipMemcpyAsync(keys.data(), L->tkeys.p, B * 8, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(classes_out, L->const_col.p, cols, hipMemcpyDeviceToHost, s));
@@ -426,8 +404,11 @@ int xfg_debug_trace_ingest(xfg_ctx* c, uint32_t count, uint64_t n, const uint64_
         HIPCHK(hipMemcpyAsync(trace_out, L->trace.p, cols * n * 8, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         for (size_t k = 0; k < cols; k++) classes_out[k] = (uint8_t)col_class(classes_out[k]);
-        for (size_t b = 0; b < B; b++)
-            faults_out[b] = decode_trace_key(keys[b], ha[b], [&](uint32_t col, u64 step) { return buf[at.at(b, col, step)]; });
+        TraceSrc host;  // `found` comes from the caller's copy of the buffer
+        host.kind = TraceSrc::HOST_STAGED;
+        host.p = buf;
+        host.layout = at;
+        for (size_t b = 0; b < B; b++) faults_out[b] = trace_fault_of(keys[b], ha[b], host, b, nullptr);
         return XFG_OK;
     });
 }
@@ -677,14 +658,8 @@ int xfg_debug_constraint_eval(xfg_ctx* c, uint32_t count, uint64_t n, uint32_t b
             c->err = "trace element or coefficient is not a canonical field element";
             return XFG_INVALID_ARGUMENT;
         }
-        std::vector<AirConst> ha(B);
-        for (size_t b = 0; b < B; b++) {
-            if (!air_canonical(&airs[b])) {
-                c->err = "AIR constant is not a canonical field element";
-                return XFG_INVALID_ARGUMENT;
-            }
-            ha[b] = air_of(&airs[b]);
-        }
+        std::vector<AirConst> ha;
+        if (!airs_of(c, airs, B, ha, L)) return XFG_INVALID_ARGUMENT;
         const ProofShape sh(n, Opts{0, blowup, 0, ext, 8, 31});
         ensure_tables(c, std::max(sh.logn + sh.logbeta, sh.logn + 1));
         ensure_fourstep(c, sh.logn, sh.logbeta);
@@ -694,8 +669,8 @@ int xfg_debug_constraint_eval(xfg_ctx* c, uint32_t count, uint64_t n, uint32_t b
         size_constraint_eval(L, B, sh);
         hipStream_t s = L->stream;
         HIPCHK(hipMemcpy(L->trace.p, trace, B * 7 * n * 8, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(L->air.p, ha.data(), B * sizeof(AirConst), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(L->coeffs.p, coeffs, B * 15 * ext * 8, hipMemcpyHostToDevice));
+        launch_trace_front(L, (int)B, sh.logn, TraceFront{TraceFront::IN_LANE, TraceFront::NONE, nullptr, {}});
         launch_trace_lde(L, T, (int)B, sh, false);
         launch_constraint_eval(L->lde.p, L->air.p, L->coeffs.p, ce_div, L->ce.p, sh.logn, sh.logbeta, (int)B, sh.DE, s,
                                trace_const(L, sh), L->ce_uni.p);

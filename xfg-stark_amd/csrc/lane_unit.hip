@@ -167,31 +167,38 @@ ColConst trace_const(const Lane* c, const ProofShape& sh) {
     return cc;
 }
 
-void launch_trace_lde(Lane* c, const Tables& T, int B, const ProofShape& sh, bool probe, bool generated,
-                      const StridedRows* ingest, bool ingest_validate) {
+void launch_trace_front(Lane* c, int B, int logn, const TraceFront& f) {
+    hipStream_t s = c->stream;
+    // xfg_debug_poison_lde: the planes of constant and shared columns are never written where the live ones
+    // alone are: nothing an earlier unit left there can pass for a plane of this one
+    if (c->poison_lde && f.kind != TraceFront::IN_LANE)
+        HIPCHK(hipMemsetAsync(c->trace.p, 0xFF, ((size_t)B * 7 * 8) << logn, s));
+    // constant columns, and the columns of proofs 1 .. B - 1 that equal proof 0's
+    switch (f.kind) {
+        case TraceFront::GENERATED:  // found in the rows as they are generated
+            launch_trace_probe(c->air.p, B, logn, c->const_col.p, c->const_val.p, s, f.synth);
+            launch_trace_gen(c->air.p, B, logn, c->const_col.p, c->trace.p, s, f.synth);
+            break;
+        case TraceFront::IN_LANE:  // one pass over the trace, behind its check
+            if (f.check != TraceFront::NONE)
+                launch_trace_check(c->trace.p, c->air.p, c->tkeys.p, logn, B, f.check == TraceFront::AIR, s);
+            launch_const_detect(c->trace.p, B * 7, logn, c->const_col.p, s, 7, c->const_val.p);
+            break;
+        case TraceFront::IN_PLACE:  // found, with the check's words, in the caller's buffer where it lies
+            launch_trace_ingest_probe(f.rows, c->air.p, B, logn, f.check == TraceFront::AIR, c->tkeys.p, c->const_col.p,
+                                      c->const_val.p, s);
+            launch_trace_ingest_write(f.rows, B, logn, c->const_col.p, c->trace.p, s);
+            break;
+    }
+}
+
+void launch_trace_lde(Lane* c, const Tables& T, int B, const ProofShape& sh, bool probe) {
     hipStream_t s = c->stream;
     const unsigned char* skip = c->const_col.p;
-    // xfg_debug_poison_lde: nothing an earlier unit left in the buffers can pass for a plane of this one
-    // (the LDE planes and the coefficients of constant and shared columns are never written, nor are
-    // their planes of a generated or an ingested trace: that one is poisoned here, ahead of its writer)
+    // xfg_debug_poison_lde: the LDE planes and the coefficients of constant and shared columns are never written
     if (c->poison_lde) {
         HIPCHK(hipMemsetAsync(c->lde.p, 0xFF, (size_t)B * 7 * sh.N * 8, s));
         HIPCHK(hipMemsetAsync(c->coef.p, 0xFF, (size_t)B * 7 * sh.n * 8, s));
-        if (generated || ingest) HIPCHK(hipMemsetAsync(c->trace.p, 0xFF, (size_t)B * 7 * sh.n * 8, s));
-    }
-    // constant columns, and the columns of proofs 1 .. B - 1 that equal proof 0's
-    if (generated) {
-        // found in the rows as they are generated; then the live columns alone go to c->trace
-        launch_trace_probe(c->air.p, B, sh.logn, c->const_col.p, c->const_val.p, s);
-        launch_trace_gen(c->air.p, B, sh.logn, c->const_col.p, c->trace.p, s);
-    } else if (ingest) {
-        // found, with the check's words, in the caller's buffer where it lies; then the live columns alone go
-        // to c->trace
-        launch_trace_ingest_probe(*ingest, c->air.p, B, sh.logn, ingest_validate, c->tkeys.p, c->const_col.p,
-                                  c->const_val.p, s);
-        launch_trace_ingest_write(*ingest, B, sh.logn, c->const_col.p, c->trace.p, s);
-    } else {  // one pass over the trace
-        launch_const_detect(c->trace.p, B * 7, sh.logn, c->const_col.p, s, 7, c->const_val.p);
     }
     launch_interpolate(c->trace.p, sh.n, c->coef.p, sh.n, c->scratch.p, B * 7, sh.logn, false, sh.n, T, s, skip);
     if (probe) {
@@ -301,40 +308,34 @@ static ReplayView enqueue_commit_chain(Lane* c, const Tables& T, const u64* ce_d
     stage_mark(c, 0);
     const size_t tbytes = (size_t)7 * n * 8;  // one proof's trace
     switch (ts.kind) {
-        case TraceSrc::GENERATED: break;  // launch_trace_lde: classified from the generator, live columns written
+        case TraceSrc::GENERATED: break;
         case TraceSrc::HOST_DIRECT:  // xfg_prove_trace: one trace, straight from the caller's memory
             HIPCHK(hipMemcpyAsync(c->trace.p, ts.p, B * tbytes, hipMemcpyHostToDevice, s));
             break;
         case TraceSrc::HOST_STAGED: {
-            // into the lane's pinned staging (the stream has drained: the last unit's upload is over),
-            // then one asynchronous DMA; a proof refused at submission (cell >= p) is staged as zeros
+            // gathered into the lane's pinned dense staging (the stream has drained: the last unit's upload is
+            // over), then one asynchronous DMA; a proof refused at submission (cell >= p) is staged as zeros
             u64* st = c->h_trace.p;
             const u64* src = ts.p;
             const int* refused = ts.refused;
-            if (ts.strided) {  // traces in another layout are gathered where dense ones are copied
-                const TraceLayout L = ts.layout;
-                host_pool().parallel_for(B, [st, src, refused, n, tbytes, L](int b) {
-                    if (refused[b]) memset(st + (size_t)b * 7 * n, 0, tbytes);
-                    else gather_trace(src + (size_t)b * L.trace_stride, L, n, st + (size_t)b * 7 * n);
-                });
-            } else {
-                host_pool().parallel_for(B, [st, src, refused, n, tbytes](int b) {
-                    if (refused[b]) memset(st + (size_t)b * 7 * n, 0, tbytes);
-                    else memcpy(st + (size_t)b * 7 * n, src + (size_t)b * 7 * n, tbytes);
-                });
-            }
+            const TraceLayout L = ts.layout;
+            host_pool().parallel_for(B, [st, src, refused, n, tbytes, L](int b) {
+                if (refused[b]) memset(st + (size_t)b * 7 * n, 0, tbytes);
+                else gather_trace(src + (size_t)b * L.trace_stride, L, n, st + (size_t)b * 7 * n);
+            });
             HIPCHK(hipMemcpyAsync(c->trace.p, st, B * tbytes, hipMemcpyHostToDevice, s));
             break;
         }
-        case TraceSrc::DEVICE:
-            HIPCHK(hipMemcpyAsync(c->trace.p, ts.p, B * tbytes, hipMemcpyDeviceToDevice, s));
-            break;
-        case TraceSrc::DEVICE_STRIDED: break;  // launch_trace_lde: read where they lie, checked and classified in one pass
+        case TraceSrc::DEVICE: break;  // read where they lie
     }
-    const bool ingested = ts.kind == TraceSrc::DEVICE_STRIDED;
-    const StridedRows rows{ts.p, ts.layout};
-    if (ts.checks() && !ingested) launch_trace_check(c->trace.p, c->air.p, c->tkeys.p, logn, B, ts.validate, s);
-    launch_trace_lde(c, T, B, sh, c->lde_probe, ts.kind == TraceSrc::GENERATED, ingested ? &rows : nullptr, ts.validate);
+    TraceFront front{TraceFront::GENERATED, TraceFront::NONE, nullptr, {}};
+    if (ts.kind != TraceSrc::GENERATED) {
+        front.kind = ts.on_device() ? TraceFront::IN_PLACE : TraceFront::IN_LANE;
+        front.check = ts.validate ? TraceFront::AIR : ts.checks() ? TraceFront::CANONICAL : TraceFront::NONE;
+        if (ts.on_device()) front.rows = StridedRows{ts.p, ts.layout};
+    }
+    launch_trace_front(c, B, logn, front);
+    launch_trace_lde(c, T, B, sh, c->lde_probe);
     stage_mark(c, 1);
     // ---- 2. trace root -> constraint composition coefficients (7 transition + 8 boundary)
     CoinStep cs;

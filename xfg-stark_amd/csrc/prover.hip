@@ -62,7 +62,7 @@ static void worker_main(xfg_ctx* c, int l) {
         L->timing = timing;
         // the unit's own slice of the batch's traces, refusals and key words (halved units too)
         TraceSrc ts = b->trace;
-        if (ts.p) ts.p += (size_t)b0 * (ts.strided ? ts.layout.trace_stride : 7 * b->n);
+        if (ts.p) ts.p += (size_t)b0 * ts.layout.trace_stride;
         if (!b->refused.empty()) ts.refused = b->refused.data() + b0;
         if (!b->keys.empty()) ts.keys = b->keys.data() + b0;
         prove_lane(L, b->T, b->ce_div, b->jobs.data() + b0, b1 - b0, ts, b->n, b->o);
@@ -121,24 +121,6 @@ static void note_status(xfg_ctx* c, const Batch& b, size_t k) {
     if (b.st[k] == XFG_PROVER_ERROR)
         c->err = b.jobs[k].pow_exhausted ? "Prover error: proof-of-work search exhausted"
                                          : "Prover error: proof generation failed (degenerate transcript or DEEP degree)";
-}
-
-// Trace::validate's panic messages (winter-air 0.8)
-static std::string trace_fault_text(const xfg_trace_fault& f) {
-    if (f.kind == 1)
-        return "trace does not satisfy assertion main_trace(" + std::to_string(f.column) + ", " +
-               std::to_string(f.step) + ") == " + std::to_string(f.expected);
-    if (f.kind == 2)
-        return "main transition constraint " + std::to_string(f.index) + " did not evaluate to ZERO at step " +
-               std::to_string(f.step);
-    return f.kind == 3 ? "trace element is not a canonical field element" : "";
-}
-// one cell of a caller's trace buffer (host memory, or device memory of the current device)
-static u64 fetch_cell(const u64* traces, bool on_device, size_t at) {
-    if (!on_device) return traces[at];
-    u64 v = 0;
-    HIPCHK(hipMemcpy(&v, traces + at, 8, hipMemcpyDeviceToHost));
-    return v;
 }
 
 }  // namespace xfg
@@ -273,6 +255,7 @@ int xfg_prove_trace(xfg_ctx* c, const uint64_t* trace, uint32_t width, uint64_t 
         bp->which = {0};
         bp->trace.kind = TraceSrc::HOST_DIRECT;
         bp->trace.p = trace;
+        bp->trace.layout = dense_layout(n);
         std::unique_ptr<Batch> b =
             c->queue.wait(submit_batch(c, std::move(bp), n, o, 1, &out, out_len, nullptr, {Unit{0, 1, -1}}));
         if (b->err) std::rethrow_exception(b->err);
@@ -333,15 +316,10 @@ int xfg_batch_wait(xfg_ctx* c, uint64_t ticket) {
         // caller-supplied traces: what the check found, decoded (the cell of a failed assertion is read
         // from the caller's buffer, which stays theirs until here)
         if (!b->keys.empty()) {
-            const bool dev = b->trace.on_device();
-            if (dev) HIPCHK(hipSetDevice(c->device));
-            const TraceLayout L = b->trace.layout;  // the cell's address comes from the batch's layout
+            if (b->trace.on_device()) HIPCHK(hipSetDevice(c->device));
             for (size_t k = 0; k < b->jobs.size(); k++) {
-                const xfg_trace_fault f = decode_trace_key(b->keys[k], b->jobs[k].air, [&](uint32_t col, u64 step) {
-                    return fetch_cell(b->trace.p, dev, (size_t)L.at(k, col, step));
-                });
+                const xfg_trace_fault f = trace_fault_of(b->keys[k], b->jobs[k].air, b->trace, k, &c->err);
                 if (b->faults) b->faults[b->which[k]] = f;
-                if (f.kind) c->err = trace_fault_text(f);
             }
         }
         return XFG_OK;
@@ -376,31 +354,13 @@ static const char* device_traces_problem(xfg_ctx* c, const void* traces, size_t 
     return nullptr;
 }
 
-// the key of the first cell >= p of a host trace [7][n] in the check kernel's order (step, then
-// column), TRACE_KEY_VALID when every cell is canonical
-static u64 host_noncanonical_key(const u64* tr, u64 n) {
-    u64 key = TRACE_KEY_VALID;
-    for (unsigned col = 0; col < 7; col++)
-        for (u64 s = 0; s < n; s++)
-            if (tr[col * n + s] >= P) {
-                key = std::min(key, trace_key(TRACE_KEY_NONCANONICAL, s, col));
-                break;
-            }
-    return key;
-}
-
-// the layout an entry was given as the library takes it: null (dense, the existing code path) for NULL and
-// for the dense layout spelled out, else the caller's strides
-static const TraceLayout* resolve_layout(const xfg_trace_layout* layout, u64 n, TraceLayout& store) {
-    if (!layout) return nullptr;
-    store = TraceLayout{layout->trace_stride, layout->col_stride, layout->row_stride};
-    return is_dense(store, n) ? nullptr : &store;
-}
+// the dense layout passes for every n and count that the checks in front of it let through (submit_trace_batch:
+// n <= 2^21 and count < 2^32, 7 n count < 2^56; check_traces: n <= 2^32 and count < 2^16, 7 n count < 2^51)
 static const char* const EXTENT_REFUSAL = "trace layout: the extent of the traces overflows or is above 2^58 words";
 
-// xfg_prove_trace_batch_submit (L null: the dense layout) and xfg_prove_trace_batch_strided_submit
+// xfg_prove_trace_batch_submit (L: the dense layout) and xfg_prove_trace_batch_strided_submit
 static int submit_trace_batch(xfg_ctx* c, uint32_t count, const uint64_t* traces, uint32_t width, uint64_t n,
-                              const TraceLayout* L, const xfg_air_consts* airs, const xfg_options* opts, uint32_t flags,
+                              const TraceLayout& L, const xfg_air_consts* airs, const xfg_options* opts, uint32_t flags,
                               uint8_t* const* outs, size_t* out_lens, int* statuses, xfg_trace_fault* faults,
                               uint64_t* ticket) {
     if (!c) return XFG_INVALID_ARGUMENT;
@@ -420,14 +380,11 @@ static int submit_trace_batch(xfg_ctx* c, uint32_t count, const uint64_t* traces
     }
     Opts o = to_opts(opts);
     if (int st = check_request(c, n, o)) return st;
-    for (uint32_t i = 0; i < count; i++)
-        if (!air_canonical(&airs[i])) {  // the constraint kernel subtracts them from trace values
-            c->err = "AIR constant is not a canonical field element";
-            return XFG_INVALID_ARGUMENT;
-        }
+    std::vector<AirConst> ha;
+    if (int st = guarded(c, [&] { return airs_of(c, airs, count, ha) ? XFG_OK : XFG_INVALID_ARGUMENT; })) return st;
     const bool dev = (flags & XFG_TRACE_ON_DEVICE) != 0;
-    u64 extent = (u64)count * 7 * n;  // words from the first cell to the last
-    if (L && !trace_extent(*L, count, n, &extent)) {
+    u64 extent = 0;  // words from the first cell to the last
+    if (!trace_extent(L, count, n, &extent)) {
         c->err = EXTENT_REFUSAL;
         return XFG_INVALID_ARGUMENT;
     }
@@ -443,20 +400,16 @@ static int submit_trace_batch(xfg_ctx* c, uint32_t count, const uint64_t* traces
         bp->refused.assign(count, 0);
         bp->keys.assign(count, TRACE_KEY_VALID);
         for (uint32_t i = 0; i < count; i++) {
-            bp->jobs[i].air = air_of(&airs[i]);
+            bp->jobs[i].air = ha[i];
             bp->which[i] = i;
             statuses[i] = XFG_OK;
         }
         if (!dev) {
             // all_canonical per proof on the host pool (the submitting thread starts every batch's latency)
             u64* keys = bp->keys.data();
-            if (L) {  // through the strides
-                host_pool().parallel_for((int)count, [&](int i) {
-                    keys[i] = host_noncanonical_key(traces + (size_t)i * L->trace_stride, *L, n);
-                });
-            } else {
-                host_pool().parallel_for((int)count, [&](int i) { keys[i] = host_noncanonical_key(traces + (size_t)i * 7 * n, n); });
-            }
+            host_pool().parallel_for((int)count, [&](int i) {
+                keys[i] = host_noncanonical_key(traces + (size_t)i * L.trace_stride, L, n);
+            });
             for (uint32_t i = 0; i < count; i++)
                 if (keys[i] != TRACE_KEY_VALID) {
                     bp->refused[i] = statuses[i] = XFG_INVALID_ARGUMENT;
@@ -464,10 +417,9 @@ static int submit_trace_batch(xfg_ctx* c, uint32_t count, const uint64_t* traces
                 }
             c->stage_traces = true;
         }
-        bp->trace.kind = dev ? (L ? TraceSrc::DEVICE_STRIDED : TraceSrc::DEVICE) : TraceSrc::HOST_STAGED;
+        bp->trace.kind = dev ? TraceSrc::DEVICE : TraceSrc::HOST_STAGED;
         bp->trace.p = traces;
-        bp->trace.layout = L ? *L : dense_layout(n);
-        bp->trace.strided = L != nullptr;
+        bp->trace.layout = L;
         bp->trace.validate = (flags & XFG_TRACE_VALIDATE) != 0;
         bp->faults = faults;
         *ticket = submit_batch(c, std::move(bp), n, o, count, outs, out_lens, statuses,
@@ -480,8 +432,8 @@ int xfg_prove_trace_batch_submit(xfg_ctx* c, uint32_t count, const uint64_t* tra
                                  const xfg_air_consts* airs, const xfg_options* opts, uint32_t flags,
                                  uint8_t* const* outs, size_t* out_lens, int* statuses, xfg_trace_fault* faults,
                                  uint64_t* ticket) {
-    return submit_trace_batch(c, count, traces, width, n, nullptr, airs, opts, flags, outs, out_lens, statuses, faults,
-                              ticket);
+    return submit_trace_batch(c, count, traces, width, n, dense_layout(n), airs, opts, flags, outs, out_lens, statuses,
+                              faults, ticket);
 }
 
 int xfg_prove_trace_batch(xfg_ctx* c, uint32_t count, const uint64_t* traces, uint32_t width, uint64_t n,
@@ -498,9 +450,8 @@ int xfg_prove_trace_batch_strided_submit(xfg_ctx* c, uint32_t count, const uint6
                                          const xfg_trace_layout* layout, const xfg_air_consts* airs,
                                          const xfg_options* opts, uint32_t flags, uint8_t* const* outs, size_t* out_lens,
                                          int* statuses, xfg_trace_fault* faults, uint64_t* ticket) {
-    TraceLayout store{};
-    const TraceLayout* L = resolve_layout(layout, n, store);
-    return submit_trace_batch(c, count, traces, 7, n, L, airs, opts, flags, outs, out_lens, statuses, faults, ticket);
+    return submit_trace_batch(c, count, traces, 7, n, layout_of(layout, n), airs, opts, flags, outs, out_lens, statuses,
+                              faults, ticket);
 }
 
 int xfg_prove_trace_batch_strided(xfg_ctx* c, uint32_t count, const uint64_t* traces, uint64_t n,
@@ -514,8 +465,8 @@ int xfg_prove_trace_batch_strided(xfg_ctx* c, uint32_t count, const uint64_t* tr
     return xfg_batch_wait(c, t);
 }
 
-// xfg_check_traces (L null: the dense layout) and xfg_check_traces_strided
-static int check_traces(xfg_ctx* c, uint32_t count, const uint64_t* traces, uint64_t n, const TraceLayout* L,
+// xfg_check_traces (L: the dense layout) and xfg_check_traces_strided
+static int check_traces(xfg_ctx* c, uint32_t count, const uint64_t* traces, uint64_t n, const TraceLayout& L,
                         const xfg_air_consts* airs, uint32_t flags, xfg_trace_fault* faults) {
     if (!c) return XFG_INVALID_ARGUMENT;
     c->err.clear();
@@ -528,74 +479,65 @@ static int check_traces(xfg_ctx* c, uint32_t count, const uint64_t* traces, uint
                  "XFG_TRACE_ON_DEVICE";
         return XFG_INVALID_ARGUMENT;
     }
-    for (uint32_t i = 0; i < count; i++)
-        if (!air_canonical(&airs[i])) {
-            c->err = "AIR constant is not a canonical field element";
-            return XFG_INVALID_ARGUMENT;
-        }
-    const bool dev = (flags & XFG_TRACE_ON_DEVICE) != 0;
-    const size_t cells = (size_t)count * 7 * n;
-    u64 extent = cells;
-    if (L && !trace_extent(*L, count, n, &extent)) {
+    std::vector<AirConst> ha;
+    if (int st = guarded(c, [&] { return airs_of(c, airs, count, ha) ? XFG_OK : XFG_INVALID_ARGUMENT; })) return st;
+    TraceSrc src;
+    src.kind = (flags & XFG_TRACE_ON_DEVICE) ? TraceSrc::DEVICE : TraceSrc::HOST_STAGED;
+    src.p = traces;
+    src.layout = L;
+    u64 extent = 0;
+    if (!trace_extent(L, count, n, &extent)) {
         c->err = EXTENT_REFUSAL;
         return XFG_INVALID_ARGUMENT;
     }
-    const TraceLayout at = L ? *L : dense_layout(n);
     return on_lane0(c, [&](Lane* lane) -> int {
-        if (const char* m = dev ? device_traces_problem(c, traces, (size_t)extent * 8) : nullptr) {
+        if (const char* m = src.on_device() ? device_traces_problem(c, traces, (size_t)extent * 8) : nullptr) {
             c->err = m;
             return XFG_INVALID_ARGUMENT;
         }
+        const int logn = (int)ilog2(n);
         lane->air.ensure(count);
         lane->tkeys.ensure(count);
-        std::vector<AirConst> ha(count);
-        for (uint32_t i = 0; i < count; i++) ha[i] = air_of(&airs[i]);
         HIPCHK(hipMemcpy(lane->air.p, ha.data(), count * sizeof(AirConst), hipMemcpyHostToDevice));
-        if (L && dev) {
+        if (src.on_device()) {
             // no copy: the ingest's first pass, constraints included, straight on the caller's buffer (only read);
             // its column classes go to the lane's buffers and are not used here
             lane->const_col.ensure(const_flag_bytes((size_t)count * 7));
             lane->const_val.ensure((size_t)count * 7);
-            launch_trace_ingest_probe(StridedRows{traces, at}, lane->air.p, (int)count, (int)ilog2(n), true, lane->tkeys.p,
+            launch_trace_ingest_probe(StridedRows{traces, L}, lane->air.p, (int)count, logn, true, lane->tkeys.p,
                                       lane->const_col.p, lane->const_val.p, lane->stream);
         } else {
+            // host traces: the kernel works on the lane's dense copy (it canonicalises what it reports as >= p)
+            const size_t cells = (size_t)count * 7 * n;
             lane->trace.ensure(cells);
-            // the kernel works on the lane's copy (it canonicalises what it reports as >= p)
-            if (L) {  // host traces in another layout: gathered, one trace per task, then the dense path
-                std::vector<u64> dense(cells);
+            if (is_dense(L, n)) {  // uploaded as they lie (a gather first: a tenth of the rate, profiles/r21)
+                HIPCHK(hipMemcpyAsync(lane->trace.p, traces, cells * 8, hipMemcpyHostToDevice, lane->stream));
+            } else {  // gathered, one trace per task
+                const std::unique_ptr<u64[]> dense(new u64[cells]);
                 host_pool().parallel_for((int)count, [&](int i) {
-                    gather_trace(traces + (size_t)i * at.trace_stride, at, n, dense.data() + (size_t)i * 7 * n);
+                    gather_trace(traces + (size_t)i * L.trace_stride, L, n, dense.get() + (size_t)i * 7 * n);
                 });
-                HIPCHK(hipMemcpy(lane->trace.p, dense.data(), cells * 8, hipMemcpyHostToDevice));
-            } else {
-                HIPCHK(hipMemcpyAsync(lane->trace.p, traces, cells * 8,
-                                      dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, lane->stream));
+                HIPCHK(hipMemcpy(lane->trace.p, dense.get(), cells * 8, hipMemcpyHostToDevice));
             }
-            launch_trace_check(lane->trace.p, lane->air.p, lane->tkeys.p, (int)ilog2(n), (int)count, true, lane->stream);
+            launch_trace_check(lane->trace.p, lane->air.p, lane->tkeys.p, logn, (int)count, true, lane->stream);
         }
         std::vector<u64> keys(count);
         HIPCHK(hipMemcpyAsync(keys.data(), lane->tkeys.p, count * 8, hipMemcpyDeviceToHost, lane->stream));
         HIPCHK(hipStreamSynchronize(lane->stream));
-        for (uint32_t i = 0; i < count; i++) {
-            faults[i] = decode_trace_key(keys[i], ha[i], [&](uint32_t col, u64 step) {
-                return fetch_cell(traces, dev, (size_t)at.at(i, col, step));
-            });
-            if (faults[i].kind) c->err = trace_fault_text(faults[i]);
-        }
+        for (uint32_t i = 0; i < count; i++) faults[i] = trace_fault_of(keys[i], ha[i], src, i, &c->err);
         return XFG_OK;
     });
 }
 
 int xfg_check_traces(xfg_ctx* c, uint32_t count, const uint64_t* traces, uint64_t n, const xfg_air_consts* airs,
                      uint32_t flags, xfg_trace_fault* faults) {
-    return check_traces(c, count, traces, n, nullptr, airs, flags, faults);
+    return check_traces(c, count, traces, n, dense_layout(n), airs, flags, faults);
 }
 
 int xfg_check_traces_strided(xfg_ctx* c, uint32_t count, const uint64_t* traces, uint64_t n,
                              const xfg_trace_layout* layout, const xfg_air_consts* airs, uint32_t flags,
                              xfg_trace_fault* faults) {
-    TraceLayout store{};
-    return check_traces(c, count, traces, n, resolve_layout(layout, n, store), airs, flags, faults);
+    return check_traces(c, count, traces, n, layout_of(layout, n), airs, flags, faults);
 }
 
 int xfg_prepare(xfg_ctx* c, uint32_t count, uint64_t trace_length, const xfg_options* opts) {

@@ -52,7 +52,8 @@ struct Lane {
     hipEvent_t lde_ev[2] = {};
     double lde_ms = 0;
     u64 lde_sets = 0, lde_polys = 0;
-    // xfg_debug_poison_lde: launch_trace_lde sets c->lde, c->coef and a generated unit's c->trace to 0xFF bytes first
+    // xfg_debug_poison_lde: launch_trace_lde sets c->lde and c->coef to 0xFF bytes first, launch_trace_front the
+    // c->trace of a unit whose live planes alone it writes
     bool poison_lde = false;
     DBuf<AirConst> air;
     DBuf<CeUniform> ce_uni;  // [B] launch_constraint_eval's per-proof uniform part (constant trace columns)
@@ -112,20 +113,19 @@ struct Lane {
     }
 };
 
-// where a unit's traces come from, and what is checked on the way. p: the unit's own slice [B][7][n]
+// where a unit's traces come from, and what is checked on the way. p: cell (0, 0, 0) of the unit's own slice
 // (null: generated on the device from the AIR constants)
-// DEVICE_STRIDED: device traces in a layout other than the dense one; they are never copied, the unit's
-// front end reads them where they lie (launch_trace_lde). HOST_STAGED with `strided` set: host traces in such
-// a layout, gathered into the lane's staging where dense ones are copied into it
 struct TraceSrc {
-    enum Kind { GENERATED, HOST_DIRECT, HOST_STAGED, DEVICE, DEVICE_STRIDED };
+    enum Kind { GENERATED, HOST_DIRECT, HOST_STAGED, DEVICE };
     Kind kind = GENERATED;
     const u64* p = nullptr;
-    // where the cells lie from p on (batches of caller-supplied traces: the dense layout unless `strided`); a
-    // unit's slice starts trace_stride words per proof further on
+    // where the cells lie from p on: dense_layout(n) unless the caller gave another. A unit's slice starts
+    // trace_stride words per proof further on
     TraceLayout layout{0, 0, 0};
-    bool strided = false;
-    bool on_device() const { return kind == DEVICE || kind == DEVICE_STRIDED; }
+    // read where they lie, or copied into the lane's dense [B][7][n] first: device traces, in whatever layout, are
+    // never copied (the IN_PLACE front end, launch_trace_front; check_traces); host traces are gathered into the
+    // lane's staging
+    bool on_device() const { return kind == DEVICE; }
     bool validate = false;        // XFG_TRACE_VALIDATE: the AIR check behind the upload
     bool size_staging = false;    // grow the lane's pinned trace staging with its other buffers
     const int* refused = nullptr;  // [B] non-zero: refused at submission, the slot is proven over zeros
@@ -143,8 +143,8 @@ struct Batch {
     size_t* out_lens = nullptr;    // caller capacities in, proof lengths out
     int* statuses = nullptr;       // caller statuses, written by wait
     std::vector<int> st;           // per-job copy-out status
-    // caller-supplied traces [jobs][7][n] (job k <-> caller index k: such a batch keeps refused proofs
-    // as jobs so that every unit's slice stays at b0 * 7 * n); trace.p is the batch's base
+    // caller-supplied traces, trace.p the batch's base (job k <-> caller index k: such a batch keeps refused
+    // proofs as jobs so that every unit's slice stays at b0 * trace.layout.trace_stride)
     TraceSrc trace;
     std::vector<int> refused;          // per job: status set at submission (cell >= p), else 0
     std::vector<u64> keys;             // per job: the trace check's word
@@ -244,20 +244,29 @@ void prove_lane(Lane* c, const Tables& T, const u64* ce_div, ProofJob* jobs, int
 void size_trace_lde(Lane* c, size_t B, const ProofShape& sh);        // trace, coef, scratch, lde
 void size_constraint_eval(Lane* c, size_t B, const ProofShape& sh);  // air, coeffs, ce, ce_uni
 void size_ood_deep(Lane* c, size_t B, const ProofShape& sh);  // hcoef, zpts, partial, ood, dp, carry, deep
-// trace -> coefficients -> LDE (DefaultTraceLde::new); probe: the xfg_lde_probe events around the LDE.
-// Constant columns, and columns equal to proof 0's, are detected from the values and not transformed: the
-// flags stay in c->const_col, the values in c->const_val, and their planes of c->coef and c->lde are left
-// unwritten. Whatever reads either afterwards takes trace_const along.
-// generated = false: the trace lies in c->trace (whatever put it there) and is read there, one pass
-// (launch_const_detect). generated = true: the unit's traces are those of the burn row generator on c->air
-// and are classified as it produces them (launch_trace_probe); then launch_trace_gen writes the live
-// columns alone to c->trace, so the trace planes of constant and shared columns hold nothing either
-// ingest (generated = false): the unit's traces lie in the caller's device memory behind *ingest and are not in
-// c->trace: one pass finds the check's words (c->tkeys, AIR constraints included when ingest_validate), the
-// flags and the values (launch_trace_ingest_probe on c->air), a second writes the canonical live columns to
-// c->trace (launch_trace_ingest_write); the planes of the others hold nothing, as for a generated unit
-void launch_trace_lde(Lane* c, const Tables& T, int B, const ProofShape& sh, bool probe, bool generated = false,
-                      const StridedRows* ingest = nullptr, bool ingest_validate = false);
+// The front end of a unit's trace: whatever the source, it leaves the live columns in c->trace [B][7][n], the
+// classes of the columns (constant, equal to proof 0's, live) in c->const_col, element 0 of every column in
+// c->const_val and, where the source is checked, the check's word per proof in c->tkeys; c->air holds the
+// unit's AIR constants.
+// GENERATED: the rows of the burn row generator on c->air (synth: the synthetic generator, debug) are
+//   classified as they are produced (launch_trace_probe), then launch_trace_gen writes the live columns alone.
+// IN_LANE: the traces lie in c->trace (whatever put them there): launch_trace_check unless check is NONE (it
+//   canonicalises the cells it reports as >= p), then one pass for the classes (launch_const_detect).
+// IN_PLACE: the traces lie in device memory behind `rows` and are not copied: one pass finds the words
+//   (canonicity, and the AIR's constraints when check is AIR), the classes and the values
+//   (launch_trace_ingest_probe), a second writes the canonical live columns (launch_trace_ingest_write).
+// GENERATED and IN_PLACE leave the planes of constant and shared columns of c->trace unwritten
+struct TraceFront {
+    enum Kind { GENERATED, IN_LANE, IN_PLACE } kind;
+    enum Check { NONE, CANONICAL, AIR } check;
+    const SynthRowGen* synth;
+    StridedRows rows;
+};
+void launch_trace_front(Lane* c, int B, int logn, const TraceFront& f);
+// trace -> coefficients -> LDE (DefaultTraceLde::new) behind launch_trace_front; probe: the xfg_lde_probe
+// events around the LDE. The columns flagged in c->const_col are not transformed: their planes of c->coef and
+// c->lde are left unwritten, and whatever reads either afterwards takes trace_const along
+void launch_trace_lde(Lane* c, const Tables& T, int B, const ProofShape& sh, bool probe);
 ColConst trace_const(const Lane* c, const ProofShape& sh);
 // the proof-of-work search on the device for the B seeds the caller wrote to grind_seeds(c, B): launched on
 // the lane's gather stream (idle between a unit's chain and its gathers) and waited for. Returns the B
@@ -276,10 +285,45 @@ static inline bool air_canonical(const xfg_air_consts* a) {
     return all_canonical(a->pub_inputs, 12) && a->nullifier < P && a->commitment < P;
 }
 
-// the trace check's word (trace_key, trace_layout.hpp) as the C ABI reports it; cell(column, step) fetches
-// that cell of the proof's trace as the caller holds it
-template <class Cell>
-static xfg_trace_fault decode_trace_key(u64 key, const AirConst& A, Cell cell) {
+// `count` AIR constants of a caller as the kernels take them, into out; false, with the text in c->err, when
+// one is not canonical (the constraint kernel subtracts them from trace values). up: copied to that lane's
+// c->air as well, before the call returns
+static bool airs_of(xfg_ctx* c, const xfg_air_consts* airs, size_t count, std::vector<AirConst>& out, Lane* up = nullptr) {
+    out.resize(count);
+    for (size_t i = 0; i < count; i++) {
+        if (!air_canonical(&airs[i])) {
+            c->err = "AIR constant is not a canonical field element";
+            return false;
+        }
+        out[i] = air_of(&airs[i]);
+    }
+    if (up) {
+        up->air.ensure(count);
+        HIPCHK(hipMemcpy(up->air.p, out.data(), count * sizeof(AirConst), hipMemcpyHostToDevice));
+    }
+    return true;
+}
+
+// the layout an entry was given: NULL is the dense one
+static inline TraceLayout layout_of(const xfg_trace_layout* layout, u64 n) {
+    return layout ? TraceLayout{layout->trace_stride, layout->col_stride, layout->row_stride} : dense_layout(n);
+}
+
+// Trace::validate's panic messages (winter-air 0.8)
+static std::string trace_fault_text(const xfg_trace_fault& f) {
+    if (f.kind == 1)
+        return "trace does not satisfy assertion main_trace(" + std::to_string(f.column) + ", " +
+               std::to_string(f.step) + ") == " + std::to_string(f.expected);
+    if (f.kind == 2)
+        return "main transition constraint " + std::to_string(f.index) + " did not evaluate to ZERO at step " +
+               std::to_string(f.step);
+    return f.kind == 3 ? "trace element is not a canonical field element" : "";
+}
+
+// the trace check's word (trace_key, trace_layout.hpp) for trace i of src as the C ABI reports it: the cell of
+// a failed assertion or of a value >= p is read from the caller's buffer through the layout (host memory, or
+// device memory of the current device: one 8-byte copy); the text of a fault goes to *err (null: nowhere)
+static xfg_trace_fault trace_fault_of(u64 key, const AirConst& A, const TraceSrc& src, size_t i, std::string* err) {
     xfg_trace_fault f{};
     if (key == TRACE_KEY_VALID) return f;
     const unsigned kind = (unsigned)(key >> 62), idx = (unsigned)(key & 7);
@@ -287,19 +331,22 @@ static xfg_trace_fault decode_trace_key(u64 key, const AirConst& A, Cell cell) {
     if (kind == TRACE_KEY_TRANSITION) {
         f.kind = 2;
         f.index = idx;
-        return f;
-    }
-    if (kind == TRACE_KEY_ASSERTION) {
-        const u64 asserted[8] = {A.pub[0], A.pub[1], A.pub[2], A.pub[3], 0, A.nullifier, A.commitment, AIR_LAST_STATE};
-        f.kind = 1;
-        f.index = idx;
-        f.column = idx < 7 ? idx : 4;
-        f.expected = asserted[idx];
     } else {
-        f.kind = 3;
-        f.column = idx;
+        if (kind == TRACE_KEY_ASSERTION) {
+            const u64 asserted[8] = {A.pub[0], A.pub[1], A.pub[2], A.pub[3], 0, A.nullifier, A.commitment, AIR_LAST_STATE};
+            f.kind = 1;
+            f.index = idx;
+            f.column = idx < 7 ? idx : 4;
+            f.expected = asserted[idx];
+        } else {
+            f.kind = 3;
+            f.column = idx;
+        }
+        const u64* cell = src.p + src.layout.at(i, f.column, f.step);
+        if (src.on_device()) HIPCHK(hipMemcpy(&f.found, cell, 8, hipMemcpyDeviceToHost));
+        else f.found = *cell;
     }
-    f.found = cell(f.column, f.step);
+    if (err) *err = trace_fault_text(f);
     return f;
 }
 

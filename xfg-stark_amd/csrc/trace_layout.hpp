@@ -6,6 +6,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #if defined(__HIPCC__)
 #define XFG_HD __host__ __device__
@@ -56,19 +57,32 @@ inline bool trace_extent(const TraceLayout& L, uint64_t count, uint64_t n, uint6
 }
 
 // the key of the first cell >= p of one host trace (tr: its cell (0, 0)) in the check kernel's order, step
-// then column; TRACE_KEY_VALID when every cell is canonical
+// then column; TRACE_KEY_VALID when every cell is canonical. Whole columns are scanned one after the other when
+// their cells are neighbours (the smallest key over the columns' first offenders), rows otherwise: the same key
 inline uint64_t host_noncanonical_key(const uint64_t* tr, const TraceLayout& L, uint64_t n) {
+    uint64_t key = TRACE_KEY_VALID;
+    if (L.row_stride == 1) {
+        for (unsigned c = 0; c < 7; c++) {
+            const uint64_t* col = tr + c * L.col_stride;
+            for (uint64_t s = 0; s < n; s++)
+                if (col[s] >= TRACE_FIELD_P) {
+                    const uint64_t k = trace_key(TRACE_KEY_NONCANONICAL, s, c);
+                    key = k < key ? k : key;
+                    break;
+                }
+        }
+        return key;
+    }
     for (uint64_t s = 0; s < n; s++)
         for (unsigned c = 0; c < 7; c++)
             if (tr[L.at(0, c, s)] >= TRACE_FIELD_P) return trace_key(TRACE_KEY_NONCANONICAL, s, c);
-    return TRACE_KEY_VALID;
+    return key;
 }
 
 // one host trace (tr: its cell (0, 0)) into the dense dst [7][n]
 inline void gather_trace(const uint64_t* tr, const TraceLayout& L, uint64_t n, uint64_t* dst) {
-    if (L.row_stride == 1) {  // whole columns
-        for (unsigned c = 0; c < 7; c++)
-            for (uint64_t s = 0; s < n; s++) dst[c * n + s] = tr[c * L.col_stride + s];
+    if (L.row_stride == 1) {  // whole columns: of the dense layout, the trace's 7 n words as they lie
+        for (unsigned c = 0; c < 7; c++) memcpy(dst + c * n, tr + c * L.col_stride, n * 8);
         return;
     }
     for (uint64_t s = 0; s < n; s++) {  // row by row: a row's cells are neighbours in the usual sources
