@@ -245,7 +245,8 @@ int xfg_proof_parse(const uint8_t* proof, size_t len, xfg_proof_info* info, char
 
 /* winterfell::verify::<XfgBurnMintAir, Blake3_256, DefaultRandomCoin> with
  * AcceptableOptions::OptionSet([*acceptable])  <- XfgBurnMintVerifier::verify_with_public_inputs /
- * verify_with_winterfell, src/burn_mint_verifier.rs:186-203, 265-283. The statement is the AIR
+ * verify_with_winterfell, src/burn_mint_verifier.rs:186-203, 265-283 (the reference passes a one-element
+ * set, :271; xfg_verify_acceptable takes the whole policy argument). The statement is the AIR
  * constants (12 public inputs + nullifier + commitment, see xfg_burn_air_consts). XFG_OK = accepted;
  * XFG_VERIFY_FAILED = rejected, err receives the VerifierError (Debug form, e.g.
  * "InconsistentOodConstraintEvaluations"). */
@@ -261,6 +262,48 @@ int xfg_verify_batch(uint32_t count, const uint8_t* const* proofs, const size_t*
  * runs the per-query DEEP / FRI / remainder checks. results[i] as xfg_verify. */
 int xfg_verify_batch_gpu(xfg_ctx* ctx, uint32_t count, const uint8_t* const* proofs, const size_t* lens,
                          const xfg_air_consts* airs, const xfg_options* acceptable, int* results);
+
+/* ---- the verifiers' policy argument: winterfell::AcceptableOptions (winter-verifier 0.8) ----
+ * Which proofs a verifier takes is the verifying side's decision: a set of option sets, or a minimum
+ * conjectured security level. Kind 2 is reserved for AcceptableOptions::MinProvenSecurity, which is not
+ * offered (its bound is a floating-point search over list-decoding parameters that cannot be restated
+ * reliably here); kind 2 and every other unknown kind is refused. */
+#define XFG_ACCEPT_OPTION_SET 0u               /* AcceptableOptions::OptionSet */
+#define XFG_ACCEPT_MIN_CONJECTURED_SECURITY 1u /* AcceptableOptions::MinConjecturedSecurity */
+typedef struct {
+    uint32_t kind;
+    uint32_t min_security;      /* bits, kind 1 */
+    const xfg_options* options; /* kind 0: num_options entries, 1..32 */
+    uint32_t num_options;
+} xfg_acceptable;
+/* StarkProof::security_level(conjectured = true) of a proof of this shape (winter-air 0.8
+ * get_conjectured_security for the 64-bit field and Blake3_256): min(min(64 field_extension -
+ * log2(trace_length blowup_factor), log2(blowup_factor) num_queries [+ grinding_factor when that product is at
+ * least 80]) - 1, 128). The cap of 128 needs the cubic extension and is never reached here.
+ * XFG_INVALID_ARGUMENT for a null pointer and for a shape outside the supported set (xfg_options, and a trace
+ * length that is no power of two in [8, 2^21]) */
+int xfg_security_level(uint64_t trace_length, const xfg_options* opts, uint32_t* bits);
+/* xfg_verify, xfg_verify_batch and xfg_verify_batch_gpu under a policy; each of the three above is its
+ * namesake here with the one-element set {*acceptable}: same verdicts, same error texts.
+ * The order of the checks, as in Winterfell: (1) StarkProof::from_bytes errors; (2) the policy, on the
+ * options and trace length the proof states, before its transcript is touched -- a set answers
+ * "UnacceptableProofOptions" unless one member equals all six option fields, a minimum answers
+ * "InsufficientConjecturedSecurity(<required>, <the proof's>)", and a proof that is below the minimum and
+ * tampered with as well reports the policy error; (3) the library's own limits, which also answer
+ * "UnacceptableProofOptions": the cubic field extension, a last FRI layer below the blowup factor, and the
+ * LDE size limits of xfg_options. Under a minimum-security policy (3) rejects proofs that Winterfell would
+ * go on to verify.
+ * Refused with XFG_INVALID_ARGUMENT, nothing verified and nothing launched: a null policy, a kind other than
+ * 0 or 1, kind 0 with null options or with num_options 0 or above 32 (and what the namesake refuses).
+ * On the GPU one batch may hold proofs of any mix of options the policy takes, every folding factor included:
+ * results[i] belongs to proofs[i] whatever their order. */
+int xfg_verify_acceptable(const uint8_t* proof, size_t len, const xfg_air_consts* air,
+                          const xfg_acceptable* acceptable, char* err, size_t err_len);
+int xfg_verify_batch_acceptable(uint32_t count, const uint8_t* const* proofs, const size_t* lens,
+                                const xfg_air_consts* airs, const xfg_acceptable* acceptable, int* results,
+                                uint32_t threads);
+int xfg_verify_batch_gpu_acceptable(xfg_ctx* ctx, uint32_t count, const uint8_t* const* proofs, const size_t* lens,
+                                    const xfg_air_consts* airs, const xfg_acceptable* acceptable, int* results);
 
 /* ---- instrumentation (benchmarks / parity tests) ---- */
 /* host BLAKE3 of the library (any length), for self-tests */
@@ -483,6 +526,12 @@ int xfg_grind_probe(const xfg_ctx* ctx, uint32_t* device_min, uint64_t* device_s
 int xfg_debug_verify_batch_gpu(xfg_ctx* ctx, uint32_t count, const uint8_t* const* proofs, const size_t* lens,
                                const xfg_air_consts* airs, const xfg_options* acceptable, int* results,
                                uint64_t* flags, char* errs, size_t err_stride);
+/* the same for xfg_verify_batch_gpu_acceptable: the policy in place of the options. flags[i] and errs + i *
+ * err_stride belong to proofs[i], wherever the device's per-folding-factor ranges put its queries */
+int xfg_debug_verify_batch_gpu_acceptable(xfg_ctx* ctx, uint32_t count, const uint8_t* const* proofs,
+                                          const size_t* lens, const xfg_air_consts* airs,
+                                          const xfg_acceptable* acceptable, int* results, uint64_t* flags, char* errs,
+                                          size_t err_stride);
 
 #ifdef __cplusplus
 }

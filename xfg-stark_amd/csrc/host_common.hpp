@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/xfg_stark.h"
+#include "acceptable.hpp"
 #include "gl.hpp"
 #include "host_crypto.hpp"
 
@@ -18,36 +19,9 @@ static inline unsigned ilog2(u64 x) {
     while ((1ULL << r) < x) r++;
     return r;
 }
-static inline bool is_pow2(u64 x) { return x && !(x & (x - 1)); }
 
 // ------------------------------------------------------------------ options / context elements
-struct Opts {
-    u64 q, beta, grind, ext, fold, remdeg;
-};
-static inline Opts to_opts(const xfg_options* o) {
-    return Opts{o->num_queries, o->blowup_factor, o->grinding_factor, o->field_extension, o->fri_folding_factor,
-                o->fri_remainder_max_degree};
-}
-// blowup 32, 64, 128 (LDEs composed of blowup-16 transforms): n * beta is limited to the largest LDE proven
-// at blowup 16, 2^20 x 16
-constexpr u64 WIDE_LDE_MAX = 1ULL << 24;
-static inline bool wide_lde_too_large(u64 n, u64 beta) { return beta > 16 && n > WIDE_LDE_MAX / beta; }
-// check_options' answer to that rule (check_request names the sizes when it is this one that failed)
-constexpr const char* WIDE_LDE_REFUSAL = "blowup factors above 16 need an LDE domain of at most 2^24 points";
-// ProofOptions::new validation (winter-air 0.8) + what this GPU path implements
-static inline const char* check_options(u64 n, const Opts& o) {
-    if (!is_pow2(n) || n < 8) return "trace length must be a power of two and at least 8";
-    if (n > (1ULL << 21)) return "trace length above 2^21 is not supported";
-    if (!is_pow2(o.beta) || o.beta < 2 || o.beta > 128) return "blowup factor must be a power of two in [2, 128]";
-    if (o.q < 1 || o.q > 255) return "number of queries must be in [1, 255]";
-    if (o.grind > 32) return "grinding factor cannot be greater than 32";
-    if (o.ext != 1 && o.ext != 2) return "field extension must be None (1) or Quadratic (2)";
-    if (o.fold != 2 && o.fold != 4 && o.fold != 8 && o.fold != 16) return "FRI folding factor must be 2, 4, 8 or 16";
-    if (o.remdeg > 255 || !is_pow2(o.remdeg + 1)) return "FRI remainder max degree must be one less than a power of two";
-    if (o.q >= n * o.beta) return "number of queries must be smaller than the LDE domain size";
-    if (wide_lde_too_large(n, o.beta)) return WIDE_LDE_REFUSAL;
-    return nullptr;
-}
+// Opts, to_opts and check_options (ProofOptions::new validation + what this GPU path implements): acceptable.hpp
 static inline unsigned num_fri_layers(u64 N, const Opts& o) {
     u64 maxrem = (o.remdeg + 1) * o.beta;
     unsigned k = 0;

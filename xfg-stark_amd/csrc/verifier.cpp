@@ -223,15 +223,21 @@ static void air_transition(const AirConst& a, const E2 cur[7], const E2 nxt[7], 
 static E2 elem_e(const Span& s, size_t i, int de) { return de == 2 ? E2{s.elem(2 * i), s.elem(2 * i + 1)} : e2(s.elem(i)); }
 
 // returns "" when the proof verifies, else the VerifierError (Debug form)
-std::string verify_transcript(const uint8_t* bytes, size_t len, const AirConst& air, const Opts& acceptable,
+std::string verify_transcript(const uint8_t* bytes, size_t len, const AirConst& air, const Acceptable& acceptable,
                               VState& st) {
     ParsedProof& pf = st.pf;
     std::string e = parse_proof(bytes, len, pf);
     if (!e.empty()) return e;
     if (pf.width != 7 || pf.aux != 0) return "InconsistentTraceWidth";
-    const Opts& o = pf.o;
-    if (memcmp(&o, &acceptable, sizeof o)) return "UnacceptableProofOptions";  // AcceptableOptions::OptionSet
+    const Opts& o = pf.o;  // from here on the proof's own options: the caller's policy is not read again
     const u64 n = 1ULL << pf.logn;
+    {
+        char buf[POLICY_ERROR_LEN];
+        const char* refused = policy_error(acceptable, n, o, buf);  // AcceptableOptions::validate
+        if (*refused) return refused;
+    }
+    // the library's own limits, after the policy: what a minimum-security policy lets through and the prover
+    // and verifiers do not implement (cubic extension, LDE sizes) is not acceptable either
     if (check_options(n, o)) return "UnacceptableProofOptions";
     // folding factors 2, 4, 16: options whose last layer is smaller than the blowup leave the remainder no
     // coefficient (the prover refuses them too, check_request); every layer below then has >= 1 row
@@ -470,7 +476,7 @@ std::string verify_queries_host(const VState& st) {
     return finish_proof(st, plan.broken, flags);
 }
 
-static std::string verify_proof(const uint8_t* bytes, size_t len, const AirConst& air, const Opts& acceptable) {
+static std::string verify_proof(const uint8_t* bytes, size_t len, const AirConst& air, const Acceptable& acceptable) {
     VState st;
     std::string e = verify_transcript(bytes, len, air, acceptable, st);
     return e.empty() ? verify_queries_host(st) : e;
@@ -489,6 +495,34 @@ static void put_err(const std::string& e, char* buf, size_t len) {
     size_t k = std::min(len - 1, e.size());
     memcpy(buf, e.data(), k);
     buf[k] = 0;
+}
+
+// the body of xfg_verify and xfg_verify_acceptable
+static int verify_one(const uint8_t* proof, size_t len, const xfg_air_consts* air, const Acceptable& acceptable,
+                      char* err, size_t err_len) {
+    std::string e;
+    try {
+        e = verify_proof(proof, len, air_of(air), acceptable);
+    } catch (const std::exception& x) {
+        e = std::string("ProofDeserializationError(\"") + x.what() + "\")";
+    }
+    put_err(e, err, err_len);
+    return e.empty() ? XFG_OK : XFG_VERIFY_FAILED;
+}
+// the body of xfg_verify_batch and xfg_verify_batch_acceptable
+static int verify_batch_host(uint32_t count, const uint8_t* const* proofs, const size_t* lens,
+                             const xfg_air_consts* airs, const Acceptable& acceptable, int* results, uint32_t threads) {
+    unsigned nt = threads ? threads : std::max(1u, std::thread::hardware_concurrency());
+    nt = std::min<unsigned>(nt, std::max<uint32_t>(1, count));
+    std::vector<std::thread> th;
+    for (unsigned t = 0; t < nt; t++)
+        th.emplace_back([&, t] {
+            for (uint32_t i = t; i < count; i += nt)
+                results[i] = proofs[i] ? verify_one(proofs[i], lens[i], &airs[i], acceptable, nullptr, 0)
+                                       : XFG_INVALID_ARGUMENT;
+        });
+    for (auto& x : th) x.join();
+    return XFG_OK;
 }
 
 }  // namespace xfg
@@ -532,14 +566,19 @@ int xfg_proof_parse(const uint8_t* proof, size_t len, xfg_proof_info* info, char
 int xfg_verify(const uint8_t* proof, size_t len, const xfg_air_consts* air, const xfg_options* acceptable, char* err,
                size_t err_len) {
     if (!proof || !air || !acceptable) return XFG_INVALID_ARGUMENT;
-    std::string e;
-    try {
-        e = verify_proof(proof, len, air_of(air), to_opts(acceptable));
-    } catch (const std::exception& x) {
-        e = std::string("ProofDeserializationError(\"") + x.what() + "\")";
-    }
-    put_err(e, err, err_len);
-    return e.empty() ? XFG_OK : XFG_VERIFY_FAILED;
+    return verify_one(proof, len, air, acceptable_one(to_opts(acceptable)), err, err_len);
+}
+int xfg_verify_acceptable(const uint8_t* proof, size_t len, const xfg_air_consts* air,
+                          const xfg_acceptable* acceptable, char* err, size_t err_len) {
+    Acceptable a;
+    if (!proof || !air || !make_acceptable(acceptable, a)) return XFG_INVALID_ARGUMENT;
+    return verify_one(proof, len, air, a, err, err_len);
+}
+
+int xfg_security_level(uint64_t trace_length, const xfg_options* opts, uint32_t* bits) {
+    if (!opts || !bits || check_options(trace_length, to_opts(opts))) return XFG_INVALID_ARGUMENT;
+    *bits = conjectured_security(trace_length, to_opts(opts));
+    return XFG_OK;
 }
 
 int xfg_selftest_blake3(const uint8_t* in, size_t len, uint8_t out[32]) {
@@ -552,17 +591,14 @@ int xfg_selftest_blake3(const uint8_t* in, size_t len, uint8_t out[32]) {
 int xfg_verify_batch(uint32_t count, const uint8_t* const* proofs, const size_t* lens, const xfg_air_consts* airs,
                      const xfg_options* acceptable, int* results, uint32_t threads) {
     if (!proofs || !lens || !airs || !acceptable || !results) return XFG_INVALID_ARGUMENT;
-    unsigned nt = threads ? threads : std::max(1u, std::thread::hardware_concurrency());
-    nt = std::min<unsigned>(nt, std::max<uint32_t>(1, count));
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < nt; t++)
-        th.emplace_back([&, t] {
-            for (uint32_t i = t; i < count; i += nt)
-                results[i] = proofs[i] ? xfg_verify(proofs[i], lens[i], &airs[i], acceptable, nullptr, 0)
-                                       : XFG_INVALID_ARGUMENT;
-        });
-    for (auto& x : th) x.join();
-    return XFG_OK;
+    return verify_batch_host(count, proofs, lens, airs, acceptable_one(to_opts(acceptable)), results, threads);
+}
+int xfg_verify_batch_acceptable(uint32_t count, const uint8_t* const* proofs, const size_t* lens,
+                                const xfg_air_consts* airs, const xfg_acceptable* acceptable, int* results,
+                                uint32_t threads) {
+    Acceptable a;
+    if (!proofs || !lens || !airs || !results || !make_acceptable(acceptable, a)) return XFG_INVALID_ARGUMENT;
+    return verify_batch_host(count, proofs, lens, airs, a, results, threads);
 }
 
 }  // extern "C"

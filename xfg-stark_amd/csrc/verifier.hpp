@@ -57,9 +57,10 @@ struct VState {
     std::vector<u64> pos;  // unique query positions (sorted)
     VFieldProof f{};       // z, zg, hz, gam, dc, ood, falpha, de, logN; the rest is plan_proof's
 };
-// parse, option checks, transcript replay, OOD consistency, proof of work, query positions:
-// "" when the proof may proceed to the query checks, else the VerifierError
-std::string verify_transcript(const uint8_t* bytes, size_t len, const AirConst& air, const Opts& acceptable,
+// parse, the caller's policy (acceptable.hpp policy_error), the library's own option limits, transcript replay,
+// OOD consistency, proof of work, query positions: "" when the proof may proceed to the query checks, else the
+// VerifierError. Everything behind the policy check reads the proof's own options (st.pf.o)
+std::string verify_transcript(const uint8_t* bytes, size_t len, const AirConst& air, const Acceptable& acceptable,
                               VState& st);
 
 AirConst air_of(const xfg_air_consts* a);
@@ -68,9 +69,11 @@ AirConst air_of(const xfg_air_consts* a);
 // Merkle openings and its queries as records of blob offsets (verify_checks.hpp). The batched GPU
 // verifier uploads many proofs' records and runs vtree_kernel (one workgroup per opening: leaf hashes,
 // BatchMerkleProof::get_root level by level, root comparison) and vfield_kernel<LOGF> (one thread per
-// query: query_bits; every planned proof has the acceptable options' folding factor `fold`, which
-// launch_verify takes: 2, 4, 8 or 16, anything else throws). The host verifier walks the same records
-// serially over the proof's own bytes (verify_queries_host). Both hand their flag word to finish_proof.
+// query: query_bits). A batch may mix folding factors: its query records lie in four contiguous ranges, one
+// per factor 2, 4, 8, 16 (acceptable.hpp bucket_queries), and launch_verify launches one instantiation per
+// non-empty range; the tree records are per-tree generic and stay in input order. The host verifier walks
+// the same records serially over the proof's own bytes (verify_queries_host), with the instantiation of the
+// proof's own factor. Both hand their flag word to finish_proof.
 // one proof's part of a batch (blob offsets already global; tree / vector / proof indices local)
 struct VerifyPlan {
     std::vector<VTree> trees;
@@ -95,7 +98,9 @@ std::string finish_proof(const VState& st, int broken, u64 flags);
 // the query checks on the host: plan_proof over the proof's own bytes, every opening, every query
 std::string verify_queries_host(const VState& st);
 
+// fq: the batch's query records, range r = [ranges.begin[r], ranges.begin[r + 1]) those of folding factor 2^(r + 1);
+// an empty range launches nothing (nor do zero trees)
 void launch_verify(const uint8_t* blob, const VTree* trees, u64 ntrees, const VTreeLeaf* tleaves, const VVec* vecs,
-                   const VFieldProof* fp, const VFieldQuery* fq, u64 nq, int fold, u64* flags, hipStream_t s);
+                   const VFieldProof* fp, const VFieldQuery* fq, const FoldRanges& ranges, u64* flags, hipStream_t s);
 
 }  // namespace xfg

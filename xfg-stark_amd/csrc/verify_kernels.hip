@@ -134,7 +134,8 @@ __global__ __launch_bounds__(256) void vtree_kernel(const uint8_t* blob, const V
 }
 
 // one thread per (proof, query): query_bits (verify_checks.hpp), its failures set in flags[proof].
-// F = 2^LOGF: the folding factor of every proof of the batch (the acceptable options')
+// F = 2^LOGF: the folding factor of every proof that has a record in fq[0 .. nq), one of the batch's four
+// ranges (launch_verify); Q.proof indexes the whole batch's fp and flags
 template <int LOGF>
 __global__ __launch_bounds__(64) void vfield_kernel(const uint8_t* blob, const VFieldProof* fp, const VFieldQuery* fq,
                                                     u64 nq, u64* flags) {
@@ -148,10 +149,14 @@ __global__ __launch_bounds__(64) void vfield_kernel(const uint8_t* blob, const V
 static unsigned blocks_for(u64 n, unsigned t) { return (unsigned)((n + t - 1) / t); }
 
 void launch_verify(const uint8_t* blob, const VTree* trees, u64 ntrees, const VTreeLeaf* tleaves, const VVec* vecs,
-                   const VFieldProof* fp, const VFieldQuery* fq, u64 nq, int fold, u64* flags, hipStream_t s) {
+                   const VFieldProof* fp, const VFieldQuery* fq, const FoldRanges& ranges, u64* flags, hipStream_t s) {
     if (ntrees) XFG_LAUNCH(vtree_kernel, dim3((unsigned)ntrees), dim3(256), 0, s, blob, trees, tleaves, vecs, flags);
-    const dim3 g(blocks_for(nq, 64)), b(64);
-    if (nq) with_fold(fold, [&](auto LOGF) { XFG_LAUNCH(vfield_kernel<LOGF>, g, b, 0, s, blob, fp, fq, nq, flags); });
+    for (int r = 0; r < 4; r++) {  // folding factor 2 << r: its instantiation over its own range of records
+        const u64 first = ranges.begin[r], nq = ranges.begin[r + 1] - first;
+        if (!nq) continue;  // a zero-sized grid is a launch error
+        const dim3 g(blocks_for(nq, 64)), b(64);
+        with_fold(2 << r, [&](auto LOGF) { XFG_LAUNCH(vfield_kernel<LOGF>, g, b, 0, s, blob, fp, fq + first, nq, flags); });
+    }
 }
 
 }  // namespace xfg

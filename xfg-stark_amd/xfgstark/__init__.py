@@ -12,6 +12,6 @@ _api: the product API; _hooks: the kernel-level test hooks (XfgBurnMintProver.de
 import ctypes as C  # noqa: F401  (tests and scripts build their own arguments with xfgstark.C)
 
 from ._abi import (HEADER_PATH, LIB_PATH, STATUS, TRACE_ON_DEVICE, TRACE_VALIDATE, XfgStarkError,  # noqa: F401
-                   _lib, _TraceFault, _TraceLayout, _u8p, _u64p, exported_symbols)
-from ._api import (FieldExtension, PendingBatch, ProofOptions, StarkProof, TraceFault, XfgBurnMintProver,  # noqa: F401
-                   XfgBurnMintVerifier, air_consts, blake3, burn_inputs, record_size)
+                   _Acceptable, _lib, _Options, _TraceFault, _TraceLayout, _u8p, _u64p, exported_symbols)
+from ._api import (AcceptableOptions, FieldExtension, PendingBatch, ProofOptions, StarkProof, TraceFault,  # noqa: F401
+                   XfgBurnMintProver, XfgBurnMintVerifier, air_consts, blake3, burn_inputs, record_size)

@@ -36,6 +36,14 @@ class _Options(C.Structure):
                 ("fri_remainder_max_degree", C.c_uint32)]
 
 
+ACCEPT_OPTION_SET, ACCEPT_MIN_CONJECTURED_SECURITY = 0, 1  # XFG_ACCEPT_* kinds of xfg_acceptable
+
+
+class _Acceptable(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("min_security", C.c_uint32), ("options", C.POINTER(_Options)),
+                ("num_options", C.c_uint32)]
+
+
 class _BurnInputs(C.Structure):
     _fields_ = [("burn_amount", C.c_uint64), ("mint_amount", C.c_uint64), ("tx_prefix_hash", C.c_uint8 * 32),
                 ("recipient_address", C.c_char_p), ("recipient_len", C.c_size_t), ("secret", C.c_char_p),
@@ -79,6 +87,7 @@ _opts, _burn, _airs, _faults = C.POINTER(_Options), C.POINTER(_BurnInputs), C.PO
 _PROVE_BATCH = [_ctx, _u32, _burn, _u64, _opts, _bufs, _szp, _intp]
 _TRACE_BATCH = [_ctx, _u32, C.c_void_p, _u32, _u64, _airs, _opts, _u32, _bufs, _szp, _intp, _faults]
 _layout = C.POINTER(_TraceLayout)
+_accept = C.POINTER(_Acceptable)
 _TRACE_BATCH_STRIDED = [_ctx, _u32, C.c_void_p, _u64, _layout, _airs, _opts, _u32, _bufs, _szp, _intp, _faults]
 _FRI = [_ctx, _u32, _u32, _u32, _u32, _int]  # count, ext, logn, logbeta, coset_major
 _OOD_TAIL = [_u64p, _u64p, _u64p, _u32p, _u64p, _u64, _u64p, _u64p, _u64p, _u32p, _u64p, _intp]  # from hcoef on
@@ -107,6 +116,10 @@ TABLE = [
     ("xfg_verify", _int, [_u8p, _sz, _airs, _opts, _str, _sz]),
     ("xfg_verify_batch", _int, [_u32, _bufs, _szp, _airs, _opts, _intp, _u32]),
     ("xfg_verify_batch_gpu", _int, [_ctx, _u32, _bufs, _szp, _airs, _opts, _intp]),
+    ("xfg_security_level", _int, [_u64, _opts, _u32p]),
+    ("xfg_verify_acceptable", _int, [_u8p, _sz, _airs, _accept, _str, _sz]),
+    ("xfg_verify_batch_acceptable", _int, [_u32, _bufs, _szp, _airs, _accept, _intp, _u32]),
+    ("xfg_verify_batch_gpu_acceptable", _int, [_ctx, _u32, _bufs, _szp, _airs, _accept, _intp]),
     ("xfg_selftest_blake3", _int, [_u8p, _sz, _u8p]),
     ("xfg_selftest_field", _int, [_u64, _u64, _u64p]),
     ("xfg_set_timing", _int, [_ctx, _int]),
@@ -138,6 +151,7 @@ TABLE = [
     ("xfg_debug_grind", _int, [_ctx, _u32, _u32p, _u32, _u64, _u64, _u32, _u32, _u64p]),
     ("xfg_grind_probe", _int, [_ctx, _u32p, _u64p, _u64p]),
     ("xfg_debug_verify_batch_gpu", _int, [_ctx, _u32, _bufs, _szp, _airs, _opts, _intp, _u64p, _str, _sz]),
+    ("xfg_debug_verify_batch_gpu_acceptable", _int, [_ctx, _u32, _bufs, _szp, _airs, _accept, _intp, _u64p, _str, _sz]),
 ]
 
 

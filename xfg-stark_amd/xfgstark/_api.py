@@ -4,8 +4,9 @@ import ctypes as C
 import operator
 import sys
 
-from ._abi import (STATUS, TRACE_ON_DEVICE, TRACE_VALIDATE, XfgStarkError, _AirConsts, _BurnInputs, _lib, _Options,
-                   _ProofInfo, _TraceFault, _TraceLayout, _u8p)
+from ._abi import (ACCEPT_MIN_CONJECTURED_SECURITY, ACCEPT_OPTION_SET, STATUS, TRACE_ON_DEVICE, TRACE_VALIDATE,
+                   XfgStarkError, _Acceptable, _AirConsts, _BurnInputs, _lib, _Options, _ProofInfo, _TraceFault,
+                   _TraceLayout, _u8p)
 from ._hooks import KernelHooks
 from ._marshal import air_array, air_struct, array, bytes_ptr, new_buffer, out_slots, ptr, trace_array
 
@@ -85,10 +86,49 @@ class ProofOptions:
         o = self._c()
         return o, _lib.xfg_proof_size_bound(trace_length, C.byref(o))
 
+    def security_level(self, trace_length):
+        """StarkProof::security_level(conjectured = true) of a proof of `trace_length` under these options, in
+        bits (xfg_security_level); options outside the supported set raise XfgStarkError 9"""
+        o, bits = self._c(), C.c_uint32()
+        st = _lib.xfg_security_level(trace_length, C.byref(o), C.byref(bits))
+        if st:
+            raise XfgStarkError(st, f"no security level for trace length {trace_length} under {self!r}")
+        return bits.value
+
     def __repr__(self):
         return ("ProofOptions(num_queries={0.num_queries}, blowup_factor={0.blowup_factor}, grinding_factor="
                 "{0.grinding_factor}, field_extension={0.field_extension}, fri_folding_factor="
                 "{0.fri_folding_factor}, fri_remainder_max_degree={0.fri_remainder_max_degree})").format(self)
+
+
+class AcceptableOptions:
+    """winterfell::AcceptableOptions, the verifier's policy: option_set([ProofOptions, ...]) takes a proof whose
+    six options equal one member's (1..32 members), min_conjectured_security(bits) one whose conjectured
+    security level is at least `bits`. MinProvenSecurity is not offered. The library's own limits (cubic
+    extension, LDE sizes, last FRI layer) hold under either: see xfg_verify_acceptable in the header."""
+
+    def __init__(self, kind, options=(), min_security=0):
+        self.kind, self.options, self.min_security = kind, list(options), min_security
+
+    @classmethod
+    def option_set(cls, options):
+        return cls(ACCEPT_OPTION_SET, options=options)
+
+    @classmethod
+    def min_conjectured_security(cls, bits):
+        return cls(ACCEPT_MIN_CONJECTURED_SECURITY, min_security=bits)
+
+    def _c(self):
+        """the xfg_acceptable; the option array it points to stays alive on the struct"""
+        arr = (_Options * len(self.options))(*[o._c() for o in self.options])
+        a = _Acceptable(self.kind, self.min_security, arr if self.options else None, len(self.options))
+        a._keep = arr
+        return a
+
+    def __repr__(self):
+        if self.kind == ACCEPT_MIN_CONJECTURED_SECURITY:
+            return f"AcceptableOptions.min_conjectured_security({self.min_security})"
+        return f"AcceptableOptions.option_set({self.options!r})"
 
 
 class StarkProof:
@@ -157,6 +197,11 @@ class StarkProof:
         i = self._parse()
         return list(i.ood_trace[0::2]), list(i.ood_trace[1::2]), i.ood_composition
 
+    def security_level(self):
+        """StarkProof::security_level(conjectured = true): the level of the options and trace length the proof
+        states (ProofOptions.security_level)"""
+        return self.options.security_level(self.trace_length)
+
     def __len__(self):
         return len(self._data)
 
@@ -168,21 +213,32 @@ class XfgBurnMintVerifier:
     """Mirror of the reference XfgBurnMintVerifier (src/burn_mint_verifier.rs:78-316) over
     xfg_verify. The statement of a proof is its AIR constants `air` = (public inputs[12], nullifier,
     commitment), as returned by air_consts(); acceptable options default to the reference's
-    ProofOptions::new(42, 8, 4, None, 8, 31) (:95-110)."""
+    ProofOptions::new(42, 8, 4, None, 8, 31) (:95-110). `acceptable` (an AcceptableOptions) is Winterfell's
+    policy argument: with None the verifier takes the one-element set of `proof_options`, as the reference
+    does (:271); with a policy every verify call goes through the xfg_*_acceptable entries and
+    `proof_options` is not consulted."""
 
-    def __init__(self, security_parameter=128, proof_options=None):
+    def __init__(self, security_parameter=128, proof_options=None, acceptable=None):
         self.security_parameter = security_parameter
         self.proof_options = proof_options or ProofOptions.reference()
+        self.acceptable = acceptable
 
     @classmethod
     def with_options(cls, security_parameter, proof_options):
         return cls(security_parameter, proof_options)
 
+    def _entry(self, name):
+        """(the C entry `name` or its _acceptable form, the options or the policy it takes)"""
+        if self.acceptable is None:
+            return getattr(_lib, name), self.proof_options._c()
+        return getattr(_lib, name + "_acceptable"), self.acceptable._c()
+
     def verify_with_details(self, proof, air):
         """-> (accepted, error text or None, proof size)"""
         data = proof.to_bytes() if isinstance(proof, StarkProof) else bytes(proof)
-        a, o, err = air_struct(air), self.proof_options._c(), C.create_string_buffer(256)
-        st = _lib.xfg_verify(bytes_ptr(data), len(data), C.byref(a), C.byref(o), err, 256)
+        a, err = air_struct(air), C.create_string_buffer(256)
+        fn, o = self._entry("xfg_verify")
+        st = fn(bytes_ptr(data), len(data), C.byref(a), C.byref(o), err, 256)
         if st not in (0, 10):
             raise XfgStarkError(st, STATUS.get(st))
         return st == 0, (err.value.decode() or None), len(data)
@@ -204,23 +260,25 @@ class XfgBurnMintVerifier:
         k = len(proofs_and_airs)
         if k == 0:
             return []
-        keep, ptrs, lens, airs, res, o = self._batch_args(proofs_and_airs)
+        keep, ptrs, lens, airs, res = self._batch_args(proofs_and_airs)
         if gpu is not None:
-            gpu._call(_lib.xfg_verify_batch_gpu, k, ptrs, lens, airs, C.byref(o), res)
+            fn, o = self._entry("xfg_verify_batch_gpu")
+            gpu._call(fn, k, ptrs, lens, airs, C.byref(o), res)
         else:
-            st = _lib.xfg_verify_batch(k, ptrs, lens, airs, C.byref(o), res, threads)
+            fn, o = self._entry("xfg_verify_batch")
+            st = fn(k, ptrs, lens, airs, C.byref(o), res, threads)
             if st:
                 raise XfgStarkError(st, STATUS.get(st))
         return [r == 0 for r in res]
 
     def _batch_args(self, proofs_and_airs):
-        """the C arguments of a batch: (objects to keep alive, proofs, lens, airs, results, options)"""
+        """the C arguments of a batch: (objects to keep alive, proofs, lens, airs, results)"""
         k = len(proofs_and_airs)
         datas = [(p.to_bytes() if isinstance(p, StarkProof) else bytes(p)) for p, _ in proofs_and_airs]
         ptrs = (_u8p * k)(*[bytes_ptr(d) for d in datas])
         lens = (C.c_size_t * k)(*[len(d) for d in datas])
         air_np, airs = air_array(a for _, a in proofs_and_airs)
-        return (datas, air_np), ptrs, lens, airs, (C.c_int * k)(), self.proof_options._c()
+        return (datas, air_np), ptrs, lens, airs, (C.c_int * k)()
 
     def debug_batch_verify(self, proofs_and_airs, gpu):
         """batch_verify(..., gpu=gpu) with what the device decided (xfg_debug_verify_batch_gpu): list of
@@ -228,11 +286,12 @@ class XfgBurnMintVerifier:
         k = len(proofs_and_airs)
         if k == 0:
             return []
-        keep, ptrs, lens, airs, res, o = self._batch_args(proofs_and_airs)
+        keep, ptrs, lens, airs, res = self._batch_args(proofs_and_airs)
         flags = (C.c_uint64 * k)()
         stride = 256
         errs = C.create_string_buffer(k * stride)
-        gpu._call(_lib.xfg_debug_verify_batch_gpu, k, ptrs, lens, airs, C.byref(o), res, flags, errs, stride)
+        fn, o = self._entry("xfg_debug_verify_batch_gpu")
+        gpu._call(fn, k, ptrs, lens, airs, C.byref(o), res, flags, errs, stride)
         texts = [errs.raw[i * stride:(i + 1) * stride].split(b"\0", 1)[0].decode() for i in range(k)]
         return [(res[i] == 0, int(flags[i]), texts[i] or None) for i in range(k)]
 
