@@ -17,6 +17,8 @@
  *   xfg_prove_batch      <- the serial loops of the reference callers (e.g. benchmark harness
  *                           src/benchmarks/mod.rs:301-342, BatchBurnMintVerifier's pattern
  *                           src/burn_mint_verifier.rs:326-338) -- independent proofs, one launch set
+ *   xfg_prove_records    <- the same loops for statements that arrive as fixed-size packed records, in host
+ *                           memory or in device memory (validated, marshalled and hashed on the device)
  *   xfg_default_options  <- XfgBurnMintProver::new(_) ProofOptions::new(42, 8, 4, None, 8, 31)
  *                           src/burn_mint_prover.rs:27-41 (argument order: queries, blowup,
  *                           grinding, extension, FRI folding, FRI remainder max degree)
@@ -214,6 +216,51 @@ int xfg_prove_trace_batch_strided_submit(xfg_ctx* ctx, uint32_t count, const uin
                                          const xfg_trace_layout* layout, const xfg_air_consts* airs,
                                          const xfg_options* opts, uint32_t flags, uint8_t* const* outs,
                                          size_t* out_lens, int* statuses, xfg_trace_fault* faults, uint64_t* ticket);
+
+/* ---- batches of burn statements as packed records, in host or in device memory ----
+ * One statement as a fixed-size little-endian record of 128 bytes: what a queue, a collective or a Rust service
+ * hands over, with no pointers in it. A record always carries a 20-byte recipient and a 32-byte secret, so the
+ * statuses XFG_BAD_RECIPIENT_LEN and XFG_SHORT_SECRET cannot occur for one. reserved must be zero. */
+typedef struct {
+    uint64_t burn_amount;        /* offset 0 */
+    uint64_t mint_amount;        /* 8 */
+    uint8_t tx_prefix_hash[32];  /* 16 */
+    uint8_t recipient[20];       /* 48 */
+    uint8_t secret[32];          /* 68 */
+    uint32_t network_id;         /* 100 */
+    uint32_t target_chain_id;    /* 104 */
+    uint32_t commitment_version; /* 108 */
+    uint8_t reserved[16];        /* 112: zero, else XFG_INVALID_ARGUMENT for that record */
+} xfg_burn_record;
+
+#define XFG_RECORDS_ON_DEVICE 1u /* `records` is a device pointer on the context's device */
+
+/* xfg_prove_batch for `count` records: statuses, proof bytes and the xfg_last_error text are what xfg_prove_batch
+ * gives for the same statements (a record is checked in its order: burn amount, mint amount, tx hash, then the
+ * reserved bytes); out_lens[i] of an invalid record is set to 0. trace_length 0 -> 64.
+ * Host records (flags 0) are validated and marshalled on the host pool before the call returns.
+ * XFG_RECORDS_ON_DEVICE: nothing is copied to the host and no statement is touched by it before the launch:
+ * each unit of 32 proofs starts its chain with a kernel that validates and marshals its records, computes the
+ * four Keccak-256 hashes of each statement and seeds its transcript; the AIR constants and statuses come back
+ * with the unit's transcript inputs. An invalid record keeps its slot in its unit and gets no proof; the other
+ * proofs are byte-identical to proving them alone. The records must be memory of the context's device that this
+ * process's HIP runtime allocated, hold 128 * count bytes and be 8-byte aligned; the caller guarantees that they
+ * are complete (every producing stream synchronised) before the call. They are only read.
+ * Refused with XFG_INVALID_ARGUMENT, nothing launched: count 0, a null pointer, an unknown flag, device records
+ * that fail the above. Returns XFG_OK if the batch ran, like xfg_prove_batch. */
+int xfg_prove_records(xfg_ctx* ctx, uint32_t count, const xfg_burn_record* records, uint64_t trace_length,
+                      const xfg_options* opts, uint32_t flags, uint8_t* const* outs, size_t* out_lens, int* statuses);
+/* asynchronous form, waited for with xfg_batch_wait(ticket): records, outs, out_lens and statuses stay the
+ * caller's, valid and unchanged, until the wait returns. statuses[i] of invalid host records are set now, those
+ * of device records by the wait */
+int xfg_prove_records_submit(xfg_ctx* ctx, uint32_t count, const xfg_burn_record* records, uint64_t trace_length,
+                             const xfg_options* opts, uint32_t flags, uint8_t* const* outs, size_t* out_lens,
+                             int* statuses, uint64_t* ticket);
+/* the statement of each record as the verifiers take it: airs_out[i] and statuses[i] (the validation status; the
+ * constants of an invalid record are marshalled all the same). Host records are computed on the host and ctx may
+ * be NULL; with XFG_RECORDS_ON_DEVICE the prover's kernel runs on lane 0 (refused while batches are pending) */
+int xfg_air_consts_from_records(xfg_ctx* ctx, uint32_t count, const xfg_burn_record* records, uint32_t flags,
+                                xfg_air_consts* airs_out, int* statuses);
 
 /* allocate every device / pinned-host workspace and load all code objects for batches of
  * `count` proofs of this shape (setup, not a prove; later calls never allocate) */
@@ -518,6 +565,11 @@ int xfg_debug_grind(xfg_ctx* ctx, uint32_t count, const uint32_t* seeds, uint32_
                     uint64_t max_nonce, uint32_t chunk_log, uint32_t blocks, uint64_t* nonces_out);
 /* GRIND_DEVICE_MIN, and how many proofs' nonces this context has searched on the device / on the host */
 int xfg_grind_probe(const xfg_ctx* ctx, uint32_t* device_min, uint64_t* device_searches, uint64_t* host_searches);
+/* the Keccak-256 of the record kernel alone (the permutation spread over the lanes of a wave): `count` single-block
+ * messages msgs [count][136] of lens[i] <= 135 bytes each (the bytes past a message's length are ignored),
+ * padded as Keccak pads (0x01 .. 0x80, one byte 0x81 at length 135; not SHA-3's 0x06) -> out [count][32].
+ * Refused with XFG_INVALID_ARGUMENT: a null pointer, count 0 or above 65535, a length above 135 */
+int xfg_debug_keccak256(xfg_ctx* ctx, uint32_t count, const uint8_t* msgs, const uint32_t* lens, uint8_t* out);
 /* xfg_verify_batch_gpu (the same body, same rules for pending batches) with what the device decided:
  * flags[i] = the 64-bit word the two verifier kernels set for proof i (bit l < 24: layer l folding,
  * 32 + l: layer l commitment, 61 / 62: constraint / trace commitment, 63: remainder folding), 0 for a

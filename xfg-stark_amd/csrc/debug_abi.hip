@@ -474,6 +474,26 @@ int xfg_debug_grind(xfg_ctx* c, uint32_t count, const uint32_t* seeds, uint32_t 
     });
 }
 
+int xfg_debug_keccak256(xfg_ctx* c, uint32_t count, const uint8_t* msgs, const uint32_t* lens, uint8_t* out) {
+    if (!c || !msgs || !lens || !out || count == 0 || count > 65535) return XFG_INVALID_ARGUMENT;
+    for (uint32_t i = 0; i < count; i++)
+        if (lens[i] >= KECCAK_RATE) return XFG_INVALID_ARGUMENT;
+    return on_lane0(c, [&](Lane* L) -> int {
+        // the lane's word buffers as byte buffers: messages in coef, lengths in trace, digests in scratch
+        const size_t mbytes = (size_t)count * KECCAK_RATE;
+        L->coef.ensure((mbytes + 7) / 8);
+        L->trace.ensure(((size_t)count * 4 + 7) / 8);
+        L->scratch.ensure((size_t)count * 4);
+        HIPCHK(hipMemcpy(L->coef.p, msgs, mbytes, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(L->trace.p, lens, (size_t)count * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemsetAsync(L->scratch.p, 0xFF, (size_t)count * 32, L->stream));
+        launch_keccak256((const uint8_t*)L->coef.p, (const u32*)L->trace.p, (int)count, (uint8_t*)L->scratch.p, L->stream);
+        HIPCHK(hipMemcpyAsync(out, L->scratch.p, (size_t)count * 32, hipMemcpyDeviceToHost, L->stream));
+        HIPCHK(hipStreamSynchronize(L->stream));
+        return XFG_OK;
+    });
+}
+
 int xfg_grind_probe(const xfg_ctx* c, uint32_t* device_min, uint64_t* device_searches, uint64_t* host_searches) {
     if (!c) return XFG_INVALID_ARGUMENT;
     uint64_t dev = 0, host = 0;

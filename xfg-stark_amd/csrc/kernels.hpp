@@ -9,6 +9,7 @@
 #include "blake3.hpp"
 #include "ntt_plan.hpp"
 #include "trace_layout.hpp"
+#include "burn_record.hpp"
 #include "columns.hpp"
 
 namespace xfg {
@@ -98,6 +99,20 @@ struct DeepCoinStep {
     DeepParams* dp = nullptr;
     u64 ginv = 0;  // g^-1
 };
+
+// ---- burn records (burn_record.hip) ----
+// The head of the chain of a unit whose statements are packed records in device memory: for record b < B,
+// air_out[b] = its AIR constants (validation does not stop the marshalling: an invalid record's slot runs through
+// the chain like any other), coin_out[b] = its transcript's coin as Coin::init leaves it (seed = BLAKE3 of ctx ||
+// the 12 public inputs, counter 0), status_out[b] = record_status. One wave per record; the records are only read
+struct CoinContext {
+    u64 e[8];  // Context::to_elements (host_common.hpp context_elements)
+};
+void launch_burn_marshal(const xfg_burn_record* records, int B, const CoinContext& ctx, AirConst* air_out,
+                         DevCoin* coin_out, int* status_out, hipStream_t s);
+// Keccak-256 of `count` single-block messages msgs [count][136], lens[i] <= 135 -> out [count][32] (out 8-byte
+// aligned), by the record kernel's permutation
+void launch_keccak256(const uint8_t* msgs, const u32* lens, int count, uint8_t* out, hipStream_t s);
 
 // ---- Merkle (merkle.hip; heap layout: nodes[1] = root, nodes[L + i] = leaf i) ----
 // A commitment is one call: the leaves, every level above them up to the root, then the transcript

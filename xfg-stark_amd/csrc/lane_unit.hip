@@ -54,7 +54,8 @@ void size_ood_deep(Lane* c, size_t B, const ProofShape& sh) {
 }
 
 // every device buffer of a unit of B proofs, and the pinned opening buffers
-static void size_lane_buffers(Lane* c, size_t B, const ProofShape& sh, const Opts& o, const TraceSrc& ts) {
+static void size_lane_buffers(Lane* c, size_t B, const ProofShape& sh, const Opts& o, const TraceSrc& ts,
+                              const RecordSrc& rs) {
     const u64 n = sh.n, N = sh.N;
     const size_t DE = sh.DE;
     const unsigned nl = sh.nl;
@@ -93,6 +94,7 @@ static void size_lane_buffers(Lane* c, size_t B, const ProofShape& sh, const Opt
     c->h_gd.ensure(digs + opens);
     size_grind(c, B);
     if (ts.checks()) c->tkeys.ensure(B);
+    c->rstatus.ensure(B);  // a few bytes, sized for every unit so that xfg_prepare covers units of records too
     if (ts.kind == TraceSrc::HOST_STAGED || ts.size_staging) c->h_trace.ensure(B * 7 * n);
 }
 
@@ -137,8 +139,15 @@ const u64* grind_search(Lane* c, int B, unsigned grind, u64 first, u64 max_nonce
 // draws) run on the device from a copy of each proof's coin, so the whole chain from the trace
 // to the FRI remainder is enqueued without a host round trip; the host replays the same
 // transcript from the roots and OOD values once the chain has finished (replay_transcript).
-static void upload_unit_inputs(Lane* c, ProofJob* jobs, int B, const ProofShape& sh, const Opts& o) {
+// Records in device memory: the record kernel puts both on the device from the unit's records, with no host work
+// per proof before the launch; the host takes the constants from the replay block afterwards (adopt_record_inputs)
+static void upload_unit_inputs(Lane* c, ProofJob* jobs, int B, const ProofShape& sh, const Opts& o, const RecordSrc& rs) {
     hipStream_t s = c->stream;
+    if (rs.p) {
+        launch_burn_marshal(rs.p, B, coin_context(sh.n, o), c->air.p, c->dcoin.p, c->rstatus.p, s);
+        HIPCHK(hipMemsetAsync(c->dfail.p, 0, B * sizeof(int), s));
+        return;
+    }
     AirConst* airs = c->h_air.ensure(B);
     for (int b = 0; b < B; b++) airs[b] = jobs[b].air;
     upload(c->air.p, airs, B * sizeof(AirConst), s);
@@ -157,6 +166,20 @@ static void upload_unit_inputs(Lane* c, ProofJob* jobs, int B, const ProofShape&
     }
     upload(c->dcoin.p, hc, B * sizeof(DevCoin), s);
     HIPCHK(hipMemsetAsync(c->dfail.p, 0, B * sizeof(int), s));
+}
+// a unit of device records, its stream synchronised: the jobs' AIR constants from the replay block and their coins
+// seeded from them on the host, as upload_unit_inputs does for marshalled jobs. The replay then checks the
+// device's draws, and with them the seed the record kernel computed, against this coin
+static void adopt_record_inputs(const Lane* c, ProofJob* jobs, int B, const ProofShape& sh, const Opts& o) {
+    host_pool().parallel_for(B, [c, jobs, &sh, &o](int b) {
+        ProofJob& j = jobs[b];
+        j.air = c->h_rair[b];
+        u64 e[20];
+        context_elements(sh.n, o, e);
+        memcpy(e + 8, j.air.pub, 12 * 8);
+        j.coin.init(e, 20);
+        j.commitments.clear();
+    });
 }
 
 ColConst trace_const(const Lane* c, const ProofShape& sh) {
@@ -254,7 +277,8 @@ static void enqueue_fri_layers(Lane* c, const Tables& T, int B, const ProofShape
 // stream after the last FRI fold); as one larger copy the runtime takes the SDMA engine, whose
 // dependency on the lane stream cost 17 % of the pipelined throughput (same box, lib_ab.sh)
 // with_keys: the trace check's word per proof rides along (units of caller-supplied traces that are checked)
-static ReplayView pack_replay_block(Lane* c, size_t B, const ProofShape& sh, bool with_keys) {
+// with_records: the AIR constants and the statuses the record kernel wrote ride along (units of device records)
+static ReplayView pack_replay_block(Lane* c, size_t B, const ProofShape& sh, bool with_keys, bool with_records) {
     const size_t DE = sh.DE, nl = sh.nl;
     PackSet pk;
     u64 words = 0;
@@ -276,6 +300,9 @@ static ReplayView pack_replay_block(Lane* c, size_t B, const ProofShape& sh, boo
     const u64 o_dn2 = seg(c->dn2.p, B * DE * 8);
     const u64 o_const = seg(c->const_col.p, (B * 7 + 3) & ~(size_t)3);  // whole words; B * 7 flags
     const u64 o_keys = with_keys ? seg(c->tkeys.p, B * 8) : 0;
+    const u64 o_rair = with_records ? seg(c->air.p, B * sizeof(AirConst)) : 0;
+    const u64 o_rstatus = with_records ? seg(c->rstatus.p, B * sizeof(int)) : 0;
+    static_assert(PackSet::MAX >= 12, "nine segments, the keys and the two of a unit of records");
     unsigned char* hx = c->h_xfer.ensure(words * 4);
     void* hx_dev = nullptr;
     HIPCHK(hipHostGetDevicePointer(&hx_dev, hx, 0));
@@ -291,18 +318,20 @@ static ReplayView pack_replay_block(Lane* c, size_t B, const ProofShape& sh, boo
     rv.dn2h = (const u64*)(hx + o_dn2);
     c->h_const_col = hx + o_const;
     c->h_tkeys = with_keys ? (const u64*)(hx + o_keys) : nullptr;
+    c->h_rair = with_records ? (const AirConst*)(hx + o_rair) : nullptr;
+    c->h_rstatus = with_records ? (const int*)(hx + o_rstatus) : nullptr;
     return rv;
 }
 
 // the whole device chain of a unit, trace to FRI remainder and the replay block, enqueued on the
 // lane stream without a host round trip. g: the trace domain generator
 static ReplayView enqueue_commit_chain(Lane* c, const Tables& T, const u64* ce_div, ProofJob* jobs, int B,
-                                       const TraceSrc& ts, const ProofShape& sh, const Opts& o, u64 g,
-                                       HostTrace& ht) {
+                                       const TraceSrc& ts, const RecordSrc& rs, const ProofShape& sh, const Opts& o,
+                                       u64 g, HostTrace& ht) {
     const u64 n = sh.n;
     const int logn = sh.logn, logbeta = sh.logbeta, DE = sh.DE;
     hipStream_t s = c->stream;
-    upload_unit_inputs(c, jobs, B, sh, o);
+    upload_unit_inputs(c, jobs, B, sh, o, rs);
     // ---- 1. trace LDE + commitment (DefaultTraceLde::new)
     ht.mark("setup");
     stage_mark(c, 0);
@@ -378,7 +407,7 @@ static ReplayView enqueue_commit_chain(Lane* c, const Tables& T, const u64* ce_d
     stage_mark(c, 7);
     // ---- 6. FRI layers and remainder, then the replay's inputs
     enqueue_fri_layers(c, T, B, sh, (int)o.fold, cs, ht);
-    const ReplayView rv = pack_replay_block(c, B, sh, ts.checks());
+    const ReplayView rv = pack_replay_block(c, B, sh, ts.checks(), rs.p != nullptr);
     stage_mark(c, 8);
     ht.mark("launch_rem");
     return rv;
@@ -456,7 +485,7 @@ static Gathered enqueue_gathers(Lane* c, const ProofShape& sh, const OpeningInde
 // Device chain -> host transcript replay -> opening plans -> gathers -> serialisation; the per-proof
 // host steps (proof_assembly.hpp) are independent and spread over the host pool
 void prove_lane(Lane* c, const Tables& T, const u64* ce_div, ProofJob* jobs, int B, const TraceSrc& ts,
-                       u64 n, const Opts& o) {
+                       u64 n, const Opts& o, const RecordSrc& rs) {
     using clk = std::chrono::steady_clock;
     const auto t_host0 = clk::now();
     HostTrace ht;
@@ -465,10 +494,11 @@ void prove_lane(Lane* c, const Tables& T, const u64* ce_div, ProofJob* jobs, int
     const u64 g = gl_root(sh.logn);
     HostPool& pool = host_pool();
 
-    size_lane_buffers(c, B, sh, o, ts);
-    const ReplayView rv = enqueue_commit_chain(c, T, ce_div, jobs, B, ts, sh, o, g, ht);
+    size_lane_buffers(c, B, sh, o, ts, rs);
+    const ReplayView rv = enqueue_commit_chain(c, T, ce_div, jobs, B, ts, rs, sh, o, g, ht);
     HIPCHK(hipStreamSynchronize(c->stream));
     ht.mark("sync_rem");
+    if (rs.p) adopt_record_inputs(c, jobs, B, sh, o);
     // trace columns that went through the NTTs; the rest were found constant, or the same as proof 0's
     u64 live_cols = 0, shared_cols = 0;
     for (int k = 0; k < B * 7; k++) {
@@ -532,6 +562,9 @@ void prove_lane(Lane* c, const Tables& T, const u64* ce_div, ProofJob* jobs, int
         else if (key != TRACE_KEY_VALID)
             jobs[b].status = (key >> 62) == TRACE_KEY_NONCANONICAL ? XFG_INVALID_ARGUMENT : XFG_INVALID_TRACE;
     }
+    // device records: the record kernel's status is the proof's, whatever prover error the discarded slot earned
+    for (int b = 0; b < B && rs.p; b++)
+        if (c->h_rstatus[b]) jobs[b].status = c->h_rstatus[b];
     ht.dump(B, (long)((u64)B * 7 - live_cols - shared_cols), (long)shared_cols);
     if (c->lde_probe) {  // the stream has passed both events (root / query fetches synchronised it)
         float ms = 0;

@@ -4,6 +4,7 @@
 #pragma once
 #include <string>
 
+#include "burn_record.hpp"
 #include "host_common.hpp"
 #include "kernels.hpp"
 
@@ -96,6 +97,31 @@ static inline int marshal(const xfg_burn_inputs* in, AirConst& a, std::string& e
     a.pub[11] = in->commitment_version;
     air_constants(a.pub, secret, a.nullifier, a.commitment);
     return XFG_OK;
+}
+
+// marshal() for a packed record, through the helpers the record kernel shares (burn_record.hpp): the status and
+// the text are marshal()'s for record_to_inputs(r); the constants are filled in for an invalid record too
+static inline int marshal_record(const xfg_burn_record& r, AirConst& a, std::string& err) {
+    const int st = record_status(r);
+    if (st) err = record_status_text(st, r.burn_amount, r.mint_amount);
+    BurnMsgSrc s;
+    memset(&s, 0, sizeof s);
+    s.recipient = r.recipient;
+    s.secret = record_secret(r);
+    record_public_inputs(r, s.pub);
+    uint8_t msg[KECCAK_RATE], h[32];
+    keccak256(msg, burn_msg_bytes(MSG_RECIPIENT, s, msg), h);
+    s.pub[3] = le_u32(h);
+    keccak256(msg, burn_msg_bytes(MSG_NULLIFIER, s, msg), h);
+    const u64 nullifier = le_u32(h);
+    keccak256(msg, burn_msg_bytes(MSG_RECIPIENT_FULL, s, msg), h);
+    for (int i = 0; i < 4; i++) s.rf[i] = le_u64(h + 8 * i);
+    keccak256(msg, burn_msg_bytes(MSG_COMMITMENT, s, msg), h);
+    memset(&a, 0, sizeof a);
+    memcpy(a.pub, s.pub, sizeof a.pub);
+    a.nullifier = nullifier;
+    a.commitment = le_u32(h);
+    return st;
 }
 
 }  // namespace xfg

@@ -22,13 +22,20 @@ static const char* STAGE_NAMES[] = {"trace_lde",     "trace_commit", "constraint
                                     "comp_commit",   "ood",          "deep",            "fri",
                                     "queries_gather", "host_total",  "host_queries",    "host_serialize"};
 
+// the statuses record_status gives an invalid record
+static bool record_refusal(int st) {
+    return st == XFG_INVALID_BURN_AMOUNT || st == XFG_MINT_MISMATCH || st == XFG_ZERO_TX_HASH || st == XFG_INVALID_ARGUMENT;
+}
+
 static void copy_unit(Batch* b, int b0, int b1) {
     host_pool().parallel_for(b1 - b0, [&](int i0) {
         const int k = b0 + i0;
         ProofJob& j = b->jobs[k];
         if (j.status) {
             b->st[k] = j.status;
-            if (j.status == XFG_INVALID_TRACE) {  // no proof: whatever the slot's chain produced is dropped
+            // no proof: whatever the slot's chain produced is dropped (an invalid trace; a record the kernel
+            // found invalid, its status the validation's 1, 2, 3 or XFG_INVALID_ARGUMENT)
+            if (j.status == XFG_INVALID_TRACE || (b->records.p && record_refusal(j.status))) {
                 b->out_lens[b->which[k]] = 0;
                 std::vector<uint8_t>().swap(j.bytes);
             }
@@ -65,7 +72,9 @@ static void worker_main(xfg_ctx* c, int l) {
         if (ts.p) ts.p += (size_t)b0 * ts.layout.trace_stride;
         if (!b->refused.empty()) ts.refused = b->refused.data() + b0;
         if (!b->keys.empty()) ts.keys = b->keys.data() + b0;
-        prove_lane(L, b->T, b->ce_div, b->jobs.data() + b0, b1 - b0, ts, b->n, b->o);
+        RecordSrc rs = b->records;
+        if (rs.p) rs.p += b0;
+        prove_lane(L, b->T, b->ce_div, b->jobs.data() + b0, b1 - b0, ts, b->n, b->o, rs);
         copy_unit(b, b0, b1);
     });
 }
@@ -121,6 +130,17 @@ static void note_status(xfg_ctx* c, const Batch& b, size_t k) {
     if (b.st[k] == XFG_PROVER_ERROR)
         c->err = b.jobs[k].pow_exhausted ? "Prover error: proof-of-work search exhausted"
                                          : "Prover error: proof generation failed (degenerate transcript or DEEP degree)";
+}
+
+// the text of an invalid record's status as marshal() words it; the two amounts a mint mismatch names are read
+// from the caller's record (device memory of the current device: one 16-byte copy)
+static std::string record_text_of(const xfg_burn_record* rec, int status, bool on_device) {
+    uint64_t amounts[2] = {0, 0};  // burn, mint: the record's first two words
+    if (status == XFG_MINT_MISMATCH) {
+        if (on_device) HIPCHK(hipMemcpy(amounts, rec, sizeof amounts, hipMemcpyDeviceToHost));
+        else memcpy(amounts, rec, sizeof amounts);
+    }
+    return record_status_text(status, amounts[0], amounts[1]);
 }
 
 }  // namespace xfg
@@ -309,6 +329,12 @@ int xfg_batch_wait(xfg_ctx* c, uint64_t ticket) {
             return XFG_INVALID_ARGUMENT;
         }
         if (b->err) std::rethrow_exception(b->err);
+        // device records: the text of what the record kernel found, as the host path words it at submission
+        if (b->records.p) {
+            HIPCHK(hipSetDevice(c->device));
+            for (size_t k = 0; k < b->jobs.size(); k++)
+                if (record_refusal(b->st[k])) c->err = record_text_of(b->records.p + k, b->st[k], true);
+        }
         for (size_t k = 0; k < b->jobs.size(); k++) {
             b->statuses[b->which[k]] = b->st[k];
             note_status(c, *b, k);
@@ -336,22 +362,41 @@ int xfg_prove_batch(xfg_ctx* c, uint32_t count, const xfg_burn_inputs* inputs, u
 
 // XFG_TRACE_ON_DEVICE: `traces` must be device memory of the context's device that this process's HIP
 // runtime allocated, and the allocation must hold all `bytes` (the lanes copy that range). Returns what
-// is wrong, or null. Asks the runtime only: nothing is launched or copied
-static const char* device_traces_problem(xfg_ctx* c, const void* traces, size_t bytes) {
+// is wrong, or null. Asks the runtime only: nothing is launched or copied (device_range: the questions themselves,
+// shared with the records of XFG_RECORDS_ON_DEVICE)
+enum DeviceRange { RANGE_OK, RANGE_UNKNOWN, RANGE_NOT_DEVICE, RANGE_TOO_SMALL };
+static DeviceRange device_range(xfg_ctx* c, const void* p, size_t bytes) {
     hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, traces) != hipSuccess) {
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
         (void)hipGetLastError();
-        return "traces is not a device pointer known to the library's HIP runtime";
+        return RANGE_UNKNOWN;
     }
-    if (a.type != hipMemoryTypeDevice || a.device != c->device) return "traces is not device memory of the context's device";
+    if (a.type != hipMemoryTypeDevice || a.device != c->device) return RANGE_NOT_DEVICE;
     hipDeviceptr_t base = nullptr;
     size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(traces)) != hipSuccess) {
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
         (void)hipGetLastError();
-        return "traces is not a device pointer known to the library's HIP runtime";
+        return RANGE_UNKNOWN;
     }
-    if ((const char*)traces + bytes > (const char*)base + size) return "the device allocation is smaller than [count][7][n] traces";
-    return nullptr;
+    return (const char*)p + bytes > (const char*)base + size ? RANGE_TOO_SMALL : RANGE_OK;
+}
+static const char* device_traces_problem(xfg_ctx* c, const void* traces, size_t bytes) {
+    switch (device_range(c, traces, bytes)) {
+        case RANGE_UNKNOWN: return "traces is not a device pointer known to the library's HIP runtime";
+        case RANGE_NOT_DEVICE: return "traces is not device memory of the context's device";
+        case RANGE_TOO_SMALL: return "the device allocation is smaller than [count][7][n] traces";
+        default: return nullptr;
+    }
+}
+// XFG_RECORDS_ON_DEVICE: the same for `count` records, which the record kernel reads as 8-byte words
+static const char* device_records_problem(xfg_ctx* c, const xfg_burn_record* records, uint32_t count) {
+    if ((uintptr_t)records % alignof(xfg_burn_record)) return "records is not 8-byte aligned";
+    switch (device_range(c, records, (size_t)count * sizeof(xfg_burn_record))) {
+        case RANGE_UNKNOWN: return "records is not a device pointer known to the library's HIP runtime";
+        case RANGE_NOT_DEVICE: return "records is not device memory of the context's device";
+        case RANGE_TOO_SMALL: return "the device allocation is smaller than 128 * count bytes of records";
+        default: return nullptr;
+    }
 }
 
 // the dense layout passes for every n and count that the checks in front of it let through (submit_trace_batch:
@@ -538,6 +583,115 @@ int xfg_check_traces_strided(xfg_ctx* c, uint32_t count, const uint64_t* traces,
                              const xfg_trace_layout* layout, const xfg_air_consts* airs, uint32_t flags,
                              xfg_trace_fault* faults) {
     return check_traces(c, count, traces, n, layout_of(layout, n), airs, flags, faults);
+}
+
+int xfg_prove_records_submit(xfg_ctx* c, uint32_t count, const xfg_burn_record* records, uint64_t trace_length,
+                             const xfg_options* opts, uint32_t flags, uint8_t* const* outs, size_t* out_lens,
+                             int* statuses, uint64_t* ticket) {
+    if (!c) return XFG_INVALID_ARGUMENT;
+    c->err.clear();
+    if (!records || !opts || !out_lens || !statuses || !ticket || count == 0) {
+        c->err = count == 0 ? "empty batch" : "null argument";
+        return XFG_INVALID_ARGUMENT;
+    }
+    *ticket = 0;
+    if (flags & ~XFG_RECORDS_ON_DEVICE) {
+        c->err = "unknown record flag";
+        return XFG_INVALID_ARGUMENT;
+    }
+    const u64 n = trace_length ? trace_length : 64;
+    const Opts o = to_opts(opts);
+    if (int st = check_request(c, n, o)) return st;
+    return guarded(c, [&]() -> int {
+        HIPCHK(hipSetDevice(c->device));
+        std::unique_ptr<Batch> bp(new Batch());
+        if (flags & XFG_RECORDS_ON_DEVICE) {
+            if (const char* m = device_records_problem(c, records, count)) {
+                c->err = m;
+                return XFG_INVALID_ARGUMENT;
+            }
+            // every record keeps its slot: the units' kernels validate and marshal them, nothing is read here
+            bp->jobs.resize(count);
+            bp->which.resize(count);
+            for (uint32_t i = 0; i < count; i++) {
+                bp->which[i] = i;
+                statuses[i] = XFG_OK;
+            }
+            bp->records.p = records;
+        } else {
+            // as xfg_prove_batch_submit: validated and marshalled on the host pool, the valid ones become jobs
+            std::vector<AirConst> airs(count);
+            std::vector<std::string> errs(count);
+            host_pool().parallel_for((int)count, [&](int i) { statuses[i] = marshal_record(records[i], airs[i], errs[i]); });
+            for (uint32_t i = 0; i < count; i++) {
+                if (statuses[i]) {
+                    c->err = errs[i];
+                    out_lens[i] = 0;
+                    continue;
+                }
+                bp->jobs.emplace_back();
+                bp->jobs.back().air = airs[i];
+                bp->which.push_back(i);
+            }
+        }
+        const std::vector<Unit> units = split_units(c, (int)bp->jobs.size(), o.beta);
+        *ticket = submit_batch(c, std::move(bp), n, o, count, outs, out_lens, statuses, units);
+        return XFG_OK;
+    });
+}
+
+int xfg_prove_records(xfg_ctx* c, uint32_t count, const xfg_burn_record* records, uint64_t trace_length,
+                      const xfg_options* opts, uint32_t flags, uint8_t* const* outs, size_t* out_lens, int* statuses) {
+    uint64_t t = 0;
+    int r = xfg_prove_records_submit(c, count, records, trace_length, opts, flags, outs, out_lens, statuses, &t);
+    if (r) return r;
+    return xfg_batch_wait(c, t);
+}
+
+int xfg_air_consts_from_records(xfg_ctx* c, uint32_t count, const xfg_burn_record* records, uint32_t flags,
+                                xfg_air_consts* airs_out, int* statuses) {
+    const bool dev = (flags & XFG_RECORDS_ON_DEVICE) != 0;
+    if (c) c->err.clear();
+    if (!records || !airs_out || !statuses || count == 0 || (flags & ~XFG_RECORDS_ON_DEVICE) || (dev && !c)) {
+        if (c) c->err = count == 0 ? "empty batch" : "null argument or unknown record flag";
+        return XFG_INVALID_ARGUMENT;
+    }
+    std::vector<AirConst> airs(count);
+    auto give = [&] {
+        for (uint32_t i = 0; i < count; i++) {
+            memcpy(airs_out[i].pub_inputs, airs[i].pub, sizeof airs[i].pub);
+            airs_out[i].nullifier = airs[i].nullifier;
+            airs_out[i].commitment = airs[i].commitment;
+        }
+    };
+    if (!dev) {
+        std::string err;
+        for (uint32_t i = 0; i < count; i++)
+            if ((statuses[i] = marshal_record(records[i], airs[i], err)) && c) c->err = err;
+        give();
+        return XFG_OK;
+    }
+    return on_lane0(c, [&](Lane* lane) -> int {
+        if (const char* m = device_records_problem(c, records, count)) {
+            c->err = m;
+            return XFG_INVALID_ARGUMENT;
+        }
+        lane->air.ensure(count);
+        lane->dcoin.ensure(count);
+        lane->rstatus.ensure(count);
+        // the coins are not returned: any context will do
+        xfg_options any;
+        xfg_default_options(&any);
+        launch_burn_marshal(records, (int)count, coin_context(64, to_opts(&any)), lane->air.p, lane->dcoin.p,
+                            lane->rstatus.p, lane->stream);
+        HIPCHK(hipMemcpyAsync(airs.data(), lane->air.p, count * sizeof(AirConst), hipMemcpyDeviceToHost, lane->stream));
+        HIPCHK(hipMemcpyAsync(statuses, lane->rstatus.p, count * sizeof(int), hipMemcpyDeviceToHost, lane->stream));
+        HIPCHK(hipStreamSynchronize(lane->stream));
+        for (uint32_t i = 0; i < count; i++)
+            if (statuses[i]) c->err = record_text_of(records + i, statuses[i], true);
+        give();
+        return XFG_OK;
+    });
 }
 
 int xfg_prepare(xfg_ctx* c, uint32_t count, uint64_t trace_length, const xfg_options* opts) {

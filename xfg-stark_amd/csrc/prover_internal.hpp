@@ -76,6 +76,11 @@ struct Lane {
     // that never waits on the caller's pageable memory)
     DBuf<u64> tkeys;
     const u64* h_tkeys = nullptr;
+    // statements as packed records in device memory (xfg_prove_records): rstatus [B] the record kernel's status
+    // per record (launch_burn_marshal); h_rair, h_rstatus the unit's AIR constants and statuses in the replay block
+    DBuf<int> rstatus;
+    const AirConst* h_rair = nullptr;
+    const int* h_rstatus = nullptr;
     HBuf<u64> h_trace;
     std::vector<DBuf<u64>> flayer;
     std::vector<DBuf<Digest>> fnodes;
@@ -134,6 +139,13 @@ struct TraceSrc {
     bool checks() const { return validate || on_device(); }
 };
 
+// a unit's statements as packed records in device memory: p the unit's own slice (null: the jobs carry AIR
+// constants marshalled on the host). The record kernel marshals them at the head of the chain; a record the
+// kernel finds invalid keeps its slot, gets its status after the unit's host steps and no proof
+struct RecordSrc {
+    const xfg_burn_record* p = nullptr;
+};
+
 // a submitted batch: jobs [0, B) proven in units of XFG_UNIT proofs by the lane workers; proof
 // bytes are copied into the caller's buffers on the worker thread as each unit finishes
 struct Batch {
@@ -149,6 +161,9 @@ struct Batch {
     std::vector<int> refused;          // per job: status set at submission (cell >= p), else 0
     std::vector<u64> keys;             // per job: the trace check's word
     xfg_trace_fault* faults = nullptr;  // caller's, filled by wait (may be null)
+    // statements as device records, records.p the batch's base (job k <-> caller index k, as for traces: every
+    // unit's records are the contiguous slice at b0)
+    RecordSrc records;
     u64 n = 0;
     Opts o{};
     Tables T{};
@@ -236,9 +251,16 @@ Tables tables_of(xfg_ctx* c);
 // ---- defined in lane_unit.hip
 Lane* lane0(xfg_ctx* c);
 void ensure_lanes(xfg_ctx* c, size_t k);
-// one work unit: jobs[0, B) with .air filled, proven on the lane's streams and serialised into .bytes
+// one work unit: jobs[0, B) with .air filled (or rs.p: the unit's records, from which the record kernel fills the
+// lane's constants and the host then the jobs'), proven on the lane's streams and serialised into .bytes
 void prove_lane(Lane* c, const Tables& T, const u64* ce_div, ProofJob* jobs, int B, const TraceSrc& ts, u64 n,
-                const Opts& o);
+                const Opts& o, const RecordSrc& rs = RecordSrc{});
+// Context::to_elements of a proof of this shape as the record kernel takes them
+static inline CoinContext coin_context(u64 n, const Opts& o) {
+    CoinContext cx;
+    context_elements(n, o, cx.e);
+    return cx;
+}
 // buffer sizing and launch sets of the proving chain that the debug entry points run too; of the
 // shape they read n, beta and DE only
 void size_trace_lde(Lane* c, size_t B, const ProofShape& sh);        // trace, coef, scratch, lde

@@ -11,7 +11,9 @@ _api: the product API; _hooks: the kernel-level test hooks (XfgBurnMintProver.de
 """
 import ctypes as C  # noqa: F401  (tests and scripts build their own arguments with xfgstark.C)
 
-from ._abi import (HEADER_PATH, LIB_PATH, STATUS, TRACE_ON_DEVICE, TRACE_VALIDATE, XfgStarkError,  # noqa: F401
-                   _Acceptable, _lib, _Options, _TraceFault, _TraceLayout, _u8p, _u64p, exported_symbols)
+from ._abi import (HEADER_PATH, LIB_PATH, RECORD_BYTES, RECORDS_ON_DEVICE, STATUS, TRACE_ON_DEVICE,  # noqa: F401
+                   TRACE_VALIDATE, XfgStarkError, _Acceptable, _BurnRecord, _lib, _Options, _TraceFault, _TraceLayout,
+                   _u8p, _u64p, exported_symbols)
 from ._api import (AcceptableOptions, FieldExtension, PendingBatch, ProofOptions, StarkProof, TraceFault,  # noqa: F401
-                   XfgBurnMintProver, XfgBurnMintVerifier, air_consts, blake3, burn_inputs, record_size)
+                   XfgBurnMintProver, XfgBurnMintVerifier, air_consts, air_consts_from_records, blake3, burn_inputs,
+                   pack_records, record_size, unpack_records)

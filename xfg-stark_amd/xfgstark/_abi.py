@@ -19,6 +19,8 @@ STATUS = {0: "OK", 1: "INVALID_BURN_AMOUNT", 2: "MINT_MISMATCH", 3: "ZERO_TX_HAS
           5: "SHORT_SECRET", 6: "PROVER_ERROR", 7: "DEVICE_ERROR", 8: "BUFFER_TOO_SMALL", 9: "INVALID_ARGUMENT",
           10: "VERIFY_FAILED", 11: "INVALID_TRACE"}
 TRACE_VALIDATE, TRACE_ON_DEVICE = 1, 2  # XFG_TRACE_* flags of xfg_prove_trace_batch
+RECORDS_ON_DEVICE = 1  # XFG_RECORDS_ON_DEVICE of xfg_prove_records
+RECORD_BYTES = 128  # sizeof(xfg_burn_record)
 
 
 class XfgStarkError(Exception):
@@ -49,6 +51,12 @@ class _BurnInputs(C.Structure):
                 ("recipient_address", C.c_char_p), ("recipient_len", C.c_size_t), ("secret", C.c_char_p),
                 ("secret_len", C.c_size_t), ("network_id", C.c_uint32), ("target_chain_id", C.c_uint32),
                 ("commitment_version", C.c_uint32)]
+
+
+class _BurnRecord(C.Structure):
+    _fields_ = [("burn_amount", C.c_uint64), ("mint_amount", C.c_uint64), ("tx_prefix_hash", C.c_uint8 * 32),
+                ("recipient", C.c_uint8 * 20), ("secret", C.c_uint8 * 32), ("network_id", C.c_uint32),
+                ("target_chain_id", C.c_uint32), ("commitment_version", C.c_uint32), ("reserved", C.c_uint8 * 16)]
 
 
 class _AirConsts(C.Structure):
@@ -89,6 +97,7 @@ _TRACE_BATCH = [_ctx, _u32, C.c_void_p, _u32, _u64, _airs, _opts, _u32, _bufs, _
 _layout = C.POINTER(_TraceLayout)
 _accept = C.POINTER(_Acceptable)
 _TRACE_BATCH_STRIDED = [_ctx, _u32, C.c_void_p, _u64, _layout, _airs, _opts, _u32, _bufs, _szp, _intp, _faults]
+_RECORDS = [_ctx, _u32, C.c_void_p, _u64, _opts, _u32, _bufs, _szp, _intp]  # records: host or device memory
 _FRI = [_ctx, _u32, _u32, _u32, _u32, _int]  # count, ext, logn, logbeta, coset_major
 _OOD_TAIL = [_u64p, _u64p, _u64p, _u32p, _u64p, _u64, _u64p, _u64p, _u64p, _u32p, _u64p, _intp]  # from hcoef on
 
@@ -110,6 +119,9 @@ TABLE = [
     ("xfg_check_traces_strided", _int, [_ctx, _u32, C.c_void_p, _u64, _layout, _airs, _u32, _faults]),
     ("xfg_prove_trace_batch_strided", _int, _TRACE_BATCH_STRIDED),
     ("xfg_prove_trace_batch_strided_submit", _int, _TRACE_BATCH_STRIDED + [_u64p]),
+    ("xfg_prove_records", _int, _RECORDS),
+    ("xfg_prove_records_submit", _int, _RECORDS + [_u64p]),
+    ("xfg_air_consts_from_records", _int, [_ctx, _u32, C.c_void_p, _u32, _airs, _intp]),
     ("xfg_prepare", _int, [_ctx, _u32, _u64, _opts]),
     ("xfg_burn_air_consts", _int, [_burn, _airs]),
     ("xfg_proof_parse", _int, [_u8p, _sz, C.POINTER(_ProofInfo), _str, _sz]),
@@ -150,6 +162,7 @@ TABLE = [
     ("xfg_debug_merkle_fri_f", _int, _FRI + [_u32, _u64p, _u8p]),
     ("xfg_debug_grind", _int, [_ctx, _u32, _u32p, _u32, _u64, _u64, _u32, _u32, _u64p]),
     ("xfg_grind_probe", _int, [_ctx, _u32p, _u64p, _u64p]),
+    ("xfg_debug_keccak256", _int, [_ctx, _u32, _u8p, _u32p, _u8p]),
     ("xfg_debug_verify_batch_gpu", _int, [_ctx, _u32, _bufs, _szp, _airs, _opts, _intp, _u64p, _str, _sz]),
     ("xfg_debug_verify_batch_gpu_acceptable", _int, [_ctx, _u32, _bufs, _szp, _airs, _accept, _intp, _u64p, _str, _sz]),
 ]

@@ -4,11 +4,11 @@ import ctypes as C
 import operator
 import sys
 
-from ._abi import (ACCEPT_MIN_CONJECTURED_SECURITY, ACCEPT_OPTION_SET, STATUS, TRACE_ON_DEVICE, TRACE_VALIDATE,
-                   XfgStarkError, _Acceptable, _AirConsts, _BurnInputs, _lib, _Options, _ProofInfo, _TraceFault,
-                   _TraceLayout, _u8p)
+from ._abi import (ACCEPT_MIN_CONJECTURED_SECURITY, ACCEPT_OPTION_SET, RECORD_BYTES, RECORDS_ON_DEVICE, STATUS,
+                   TRACE_ON_DEVICE, TRACE_VALIDATE, XfgStarkError, _Acceptable, _AirConsts, _BurnInputs, _BurnRecord,
+                   _lib, _Options, _ProofInfo, _TraceFault, _TraceLayout, _u8p)
 from ._hooks import KernelHooks
-from ._marshal import air_array, air_struct, array, bytes_ptr, new_buffer, out_slots, ptr, trace_array
+from ._marshal import air_array, air_struct, array, bytes_ptr, new_buffer, out_slots, ptr, trace_array, zeros
 
 
 class TraceFault:
@@ -351,6 +351,76 @@ def air_consts(burn_amount, mint_amount, tx_prefix_hash, recipient_address, secr
     return list(a.pub_inputs), a.nullifier, a.commitment
 
 
+def pack_records(inputs):
+    """dicts of prove_burn_mint kwargs -> their xfg_burn_record's as a [count, 128] uint8 numpy array (the packed
+    records a sharded run scatters). A record has room for exactly a 20-byte recipient and a 32-byte secret:
+    shorter ones are zero-filled and longer ones cut, so statements that depend on either length being refused
+    (statuses 4 and 5) cannot be expressed as records"""
+    out = zeros((len(inputs), RECORD_BYTES), "uint8")
+    for i, kw in enumerate(inputs):
+        tx = bytes(kw["tx_prefix_hash"])
+        if len(tx) != 32:
+            raise XfgStarkError(9, "tx_prefix_hash must be 32 bytes ([u8; 32])")
+        r = _BurnRecord.from_buffer(out[i])
+        r.burn_amount, r.mint_amount = kw["burn_amount"], kw["mint_amount"]
+        r.tx_prefix_hash[:] = tx
+        r.recipient[:] = bytes(kw["recipient_address"]).ljust(20, b"\0")[:20]
+        r.secret[:] = bytes(kw["secret"]).ljust(32, b"\0")[:32]
+        r.network_id = kw.get("network_id", 1)
+        r.target_chain_id = kw.get("target_chain_id", 42161)
+        r.commitment_version = kw.get("commitment_version", 1)
+    return out
+
+
+def unpack_records(records):
+    """the inverse of pack_records: [count, 128] uint8 -> dicts of prove_burn_mint kwargs (the reserved bytes are
+    not part of a statement and are dropped)"""
+    a = array(records, "uint8").reshape(-1, RECORD_BYTES).copy()
+    res = []
+    for row in a:
+        r = _BurnRecord.from_buffer(row)
+        res.append(dict(burn_amount=r.burn_amount, mint_amount=r.mint_amount, tx_prefix_hash=bytes(r.tx_prefix_hash),
+                        recipient_address=bytes(r.recipient), secret=bytes(r.secret), network_id=r.network_id,
+                        target_chain_id=r.target_chain_id, commitment_version=r.commitment_version))
+    return res
+
+
+def _record_view(records, device=None):
+    """the C arguments of `count` records: (object to keep alive, pointer, count, flags). A C-contiguous uint8 numpy
+    array of 128 * count bytes is host memory; a uint8 torch.Tensor must lie on cuda:`device` and goes to the
+    library as it is (its current stream is synchronised first: the data is complete before the lanes read it)"""
+    if hasattr(records, "data_ptr"):  # a torch.Tensor (torch itself is not imported here)
+        t = records
+        if device is None or t.device.type != "cuda" or (t.device.index or 0) != device:
+            raise XfgStarkError(9, f"records tensor is on {t.device}, the prover on device {device}")
+        if str(t.dtype) != "torch.uint8" or not t.is_contiguous() or t.numel() % RECORD_BYTES:
+            raise XfgStarkError(9, "records tensor must be contiguous uint8, 128 bytes per record")
+        if t.numel():
+            import torch
+            torch.cuda.current_stream(t.device).synchronize()
+        return t, t.data_ptr() or None, t.numel() // RECORD_BYTES, RECORDS_ON_DEVICE
+    a = records
+    if not (hasattr(a, "ctypes") and str(a.dtype) == "uint8" and a.flags.c_contiguous and a.size % RECORD_BYTES == 0):
+        raise XfgStarkError(9, "records: a C-contiguous uint8 numpy array of 128 bytes per record, or a tensor")
+    return a, a.ctypes.data or None, a.size // RECORD_BYTES, 0
+
+
+def air_consts_from_records(records, prover=None):
+    """the statement of each record as the verifiers take it (xfg_air_consts_from_records): a list of
+    (public inputs[12], nullifier, commitment), an XfgStarkError in the place of an invalid record. Host records
+    are computed on the host; a tensor on `prover`'s device by the prover's record kernel"""
+    keep, where, count, flags = _record_view(records, getattr(prover, "_device", None))
+    airs, sts = (_AirConsts * max(count, 1))(), (C.c_int * max(count, 1))()
+    if prover is not None:
+        prover._call(_lib.xfg_air_consts_from_records, count, where, flags, airs, sts)
+    else:
+        st = _lib.xfg_air_consts_from_records(None, count, where, flags, airs, sts)
+        if st:
+            raise XfgStarkError(st, STATUS.get(st))
+    return [XfgStarkError(sts[i], STATUS.get(sts[i])) if sts[i] else
+            (list(airs[i].pub_inputs), airs[i].nullifier, airs[i].commitment) for i in range(count)]
+
+
 def record_size(count, trace_length, options):
     """bytes of a fixed-size batch record (XfgBurnMintProver.submit_batch_record): `count` int64
     proof lengths, then `count` slots of xfg_proof_size_bound bytes, proof i at slot i"""
@@ -604,6 +674,34 @@ class XfgBurnMintProver(KernelHooks):
         arr, keep = _burn_array(inputs)
         return self._submit(_lib.xfg_prove_batch_submit, (k, arr, trace_length, C.byref(o)), k, cap,
                             record=addr, owner=owner)
+
+    def submit_records(self, records, trace_length=64):
+        """asynchronous prove_records (xfg_prove_records_submit) -> PendingBatch. records: the statements as packed
+        xfg_burn_record's (pack_records), a C-contiguous uint8 numpy array [count, 128] or a uint8 torch.Tensor of
+        the same bytes on the prover's device. A tensor is read where it lies by the lanes' record kernel: nothing
+        is copied to the host and no statement is marshalled there before the launch. It is referenced by the
+        PendingBatch until the batch has been waited for and must not be written before then. As for
+        prove_traces, torch and the library must share one HIP runtime"""
+        keep, where, count, flags = _record_view(records, self._device)
+        o, cap = self._options._c_and_bound(trace_length)
+        return self._submit(_lib.xfg_prove_records_submit, (count, where, trace_length, C.byref(o), flags), count, cap,
+                            buf=self._take_buffer(cap * count), owner=keep)
+
+    def prove_records(self, records, trace_length=64):
+        """prove_batch for packed records (host array or device tensor, see submit_records) -> list of
+        StarkProof | XfgStarkError (per proof): the same proofs and statuses as prove_batch(unpack_records(...))"""
+        return self.submit_records(records, trace_length).result()
+
+    def air_consts_from_records(self, records):
+        """air_consts_from_records(records) with a tensor on this prover's device going through the record kernel
+        (refused while batches are pending)"""
+        return air_consts_from_records(records, prover=self)
+
+    def last_error(self):
+        """the text of the last failing call or proof on this context (xfg_last_error), "" when there is none"""
+        buf = C.create_string_buffer(1024)
+        _lib.xfg_last_error(self._ctx, buf, 1024)
+        return buf.value.decode()
 
     def _trace_view(self, traces, airs):
         """the C arguments of a batch of traces of logical shape [count][7][n]: (objects to keep alive, pointer,

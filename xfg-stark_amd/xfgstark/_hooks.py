@@ -25,6 +25,21 @@ class KernelHooks:
         self._call(_lib.xfg_debug_lde_skip, ptr(c), c.shape[0], n, blowup, ptr(f, _u8p), ptr(out))
         return out
 
+    def debug_keccak256(self, messages):
+        """Keccak-256 of single-block messages (each at most 135 bytes) by the record kernel's permutation
+        (xfg_debug_keccak256) -> list of 32-byte digests"""
+        k = len(messages)
+        msgs, lens = zeros((max(k, 1), 136), "uint8"), zeros((max(k, 1),), "uint32")
+        for i, m in enumerate(messages):
+            if len(m) > 135:
+                raise XfgStarkError(9, "debug_keccak256: a message is one block, at most 135 bytes")
+            msgs[i, :len(m)] = list(m)
+            msgs[i, len(m):] = 0xA5  # never read
+            lens[i] = len(m)
+        out = zeros((max(k, 1), 32), "uint8")
+        self._call(_lib.xfg_debug_keccak256, k, ptr(msgs, _u8p), ptr(lens, _u32p), ptr(out, _u8p))
+        return [out[i].tobytes() for i in range(k)]
+
     def debug_const_columns(self, trace):
         """the prover's constant-column detection: trace [B,width,n] -> flags [B,width] (1 = one value in every row)"""
         tr = array(trace)
