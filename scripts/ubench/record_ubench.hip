@@ -4,7 +4,7 @@
 //     records resident in device memory: HIP events around `reps` back-to-back launches on an otherwise idle stream
 //     after 20 warm ones, best and median of 5 windows, microseconds per launch. Its outputs are compared with the
 //     host marshalling first.
-// (2) marshal() (xfg-stark_amd/csrc/marshal.hpp: validation, marshalling, four Keccak-256) of the same 32 statements
+// (2) marshal() (xfg-stark_amd/csrc/marshal.hpp: validation, the statement as a record, four Keccak-256) of the same 32 statements
 //     on the host pool, as xfg_prove_batch_submit runs it on the submitting thread: a host clock around each of 200
 //     parallel_for calls after 20 warm ones, best and median, microseconds per call.
 //
@@ -33,7 +33,7 @@ int main(int argc, char** argv) {
             x ^= x << 13, x ^= x >> 7, x ^= x << 17;
             b[i] = (uint8_t)x;
         }
-        r.burn_amount = r.mint_amount = STANDARD_BURN;
+        r.burn_amount = r.mint_amount = REC_STANDARD_BURN;
         r.tx_prefix_hash[0] |= 1;
         memset(r.reserved, 0, sizeof r.reserved);
     }

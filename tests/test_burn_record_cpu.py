@@ -1,7 +1,8 @@
 """Packed burn records on the CPU (xfg-stark_amd/csrc/burn_record.hpp and the host side of the record entries).
 
-tests/sanitize/burn_record.cpp is a stand-alone program: the record's size and offsets, record_to_inputs, the
-validation order, the four Keccak message layouts against marshal.hpp and the padding words (see its header).
+tests/sanitize/burn_statement.cpp is a stand-alone program: the record's size and offsets, record_to_inputs, the
+validation order of both statement forms, the length rules of xfg_burn_inputs, the four Keccak message layouts and
+the one host marshaller (marshal.hpp) against its own hand-written marshalling, the padding words (see its header).
 Here it is built with ASan + UBSan (`make -C xfg-stark_amd sanitize`) and the binary is run directly: exit 0,
 nothing from a sanitizer. The rest needs no device: pack_records / unpack_records, and
 xfg_air_consts_from_records on host records against xfg_burn_air_consts, the oracle and the golden vectors."""
@@ -19,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "xfg-stark_amd")
 SAN_ENV = dict(ASAN_OPTIONS="halt_on_error=1:abort_on_error=0:detect_leaks=1:exitcode=77",
                UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1:exitcode=78")
-TARGET = "build/asan/burn_record"
+TARGET = "build/asan/burn_statement"
 IDS = dict(network_id=1, target_chain_id=42161, commitment_version=1)
 
 
@@ -29,12 +30,12 @@ def test_driver_is_clean_under_the_sanitizer():
                        env=dict(os.environ, **SAN_ENV))
     assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
     assert r.stderr == "", r.stderr[-4000:]
-    assert r.stdout == "burn_record ok\n"
+    assert r.stdout == "burn_statement ok\n"
 
 
 def test_sanitize_target_builds_the_driver():
     subprocess.run(["make", "-s", "-C", LIB, "sanitize"], check=True)
-    assert os.path.exists(os.path.join(LIB, "build", "asan", "burn_record"))
+    assert os.path.exists(os.path.join(LIB, "build", "asan", "burn_statement"))
 
 
 def _inputs(count, **over):

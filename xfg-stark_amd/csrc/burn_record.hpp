@@ -1,7 +1,11 @@
 // A burn statement as a packed record (xfg_burn_record, 128 bytes): its view as xfg_burn_inputs, its validation,
-// the marshalling of its public inputs and the byte layouts of the four Keccak-256 messages of a statement, each
-// stated once for the host path (marshal.hpp marshal_record), the record kernel (burn_record.hip) and the driver
-// tests/sanitize/burn_record.cpp. Pure functions, no HIP: the header compiles with a plain host compiler.
+// the marshalling of its public inputs and the byte layouts of the four Keccak-256 messages of a statement. This
+// header is the one statement of the validation order, the error texts and the message layouts: the host
+// marshaller (marshal.hpp marshal_record, which xfg_burn_inputs go through as a record too) and the record kernel
+// (burn_record.hip) both read them here, and tests/sanitize/burn_statement.cpp checks them against a hand-written
+// copy of its own. Which function adds which rule: statement_status the three checks every statement has,
+// record_status the record's reserved bytes behind them, marshal() (marshal.hpp) the lengths of an input's
+// recipient and secret. Pure functions, no HIP: the header compiles with a plain host compiler.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -26,7 +30,7 @@ static_assert(offsetof(xfg_burn_record, burn_amount) == 0 && offsetof(xfg_burn_r
                   offsetof(xfg_burn_record, commitment_version) == 108 && offsetof(xfg_burn_record, reserved) == 112,
               "the layout of the packed records a sharded run scatters");
 
-constexpr uint64_t REC_STANDARD_BURN = 8000000ULL, REC_LARGE_BURN = 8000000000ULL;  // marshal.hpp STANDARD_BURN, LARGE_BURN
+constexpr uint64_t REC_STANDARD_BURN = 8000000ULL, REC_LARGE_BURN = 8000000000ULL;  // 0.8 XFG and 800 XFG
 
 XFG_HD inline uint64_t rec_le32(const uint8_t* b) {
     return (uint64_t)b[0] | ((uint64_t)b[1] << 8) | ((uint64_t)b[2] << 16) | ((uint64_t)b[3] << 24);
@@ -50,17 +54,22 @@ inline xfg_burn_inputs record_to_inputs(const xfg_burn_record& r) {
     return in;
 }
 
-// validate_inputs on a record, in marshal()'s order: the first check that fails is the status. The recipient and
-// the secret have their lengths by construction; a non-zero reserved byte comes last
+// validate_inputs (src/burn_mint_prover.rs:132-221) on what every statement has, inputs and records alike: the
+// first check that fails is the status. tx_legacy: the first 8 bytes of the tx hash as a LE u64
+XFG_HD inline int statement_status(uint64_t burn_amount, uint64_t mint_amount, uint64_t tx_legacy) {
+    if (burn_amount != REC_STANDARD_BURN && burn_amount != REC_LARGE_BURN) return XFG_INVALID_BURN_AMOUNT;
+    if (mint_amount != burn_amount) return XFG_MINT_MISMATCH;
+    return tx_legacy == 0 ? XFG_ZERO_TX_HASH : XFG_OK;
+}
+// a record: the recipient and the secret have their lengths by construction; the record's own rule, a non-zero
+// reserved byte, comes last
 XFG_HD inline int record_status(const xfg_burn_record& r) {
-    if (r.burn_amount != REC_STANDARD_BURN && r.burn_amount != REC_LARGE_BURN) return XFG_INVALID_BURN_AMOUNT;
-    if (r.mint_amount != r.burn_amount) return XFG_MINT_MISMATCH;
-    if (rec_le64(r.tx_prefix_hash) == 0) return XFG_ZERO_TX_HASH;
+    if (const int st = statement_status(r.burn_amount, r.mint_amount, rec_le64(r.tx_prefix_hash))) return st;
     uint8_t any = 0;
     for (int i = 0; i < 16; i++) any |= r.reserved[i];
     return any ? XFG_INVALID_ARGUMENT : XFG_OK;
 }
-// the text marshal() gives for that status (the mint mismatch names the record's two amounts)
+// the text of such a status, the reference's (the mint mismatch names the statement's two amounts)
 inline std::string record_status_text(int status, uint64_t burn_amount, uint64_t mint_amount) {
     switch (status) {
         case XFG_INVALID_BURN_AMOUNT:
@@ -74,7 +83,7 @@ inline std::string record_status_text(int status, uint64_t burn_amount, uint64_t
     }
 }
 
-// the 12 public inputs as marshal() forms them, every one a 32-bit value (hence a canonical field element), for
+// the 12 public inputs as prove_burn_mint forms them, every one a 32-bit value (hence a canonical field element), for
 // an invalid record too; pub[3], the recipient hash, is left 0 for the caller to fill in. The secret's field
 // element is the first four bytes of the secret
 XFG_HD inline void record_public_inputs(const xfg_burn_record& r, uint64_t pub[12]) {
@@ -147,8 +156,11 @@ XFG_HD inline uint64_t keccak_pad_word(unsigned i, unsigned len) {
     if (i == KECCAK_RATE / 8 - 1) w ^= 0x80ULL << 56;
     return w;
 }
-// the message as bytes (host): out[136] zero-filled past the length, which is returned
+// the message as bytes (host): out[136] zero-filled past the length, which is returned. Unrolled in full: with
+// `which` a constant at the call, every byte's comparisons fold away and the stores merge into whole fields, which
+// puts the host marshaller on the submitting thread level with one that copies the fields in by hand
 inline unsigned burn_msg_bytes(int which, const BurnMsgSrc& s, uint8_t out[KECCAK_RATE]) {
+#pragma GCC unroll 136
     for (unsigned k = 0; k < KECCAK_RATE; k++) out[k] = burn_msg_byte(which, k, s);
     return burn_msg_len(which);
 }

@@ -134,6 +134,15 @@ const u64* grind_search(Lane* c, int B, unsigned grind, u64 first, u64 max_nonce
     return c->h_gnonce.p;
 }
 
+// the job's host coin at the start of its transcript: Context::to_elements || public inputs (ProverChannel::new)
+static void seed_coin(ProofJob& j, const ProofShape& sh, const Opts& o) {
+    u64 e[20];
+    context_elements(sh.n, o, e);
+    memcpy(e + 8, j.air.pub, 12 * 8);
+    j.coin.init(e, 20);
+    j.commitments.clear();
+}
+
 // AIR constants and transcript seeds of the unit's proofs, on the host and on the device.
 // The Fiat-Shamir steps between the commitments (coefficient, OOD point, DEEP and FRI alpha
 // draws) run on the device from a copy of each proof's coin, so the whole chain from the trace
@@ -151,15 +160,10 @@ static void upload_unit_inputs(Lane* c, ProofJob* jobs, int B, const ProofShape&
     AirConst* airs = c->h_air.ensure(B);
     for (int b = 0; b < B; b++) airs[b] = jobs[b].air;
     upload(c->air.p, airs, B * sizeof(AirConst), s);
-    // transcript seed: Context::to_elements || public inputs (ProverChannel::new)
     DevCoin* hc = c->h_coin.ensure(B);
     for (int b = 0; b < B; b++) {
         ProofJob& j = jobs[b];
-        u64 e[20];
-        context_elements(sh.n, o, e);
-        memcpy(e + 8, j.air.pub, 12 * 8);
-        j.coin.init(e, 20);
-        j.commitments.clear();
+        seed_coin(j, sh, o);
         hc[b].seed = j.coin.seed;
         hc[b].counter = j.coin.counter;
         hc[b].pad = 0;
@@ -172,13 +176,8 @@ static void upload_unit_inputs(Lane* c, ProofJob* jobs, int B, const ProofShape&
 // device's draws, and with them the seed the record kernel computed, against this coin
 static void adopt_record_inputs(const Lane* c, ProofJob* jobs, int B, const ProofShape& sh, const Opts& o) {
     host_pool().parallel_for(B, [c, jobs, &sh, &o](int b) {
-        ProofJob& j = jobs[b];
-        j.air = c->h_rair[b];
-        u64 e[20];
-        context_elements(sh.n, o, e);
-        memcpy(e + 8, j.air.pub, 12 * 8);
-        j.coin.init(e, 20);
-        j.commitments.clear();
+        jobs[b].air = c->h_rair[b];
+        seed_coin(jobs[b], sh, o);
     });
 }
 

@@ -132,7 +132,7 @@ static void note_status(xfg_ctx* c, const Batch& b, size_t k) {
                                          : "Prover error: proof generation failed (degenerate transcript or DEEP degree)";
 }
 
-// the text of an invalid record's status as marshal() words it; the two amounts a mint mismatch names are read
+// the text of an invalid record's status as the host marshaller words it; the two amounts a mint mismatch names are read
 // from the caller's record (device memory of the current device: one 16-byte copy)
 static std::string record_text_of(const xfg_burn_record* rec, int status, bool on_device) {
     uint64_t amounts[2] = {0, 0};  // burn, mint: the record's first two words
@@ -141,6 +141,40 @@ static std::string record_text_of(const xfg_burn_record* rec, int status, bool o
         else memcpy(amounts, rec, sizeof amounts);
     }
     return record_status_text(status, amounts[0], amounts[1]);
+}
+
+// `count` host statements, their arguments and options checked (xfg_prove_batch_submit, host records): validation
+// and marshalling (four Keccak-256 per proof) through marshal_one(i, air, text) on the host pool, since the
+// submitting thread is the start of every batch's latency; the valid statements become the batch's jobs.
+// zero_refused: an invalid statement's out_lens[i] is set to 0 (records) or left as the caller gave it (inputs)
+template <class Marshal>
+static int submit_statements(xfg_ctx* c, uint32_t count, Marshal marshal_one, bool zero_refused, u64 n, const Opts& o,
+                             uint8_t* const* outs, size_t* out_lens, int* statuses, uint64_t* ticket) {
+    return guarded(c, [&]() -> int {
+        HIPCHK(hipSetDevice(c->device));
+        std::unique_ptr<Batch> bp(new Batch());
+        std::vector<AirConst> airs(count);
+        std::vector<std::string> errs(count);
+        host_pool().parallel_for((int)count, [&](int i) { statuses[i] = marshal_one((uint32_t)i, airs[i], errs[i]); });
+        for (uint32_t i = 0; i < count; i++) {
+            if (statuses[i]) {
+                c->err = errs[i];
+                if (zero_refused) out_lens[i] = 0;
+                continue;
+            }
+            bp->jobs.emplace_back();
+            bp->jobs.back().air = airs[i];
+            bp->which.push_back(i);
+        }
+        const std::vector<Unit> units = split_units(c, (int)bp->jobs.size(), o.beta);
+        *ticket = submit_batch(c, std::move(bp), n, o, count, outs, out_lens, statuses, units);
+        return XFG_OK;
+    });
+}
+
+// a synchronous entry behind its _submit: what the submission returned, or else the wait for its ticket
+static int wait_submitted(xfg_ctx* c, int submitted, uint64_t ticket) {
+    return submitted ? submitted : xfg_batch_wait(c, ticket);
 }
 
 }  // namespace xfg
@@ -205,11 +239,8 @@ int xfg_burn_air_consts(const xfg_burn_inputs* in, xfg_air_consts* out) {
     if (!in || !out) return XFG_INVALID_ARGUMENT;
     AirConst a;
     std::string err;
-    int st = marshal(in, a, err);
-    if (st) return st;
-    memcpy(out->pub_inputs, a.pub, sizeof a.pub);
-    out->nullifier = a.nullifier;
-    out->commitment = a.commitment;
+    if (int st = marshal(in, a, err)) return st;
+    air_out(a, out);
     return XFG_OK;
 }
 
@@ -297,27 +328,8 @@ int xfg_prove_batch_submit(xfg_ctx* c, uint32_t count, const xfg_burn_inputs* in
     u64 n = trace_length ? trace_length : 64;
     Opts o = to_opts(opts);
     if (int st = check_request(c, n, o)) return st;
-    return guarded(c, [&]() -> int {
-        HIPCHK(hipSetDevice(c->device));
-        std::unique_ptr<Batch> bp(new Batch());
-        // validation + marshalling (three Keccak-256 per proof) per input on the host pool: the
-        // submitting thread is the start of every batch's latency
-        std::vector<AirConst> airs(count);
-        std::vector<std::string> errs(count);
-        host_pool().parallel_for((int)count, [&](int i) { statuses[i] = marshal(&inputs[i], airs[i], errs[i]); });
-        for (uint32_t i = 0; i < count; i++) {
-            if (statuses[i]) {
-                c->err = errs[i];
-                continue;
-            }
-            bp->jobs.emplace_back();
-            bp->jobs.back().air = airs[i];
-            bp->which.push_back(i);
-        }
-        const std::vector<Unit> units = split_units(c, (int)bp->jobs.size(), o.beta);
-        *ticket = submit_batch(c, std::move(bp), n, o, count, outs, out_lens, statuses, units);
-        return XFG_OK;
-    });
+    auto marshal_one = [inputs](uint32_t i, AirConst& a, std::string& err) { return marshal(&inputs[i], a, err); };
+    return submit_statements(c, count, marshal_one, false, n, o, outs, out_lens, statuses, ticket);
 }
 
 int xfg_batch_wait(xfg_ctx* c, uint64_t ticket) {
@@ -355,48 +367,44 @@ int xfg_batch_wait(xfg_ctx* c, uint64_t ticket) {
 int xfg_prove_batch(xfg_ctx* c, uint32_t count, const xfg_burn_inputs* inputs, uint64_t trace_length,
                     const xfg_options* opts, uint8_t* const* outs, size_t* out_lens, int* statuses) {
     uint64_t t = 0;
-    int r = xfg_prove_batch_submit(c, count, inputs, trace_length, opts, outs, out_lens, statuses, &t);
-    if (r) return r;
-    return xfg_batch_wait(c, t);
+    const int r = xfg_prove_batch_submit(c, count, inputs, trace_length, opts, outs, out_lens, statuses, &t);
+    return wait_submitted(c, r, t);
 }
 
-// XFG_TRACE_ON_DEVICE: `traces` must be device memory of the context's device that this process's HIP
-// runtime allocated, and the allocation must hold all `bytes` (the lanes copy that range). Returns what
-// is wrong, or null. Asks the runtime only: nothing is launched or copied (device_range: the questions themselves,
-// shared with the records of XFG_RECORDS_ON_DEVICE)
-enum DeviceRange { RANGE_OK, RANGE_UNKNOWN, RANGE_NOT_DEVICE, RANGE_TOO_SMALL };
-static DeviceRange device_range(xfg_ctx* c, const void* p, size_t bytes) {
+// XFG_TRACE_ON_DEVICE, XFG_RECORDS_ON_DEVICE: p (`noun` in the texts) must be device memory of the context's device
+// that this process's HIP runtime allocated, and the allocation must hold all `bytes` (the lanes read that range).
+// False, with what is wrong in c->err, otherwise. Asks the runtime only: nothing is launched or copied
+static bool device_range_ok(xfg_ctx* c, const void* p, size_t bytes, const char* noun, const char* too_small) {
+    static const char* const UNKNOWN = " is not a device pointer known to the library's HIP runtime";
     hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return RANGE_UNKNOWN;
-    }
-    if (a.type != hipMemoryTypeDevice || a.device != c->device) return RANGE_NOT_DEVICE;
     hipDeviceptr_t base = nullptr;
     size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
         (void)hipGetLastError();
-        return RANGE_UNKNOWN;
+        c->err = std::string(noun) + UNKNOWN;
+    } else if (a.type != hipMemoryTypeDevice || a.device != c->device) {
+        c->err = std::string(noun) + " is not device memory of the context's device";
+    } else if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
+        (void)hipGetLastError();
+        c->err = std::string(noun) + UNKNOWN;
+    } else if ((const char*)p + bytes > (const char*)base + size) {
+        c->err = too_small;
+    } else {
+        return true;
     }
-    return (const char*)p + bytes > (const char*)base + size ? RANGE_TOO_SMALL : RANGE_OK;
+    return false;
 }
-static const char* device_traces_problem(xfg_ctx* c, const void* traces, size_t bytes) {
-    switch (device_range(c, traces, bytes)) {
-        case RANGE_UNKNOWN: return "traces is not a device pointer known to the library's HIP runtime";
-        case RANGE_NOT_DEVICE: return "traces is not device memory of the context's device";
-        case RANGE_TOO_SMALL: return "the device allocation is smaller than [count][7][n] traces";
-        default: return nullptr;
-    }
+static bool device_traces_ok(xfg_ctx* c, const void* traces, size_t bytes) {
+    return device_range_ok(c, traces, bytes, "traces", "the device allocation is smaller than [count][7][n] traces");
 }
-// XFG_RECORDS_ON_DEVICE: the same for `count` records, which the record kernel reads as 8-byte words
-static const char* device_records_problem(xfg_ctx* c, const xfg_burn_record* records, uint32_t count) {
-    if ((uintptr_t)records % alignof(xfg_burn_record)) return "records is not 8-byte aligned";
-    switch (device_range(c, records, (size_t)count * sizeof(xfg_burn_record))) {
-        case RANGE_UNKNOWN: return "records is not a device pointer known to the library's HIP runtime";
-        case RANGE_NOT_DEVICE: return "records is not device memory of the context's device";
-        case RANGE_TOO_SMALL: return "the device allocation is smaller than 128 * count bytes of records";
-        default: return nullptr;
+// `count` records, which the record kernel reads as 8-byte words
+static bool device_records_ok(xfg_ctx* c, const xfg_burn_record* records, uint32_t count) {
+    if ((uintptr_t)records % alignof(xfg_burn_record)) {
+        c->err = "records is not 8-byte aligned";
+        return false;
     }
+    return device_range_ok(c, records, (size_t)count * sizeof(xfg_burn_record), "records",
+                           "the device allocation is smaller than 128 * count bytes of records");
 }
 
 // the dense layout passes for every n and count that the checks in front of it let through (submit_trace_batch:
@@ -435,10 +443,7 @@ static int submit_trace_batch(xfg_ctx* c, uint32_t count, const uint64_t* traces
     }
     return guarded(c, [&]() -> int {
         HIPCHK(hipSetDevice(c->device));
-        if (const char* m = dev ? device_traces_problem(c, traces, (size_t)extent * 8) : nullptr) {
-            c->err = m;
-            return XFG_INVALID_ARGUMENT;
-        }
+        if (dev && !device_traces_ok(c, traces, (size_t)extent * 8)) return XFG_INVALID_ARGUMENT;
         std::unique_ptr<Batch> bp(new Batch());
         bp->jobs.resize(count);
         bp->which.resize(count);
@@ -485,10 +490,9 @@ int xfg_prove_trace_batch(xfg_ctx* c, uint32_t count, const uint64_t* traces, ui
                           const xfg_air_consts* airs, const xfg_options* opts, uint32_t flags, uint8_t* const* outs,
                           size_t* out_lens, int* statuses, xfg_trace_fault* faults) {
     uint64_t t = 0;
-    int r = xfg_prove_trace_batch_submit(c, count, traces, width, n, airs, opts, flags, outs, out_lens, statuses,
-                                         faults, &t);
-    if (r) return r;
-    return xfg_batch_wait(c, t);
+    const int r = xfg_prove_trace_batch_submit(c, count, traces, width, n, airs, opts, flags, outs, out_lens, statuses,
+                                               faults, &t);
+    return wait_submitted(c, r, t);
 }
 
 int xfg_prove_trace_batch_strided_submit(xfg_ctx* c, uint32_t count, const uint64_t* traces, uint64_t n,
@@ -504,10 +508,9 @@ int xfg_prove_trace_batch_strided(xfg_ctx* c, uint32_t count, const uint64_t* tr
                                   uint32_t flags, uint8_t* const* outs, size_t* out_lens, int* statuses,
                                   xfg_trace_fault* faults) {
     uint64_t t = 0;
-    int r = xfg_prove_trace_batch_strided_submit(c, count, traces, n, layout, airs, opts, flags, outs, out_lens, statuses,
-                                                 faults, &t);
-    if (r) return r;
-    return xfg_batch_wait(c, t);
+    const int r = xfg_prove_trace_batch_strided_submit(c, count, traces, n, layout, airs, opts, flags, outs, out_lens,
+                                                       statuses, faults, &t);
+    return wait_submitted(c, r, t);
 }
 
 // xfg_check_traces (L: the dense layout) and xfg_check_traces_strided
@@ -536,10 +539,7 @@ static int check_traces(xfg_ctx* c, uint32_t count, const uint64_t* traces, uint
         return XFG_INVALID_ARGUMENT;
     }
     return on_lane0(c, [&](Lane* lane) -> int {
-        if (const char* m = src.on_device() ? device_traces_problem(c, traces, (size_t)extent * 8) : nullptr) {
-            c->err = m;
-            return XFG_INVALID_ARGUMENT;
-        }
+        if (src.on_device() && !device_traces_ok(c, traces, (size_t)extent * 8)) return XFG_INVALID_ARGUMENT;
         const int logn = (int)ilog2(n);
         lane->air.ensure(count);
         lane->tkeys.ensure(count);
@@ -602,40 +602,23 @@ int xfg_prove_records_submit(xfg_ctx* c, uint32_t count, const xfg_burn_record* 
     const u64 n = trace_length ? trace_length : 64;
     const Opts o = to_opts(opts);
     if (int st = check_request(c, n, o)) return st;
+    if (!(flags & XFG_RECORDS_ON_DEVICE)) {
+        auto marshal_one = [records](uint32_t i, AirConst& a, std::string& err) { return marshal_record(records[i], a, err); };
+        return submit_statements(c, count, marshal_one, true, n, o, outs, out_lens, statuses, ticket);
+    }
     return guarded(c, [&]() -> int {
         HIPCHK(hipSetDevice(c->device));
+        if (!device_records_ok(c, records, count)) return XFG_INVALID_ARGUMENT;
+        // every record keeps its slot: the units' kernels validate and marshal them, nothing is read here
         std::unique_ptr<Batch> bp(new Batch());
-        if (flags & XFG_RECORDS_ON_DEVICE) {
-            if (const char* m = device_records_problem(c, records, count)) {
-                c->err = m;
-                return XFG_INVALID_ARGUMENT;
-            }
-            // every record keeps its slot: the units' kernels validate and marshal them, nothing is read here
-            bp->jobs.resize(count);
-            bp->which.resize(count);
-            for (uint32_t i = 0; i < count; i++) {
-                bp->which[i] = i;
-                statuses[i] = XFG_OK;
-            }
-            bp->records.p = records;
-        } else {
-            // as xfg_prove_batch_submit: validated and marshalled on the host pool, the valid ones become jobs
-            std::vector<AirConst> airs(count);
-            std::vector<std::string> errs(count);
-            host_pool().parallel_for((int)count, [&](int i) { statuses[i] = marshal_record(records[i], airs[i], errs[i]); });
-            for (uint32_t i = 0; i < count; i++) {
-                if (statuses[i]) {
-                    c->err = errs[i];
-                    out_lens[i] = 0;
-                    continue;
-                }
-                bp->jobs.emplace_back();
-                bp->jobs.back().air = airs[i];
-                bp->which.push_back(i);
-            }
+        bp->jobs.resize(count);
+        bp->which.resize(count);
+        for (uint32_t i = 0; i < count; i++) {
+            bp->which[i] = i;
+            statuses[i] = XFG_OK;
         }
-        const std::vector<Unit> units = split_units(c, (int)bp->jobs.size(), o.beta);
-        *ticket = submit_batch(c, std::move(bp), n, o, count, outs, out_lens, statuses, units);
+        bp->records.p = records;
+        *ticket = submit_batch(c, std::move(bp), n, o, count, outs, out_lens, statuses, split_units(c, (int)count, o.beta));
         return XFG_OK;
     });
 }
@@ -643,9 +626,8 @@ int xfg_prove_records_submit(xfg_ctx* c, uint32_t count, const xfg_burn_record* 
 int xfg_prove_records(xfg_ctx* c, uint32_t count, const xfg_burn_record* records, uint64_t trace_length,
                       const xfg_options* opts, uint32_t flags, uint8_t* const* outs, size_t* out_lens, int* statuses) {
     uint64_t t = 0;
-    int r = xfg_prove_records_submit(c, count, records, trace_length, opts, flags, outs, out_lens, statuses, &t);
-    if (r) return r;
-    return xfg_batch_wait(c, t);
+    const int r = xfg_prove_records_submit(c, count, records, trace_length, opts, flags, outs, out_lens, statuses, &t);
+    return wait_submitted(c, r, t);
 }
 
 int xfg_air_consts_from_records(xfg_ctx* c, uint32_t count, const xfg_burn_record* records, uint32_t flags,
@@ -657,25 +639,16 @@ int xfg_air_consts_from_records(xfg_ctx* c, uint32_t count, const xfg_burn_recor
         return XFG_INVALID_ARGUMENT;
     }
     std::vector<AirConst> airs(count);
-    auto give = [&] {
-        for (uint32_t i = 0; i < count; i++) {
-            memcpy(airs_out[i].pub_inputs, airs[i].pub, sizeof airs[i].pub);
-            airs_out[i].nullifier = airs[i].nullifier;
-            airs_out[i].commitment = airs[i].commitment;
-        }
-    };
     if (!dev) {
         std::string err;
-        for (uint32_t i = 0; i < count; i++)
+        for (uint32_t i = 0; i < count; i++) {
             if ((statuses[i] = marshal_record(records[i], airs[i], err)) && c) c->err = err;
-        give();
+            air_out(airs[i], &airs_out[i]);
+        }
         return XFG_OK;
     }
     return on_lane0(c, [&](Lane* lane) -> int {
-        if (const char* m = device_records_problem(c, records, count)) {
-            c->err = m;
-            return XFG_INVALID_ARGUMENT;
-        }
+        if (!device_records_ok(c, records, count)) return XFG_INVALID_ARGUMENT;
         lane->air.ensure(count);
         lane->dcoin.ensure(count);
         lane->rstatus.ensure(count);
@@ -687,9 +660,10 @@ int xfg_air_consts_from_records(xfg_ctx* c, uint32_t count, const xfg_burn_recor
         HIPCHK(hipMemcpyAsync(airs.data(), lane->air.p, count * sizeof(AirConst), hipMemcpyDeviceToHost, lane->stream));
         HIPCHK(hipMemcpyAsync(statuses, lane->rstatus.p, count * sizeof(int), hipMemcpyDeviceToHost, lane->stream));
         HIPCHK(hipStreamSynchronize(lane->stream));
-        for (uint32_t i = 0; i < count; i++)
+        for (uint32_t i = 0; i < count; i++) {
             if (statuses[i]) c->err = record_text_of(records + i, statuses[i], true);
-        give();
+            air_out(airs[i], &airs_out[i]);
+        }
         return XFG_OK;
     });
 }
@@ -704,20 +678,17 @@ int xfg_prepare(xfg_ctx* c, uint32_t count, uint64_t trace_length, const xfg_opt
         HIPCHK(hipSetDevice(c->device));
         // two throw-away proving passes over a fixed valid statement size every lane workspace
         // (device + pinned host) and load every code object; nothing is cached between proofs
-        xfg_burn_inputs in{};
-        in.burn_amount = in.mint_amount = STANDARD_BURN;
-        for (int i = 0; i < 32; i++) in.tx_prefix_hash[i] = (uint8_t)(i + 1);
-        static const uint8_t rcpt[20] = {1}, sec[32] = {2};
-        in.recipient_address = rcpt;
-        in.recipient_len = 20;
-        in.secret = sec;
-        in.secret_len = 32;
-        in.network_id = 1;
-        in.target_chain_id = 42161;
-        in.commitment_version = 1;
+        xfg_burn_record r{};
+        r.burn_amount = r.mint_amount = REC_STANDARD_BURN;
+        for (int i = 0; i < 32; i++) r.tx_prefix_hash[i] = (uint8_t)(i + 1);
+        r.recipient[0] = 1;
+        r.secret[0] = 2;
+        r.network_id = 1;
+        r.target_chain_id = 42161;
+        r.commitment_version = 1;
         AirConst a;
         std::string err;
-        if (marshal(&in, a, err)) return XFG_PROVER_ERROR;
+        if (marshal_record(r, a, err)) return XFG_PROVER_ERROR;
         // every lane proves one full unit, twice (lane-pinned units)
         ensure_workers(c);
         const int nl = (int)c->workers.size(), U = std::min<int>((int)count, unit_size(o.beta));

@@ -307,6 +307,13 @@ static inline bool air_canonical(const xfg_air_consts* a) {
     return all_canonical(a->pub_inputs, 12) && a->nullifier < P && a->commitment < P;
 }
 
+// air_of (verifier.hpp) the other way round: the kernels' constants as a caller reads them
+static inline void air_out(const AirConst& a, xfg_air_consts* out) {
+    memcpy(out->pub_inputs, a.pub, sizeof a.pub);
+    out->nullifier = a.nullifier;
+    out->commitment = a.commitment;
+}
+
 // `count` AIR constants of a caller as the kernels take them, into out; false, with the text in c->err, when
 // one is not canonical (the constraint kernel subtracts them from trace values). up: copied to that lane's
 // c->air as well, before the call returns
